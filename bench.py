@@ -14,10 +14,15 @@ Launch: `python bench.py` (1 GPU), `python bench.py --gpus N` (starts the N rank
 `python -m torch.distributed.run --nproc-per-node N bench.py ...`, rank 0's JSON line relayed), or that torchrun
 command directly (one scene per rank, weak scaling, a single RCCL all-gather of the per-rank metric record
 at the end).  The N-rank job replaces the reference's sequential scene loop, bash_scripts/batch_llff_train.sh:24-47.
+
+A plain run sets up, warms up, times `--steps` steps and prints the result line.  Everything else the benchmark measures
+(the HIP-event kernel trace and the rooflines read from it, the two-pass mix, the sub-benchmarks, the CPU baselines) runs
+only with `--full`.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32).
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import math
 import os
@@ -75,6 +80,10 @@ def parse():
     ap.add_argument("--trace-steps", type=int, default=1,
                     help="how many of the timed steps (the last ones) carry the HIP-event kernel timing")
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: kernel trace + rooflines, two-pass mix, sub-benchmarks, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, at most 64 MB)")
     return ap.parse_args()
 
 
@@ -101,12 +110,15 @@ class RasterLoop:
         self.loss_kind = args.loss
         self.P = 0
 
-    def iteration(self):
+    def iteration(self, keep: bool = False):
         from syn3r_amd.gs.train_ops import l1_loss, photometric_loss
         p = self.p
         color, radii, depth, alpha = self.rast(p["m"], self.m2, p["o"], shs=p["sh"], scales=p["s"], rotations=p["q"])
         loss = l1_loss(color, self.target) if self.loss_kind == "l1" else photometric_loss(color, self.target, 0.2)
         loss.backward()
+        if keep:        # --dump-outputs: what a caller of the iteration receives (references only, read after the timed region)
+            self.last = dict(loss=loss, color=color, radii=radii, depth=depth, alpha=alpha, grad_means2D=self.m2.grad,
+                             **{f"grad_{k}": p[k].grad for k in ("m", "s", "q", "o", "sh")})
         for t in list(p.values()) + [self.m2]:
             t.grad = None
         return loss
@@ -461,6 +473,35 @@ def sub_benchmarks(args, dev, loop_a, loop_b, log):
     return out
 
 
+DUMP_BUDGET_BYTES = 60_000_000      # array data; with the .npy headers the files stay under 64 MB
+
+
+def dump_outputs(outdir, arrays: dict, seed: int) -> None:
+    """Write `arrays` as outdir/<name>.npy in float32.  The SH gradient is kept on a seeded tenth of the Gaussians; if the
+    total still exceeds DUMP_BUDGET_BYTES (non-default sizes), every array over 1 M elements is reduced to a seeded sample
+    of its flattened elements, the same sample in every run with the same arguments."""
+    out = Path(outdir)
+    out.mkdir(parents=True, exist_ok=True)
+    g = torch.Generator().manual_seed(seed)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().float().cpu()
+        if name == "grad_sh":
+            rows = torch.randperm(t.shape[0], generator=g)[:max(1, t.shape[0] // 10)].sort().values
+            t = t[rows]
+        host[name] = t
+    total = 4 * sum(t.numel() for t in host.values())
+    if total > DUMP_BUDGET_BYTES:
+        big = {k: t for k, t in host.items() if t.numel() > (1 << 20)}
+        small = 4 * sum(t.numel() for k, t in host.items() if k not in big)
+        frac = max(0.0, DUMP_BUDGET_BYTES - small) / (4 * sum(t.numel() for t in big.values()))
+        for k, t in big.items():
+            idx = torch.randperm(t.numel(), generator=g)[:int(t.numel() * frac)].sort().values
+            host[k] = t.reshape(-1)[idx]
+    for name, t in host.items():
+        np.save(out / f"{name}.npy", t.numpy().astype(np.float32))
+
+
 def launch_ranks(args) -> int:
     """`python bench.py --gpus N` outside torchrun: start the N ranks as a CHILD process (never an exec: this process may
     not have touched the GPU yet, but the box refuses exec from GPU processes anyway) and relay rank 0's JSON line."""
@@ -514,11 +555,15 @@ def main():
         except ImportError:
             loop_b = None
 
-    def step():
-        for _ in range(args.raster_iters):
-            loop_a.iteration()
+    last = {}
+
+    def step(keep: bool = False):
+        for i in range(args.raster_iters):
+            loop_a.iteration(keep=keep and i == args.raster_iters - 1)
         if loop_b is not None:
-            loop_b.step_pass()
+            sample = loop_b.step_pass()
+            if keep:
+                last["svd_prev_sample"] = sample
 
     def barrier():
         if dist is not None:
@@ -532,29 +577,31 @@ def main():
     log("setup done; warmup")
     for _ in range(args.warmup):
         step()
-    if loop_b is not None:
-        loop_b.count_flops()
     barrier()
-    # start/stop events only on the kernels that can be the dominant one (a timed launch costs microseconds):
+    # --full: start/stop events only on the kernels that can be the dominant one (a timed launch costs microseconds):
     # the contraction family and the spatial attention when the SVD unit is part of the step, else the blend kernels
     only = "k_gemm,k_attn_spatial,k_render" if loop_b is not None else "k_render"
     # ... and only during the last --trace-steps of the timed steps: still inside the timed region, for a fraction
     # of the events' cost (2-3 % of a step when every launch of every step is timed)
-    traced = 0 if args.no_kernel_trace else max(1, min(args.trace_steps, args.steps))
+    traced = 0 if (args.no_kernel_trace or not args.full) else max(1, min(args.trace_steps, args.steps))
+    dump = args.dump_outputs is not None
     t0 = time.perf_counter()
-    for _ in range(args.steps - traced):
-        step()
-    with L.kernel_trace(only=only if traced else "(none)") as tr:
-        for _ in range(traced):
-            step()
+    for i in range(args.steps - traced):
+        step(keep=dump and i == args.steps - 1)
+    with (L.kernel_trace(only=only if traced else "(none)") if args.full else contextlib.nullcontext()) as tr:
+        for i in range(traced):
+            step(keep=dump and i == traced - 1)
         from syn3r_amd import raster as _r
         truncated = _r.flush_pair_checks()         # every render's pair list was complete (raises otherwise)
         barrier()
         dt = time.perf_counter() - t0
     log(f"timed region done: {dt:.3f} s")
+    if dump and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, {**loop_a.last, **last}, args.seed)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
     # ONE collective at the end (north_star): the fixed per-scene record of syn3r_amd/dist.py; the job's time is
-    # the MAX of the ranks' wall-clocks, read from the gathered records
-    psnr, ssim = loop_a.metrics()
+    # the MAX of the ranks' wall-clocks, read from the gathered records (psnr / ssim of the render: --full only)
+    psnr, ssim = loop_a.metrics() if args.full else (float("nan"), float("nan"))
     rec = [float(rank), psnr, ssim, float("nan"), args.raster_iters * args.steps / dt, (args.steps / dt) if loop_b else 0.0, dt, float(truncated), 1.0]
     allrec = D.gather_records(rec)
     dt_max = float(allrec[:, D.RECORD_FIELDS.index("wall_s")].max())
@@ -562,24 +609,26 @@ def main():
     if rank == 0:
         iters = args.raster_iters * args.steps * world
         value = iters / dt_max
-        P = loop_a.pairs()
-        alg = raster_algorithmic_bytes(args.gaussians, P, args.height, args.width)
-        kern = {k: v for k, v in tr.result.items()}
-        roof = None
-        if loop_b is not None:
-            roof = loop_b.roofline(kern, max(traced, 1))
-        if roof is None and kern:
-            name = max(kern, key=lambda k: kern[k][1])
-            calls, ms = kern[name]
-            avg_s = ms / calls / 1e3
-            if name in alg:
-                ach = alg[name] / avg_s / 1e9
-                roof = dict(bound="hbm", kernel=name, achieved=round(ach, 1), peak=HBM_PEAK_GBS, unit="GB/s",
-                            frac=round(ach / HBM_PEAK_GBS, 4), traffic=None, avg_ms=round(ms / calls, 4), calls=calls,
-                            algorithmic_bytes=alg[name])
-            else:
-                roof = dict(bound="hbm", kernel=name, achieved=None, peak=HBM_PEAK_GBS, unit="GB/s", frac=None,
-                            traffic=None, avg_ms=round(ms / calls, 4), calls=calls)
+        P, roof = None, None
+        if args.full:
+            P = loop_a.pairs()
+            alg = raster_algorithmic_bytes(args.gaussians, P, args.height, args.width)
+            kern = {k: v for k, v in tr.result.items()}
+            if loop_b is not None:
+                loop_b.count_flops()
+                roof = loop_b.roofline(kern, max(traced, 1))
+            if roof is None and kern:
+                name = max(kern, key=lambda k: kern[k][1])
+                calls, ms = kern[name]
+                avg_s = ms / calls / 1e3
+                if name in alg:
+                    ach = alg[name] / avg_s / 1e9
+                    roof = dict(bound="hbm", kernel=name, achieved=round(ach, 1), peak=HBM_PEAK_GBS, unit="GB/s",
+                                frac=round(ach / HBM_PEAK_GBS, 4), traffic=None, avg_ms=round(ms / calls, 4), calls=calls,
+                                algorithmic_bytes=alg[name])
+                else:
+                    roof = dict(bound="hbm", kernel=name, achieved=None, peak=HBM_PEAK_GBS, unit="GB/s", frac=None,
+                                traffic=None, avg_ms=round(ms / calls, 4), calls=calls)
         out = {
             "metric": "llff_3view_train_loop_iters_per_sec",
             "value": round(value, 3),
@@ -595,7 +644,7 @@ def main():
             "data": "synthetic",
             "config": {
                 "workload": f"LLFF fern-like 3-view block: {args.raster_iters} raster fwd+bwd iters ({args.loss} loss) "
-                            f"({args.gaussians} Gaussians, {args.width}x{args.height}, SH3, P={P} pairs) + "
+                            f"({args.gaussians} Gaussians, {args.width}x{args.height}, SH3" + (f", P={P} pairs) + " if P is not None else ") + ")
                             + (f"1 SVD (step,pass): CFG UNet fwd [2,{args.frames},8,72,128] f16 + fused Euler step"
                                if loop_b is not None else "SVD pass NOT included (UNet not built yet)"),
                 "raster_iters_per_step": args.raster_iters,
@@ -603,13 +652,14 @@ def main():
                 "frames": args.frames,
                 "parallelism": f"scene-parallel x{world}",
             },
-            "roofline": dict(roof, traced_steps=traced) if roof else roof,
-            "roofline_other": other_rooflines(kern, alg, loop_b, max(traced, 1)),
-            "kernels_ms": {k: [v[0], round(v[1], 3)] for k, v in sorted(kern.items(), key=lambda kv: -kv[1][1])[:12]},
-            "record_fields": list(D.RECORD_FIELDS),
-            "per_rank": [[None if x != x else round(float(x), 3) for x in r.tolist()] for r in allrec],
         }
-        if loop_b is not None and world == 1:
+        if args.full:
+            out["roofline"] = dict(roof, traced_steps=traced) if roof else roof
+            out["roofline_other"] = other_rooflines(kern, alg, loop_b, max(traced, 1))
+            out["kernels_ms"] = {k: [v[0], round(v[1], 3)] for k, v in sorted(kern.items(), key=lambda kv: -kv[1][1])[:12]}
+        out["record_fields"] = list(D.RECORD_FIELDS)
+        out["per_rank"] = [[None if x != x else round(float(x), 3) for x in r.tolist()] for r in allrec]
+        if args.full and loop_b is not None and world == 1:
             # the other reading of "SVD_1pass" in the fern-like schedule: 1 200 (step, pass) units per 30 000 iterations = 25 : 1
             # (bench.py header: the headline counts 600 one-pass units, 50 : 1).  Timed here, same process, same kernels.
             half = max(1, args.raster_iters // 2)
@@ -624,10 +674,10 @@ def main():
             out["value_two_pass_mix"] = {"value": round(2 * half / dt2, 3), "unit": "iters/s", "raster_iters_per_svd_unit": half,
                                          "ms_per_step": round(1e3 * dt2 / 2, 3), "steps": 2,
                                          "note": "same step with one SVD unit per %d raster iterations (the two-pass reading of the schedule)" % half}
-        if not args.no_sub_benchmarks and world == 1:
+        if args.full and not args.no_sub_benchmarks and world == 1:
             log("sub-benchmarks (Post / Replace units at F = 25, full trainer iteration, inverse warp) ...")
             out["sub_benchmarks"] = sub_benchmarks(args, dev, loop_a, loop_b, log)
-        if not args.no_cpu_baseline and world == 1:      # reported on rank 0 of the single-GPU run only
+        if args.full and not args.no_cpu_baseline and world == 1:      # reported on rank 0 of the single-GPU run only
             log("cpu baseline (oracle on the host cores, bounded sample) ...")
             out["cpu_baseline"] = cpu_baseline(args, loop_b is not None)
             out["cpu_baseline"]["sample_note"] = ("bounded samples: one oracle run of the raster leg (1/4 of the pixels) and of the UNet leg (1/14 of "

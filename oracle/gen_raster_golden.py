@@ -1,4 +1,4 @@
-"""Generate tests/golden/raster_200k_1080p.npz: the CPU restatement (oracle/raster_oracle.py, float64) run ONCE
+"""Generate tests/golden/raster_200k_1080p*.npz: the CPU restatement (oracle/raster_oracle.py, float64) run ONCE
 on bench.py's scene — 200 000 Gaussians, 1920x1080, SH degree 3, P ~ 2.6 M (Gaussian, tile) pairs — forward and
 the gradient of a seeded linear functional of (colour, depth, alpha).  ~10 min of CPU; test infrastructure.
 
@@ -65,6 +65,27 @@ def run(N, H, W, seed=1234, log=print):
                 screen_grad=torch.stack([g["px"], g["py"]], 1), radius=pre["radius"])
 
 
+# the fixture is stored as three .npz files (each under the 1 MiB a committed file may have): `<name>.npz` with the sizes,
+# sums, sample ids and the colour image, `<name>_depth_alpha.npz`, `<name>_grads.npz`; load() merges them into one dict
+def _part(key: str) -> str:
+    if key in ("depth", "alpha", "n_contrib"):
+        return "_depth_alpha"
+    return "_grads" if key.startswith(("grad_", "screen_grad")) else ""
+
+
+def save(path: Path, out: dict) -> None:
+    for suffix in ("", "_depth_alpha", "_grads"):
+        np.savez_compressed(path.with_name(path.stem + suffix + ".npz"), **{k: v for k, v in out.items() if _part(k) == suffix})
+
+
+def load(path: Path) -> dict:
+    out = {}
+    for suffix in ("", "_depth_alpha", "_grads"):
+        with np.load(path.with_name(path.stem + suffix + ".npz")) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
+
+
 def main():
     N, H, W = (int(v) for v in sys.argv[1:4]) if len(sys.argv) >= 4 else (200_000, 1080, 1920)
     torch.set_num_threads(8)
@@ -85,7 +106,7 @@ def main():
     # viewspace-point gradient norm (what FSGS accumulates for densification): d L / d (pixel-space mean)
     out["screen_grad_sample"] = r["screen_grad"][ids].numpy().astype(np.float32)
     name = "raster_200k_1080p.npz" if (N, H, W) == (200_000, 1080, 1920) else f"raster_{N}_{W}x{H}.npz"
-    np.savez_compressed(GOLD / name, **out)
+    save(GOLD / name, out)
     print("wrote", name, {k: getattr(v, "shape", ()) for k, v in out.items()})
 
 

@@ -83,13 +83,13 @@ def test_host_side_of_the_abi_under_asan_ubsan(tmp_path):
         out, err = pr.communicate()
         assert pr.returncode == 0, f"{src.name}: {err[-2000:]}"
     lib = tmp_path / "libsyn3r_hip_san.so"
-    r = subprocess.run([hipcc, "-shared", "-fPIC", f"--offload-arch={B.ARCH}", "-fsanitize=address,undefined", "-o", str(lib), *map(str, objs)],
+    r = subprocess.run([hipcc, "-shared", "-fPIC", f"--offload-arch={B.ARCH}", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-o", str(lib), *map(str, objs)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     drv = tmp_path / "driver.cpp"
     drv.write_text(_driver_source())
     exe = tmp_path / "driver"
-    r = subprocess.run([hipcc, "-x", "c++", str(drv), "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g", "-o", str(exe),
+    r = subprocess.run([hipcc, "-x", "c++", str(drv), "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-sanitize-recover=undefined", "-g", "-o", str(exe),
                         f"-L{tmp_path}", "-lsyn3r_hip_san", f"-Wl,-rpath,{tmp_path}"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     # no device for this process: the calls that pass their checks must stop at the launch, never run a kernel on the

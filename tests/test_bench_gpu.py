@@ -1,10 +1,12 @@
 """The driver's contract with bench.py: one JSON line on stdout with the agreed keys, a roofline object for the dominant
-kernel family measured live, and internally consistent numbers (a short run: 1 step of 5 raster iterations + 1 SVD unit)."""
+kernel family measured live (`--full`), and internally consistent numbers (a short run: 1 step of 5 raster iterations + 1 SVD
+unit); a plain run carries the headline only and `--dump-outputs` writes what its last timed step computed."""
 import json
 import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -13,7 +15,7 @@ ROOT = Path(__file__).resolve().parents[1]
 
 def test_bench_line_contract(gpu):
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--raster-iters", "5",
-                        "--no-sub-benchmarks"], capture_output=True, text=True, timeout=900, cwd=str(ROOT))
+                        "--full", "--no-sub-benchmarks"], capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines                                   # ONE line on stdout
@@ -36,6 +38,41 @@ def test_bench_line_contract(gpu):
               "S2_step_interp_grad_25x4x72x128", "S3_step_interp_prob_uncertain_25x4x72x128"):
         assert gs[k]["cpu_port_s"] > 0 and gs[k]["gpu_device_us"] > 0, k
     assert b["record_fields"][-2:] == ["truncated_renders", "ok"] and b["per_rank"][0][-2:] == [0.0, 1.0]
+
+
+def test_plain_run_is_lean_and_dumps_its_last_step(gpu, tmp_path):
+    """Without --full the line carries the headline and nothing that takes measurements of its own; --steps sets the timed
+    steps; --dump-outputs writes the last timed step's outputs (rasteriser image, loss and gradients, the SVD unit's latents)
+    as float32 .npy under 64 MB, and two runs with the same arguments compute them from identical seeded inputs."""
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--raster-iters", "3",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, cwd=str(ROOT))
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        b = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in b, k
+        assert b["steps"] == 2 and b["warmup"] == 1 and b["config"]["raster_iters_per_step"] == 3
+        assert abs(b["value"] - 3 * 1000.0 / b["ms_per_step"]) < 0.02 * b["value"]
+        for k in ("roofline", "roofline_other", "kernels_ms", "value_two_pass_mix", "sub_benchmarks", "cpu_baseline"):
+            assert k not in b, k
+        files = sorted(d.glob("*.npy"))
+        assert sum(f.stat().st_size for f in files) <= 64_000_000
+        arrs = {f.stem: np.load(f) for f in files}
+        assert {"loss", "color", "depth", "alpha", "radii", "grad_means2D", "grad_m", "grad_s", "grad_q", "grad_o", "grad_sh",
+                "svd_prev_sample"} <= set(arrs)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert arrs["color"].shape == (3, 1080, 1920) and arrs["svd_prev_sample"].shape == (1, 14, 4, 72, 128)
+        for k in ("loss", "color", "depth", "alpha", "grad_m", "grad_sh"):
+            assert np.isfinite(arrs[k]).all(), k
+        dumps.append(arrs)
+    for k, a in dumps[0].items():
+        a, b = a.astype(np.float64), dumps[1][k].astype(np.float64)
+        scale = float(np.nanmax(np.abs(a))) if a.size else 0.0
+        np.testing.assert_allclose(b, a, rtol=0, atol=1e-3 * scale + 1e-30, equal_nan=True, err_msg=k)
 
 
 def test_two_rank_job_on_one_device(gpu, tmp_path):

@@ -1,5 +1,5 @@
 """The rasteriser at the BENCHMARK size — 200 000 Gaussians, 1920x1080, P ~ 2.6 M (Gaussian, tile) pairs — against the CPU
-restatement (oracle/raster_oracle.py): images and gradients from tests/golden/raster_200k_1080p.npz (the float64 oracle
+restatement (oracle/raster_oracle.py): images and gradients from tests/golden/raster_200k_1080p*.npz (the float64 oracle
 run once by oracle/gen_raster_golden.py, ~25 min of CPU), tile lists from the oracle's own preprocess + stable sort run
 live (seconds).  This is where the saturation walk-back, the staging batches and the per-half visit lists of the
 blend kernels are stressed; the small-scene tests of test_raster_gpu.py cannot reach them.
@@ -33,7 +33,7 @@ def golden(golden_dir):
     path = golden_dir / "raster_200k_1080p.npz"
     if not path.exists():
         pytest.skip("raster_200k_1080p.npz not generated (oracle/gen_raster_golden.py)")
-    return np.load(path)
+    return GG.load(path)
 
 
 @pytest.mark.parametrize("mode", ["sync", "async"])

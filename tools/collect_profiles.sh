@@ -6,13 +6,13 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/${1:-r01}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 python3 "$R/bench.py" --steps 3 --warmup 1 $BENCH_EXTRA > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 500 python3 "$R/bench.py" --full --steps 3 --warmup 1 $BENCH_EXTRA > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "[profiles] bench done"
-timeout -k 10 280 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o bench -- python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-sub-benchmarks > "$OUT/stats.log" 2>&1
+timeout -k 10 280 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o bench -- python3 "$R/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-sub-benchmarks > "$OUT/stats.log" 2>&1
 echo "[profiles] kernel stats done"
-timeout -k 10 100 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o p -- python3 "$R/bench.py" --steps 1 --warmup 0 --raster-iters 5 --no-cpu-baseline --no-sub-benchmarks --no-kernel-trace > "$OUT/fetch.log" 2>&1 || { echo "[profiles] FETCH_SIZE pass FAILED:"; tail -20 "$OUT/fetch.log"; exit 3; }
+timeout -k 10 100 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o p -- python3 "$R/bench.py" --full --steps 1 --warmup 0 --raster-iters 5 --no-cpu-baseline --no-sub-benchmarks --no-kernel-trace > "$OUT/fetch.log" 2>&1 || { echo "[profiles] FETCH_SIZE pass FAILED:"; tail -20 "$OUT/fetch.log"; exit 3; }
 echo "[profiles] FETCH_SIZE pass done"
-timeout -k 10 100 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -o p -- python3 "$R/bench.py" --steps 1 --warmup 0 --raster-iters 5 --no-cpu-baseline --no-sub-benchmarks --no-kernel-trace > "$OUT/write.log" 2>&1 || { echo "[profiles] WRITE_SIZE pass FAILED:"; tail -20 "$OUT/write.log"; exit 3; }
+timeout -k 10 100 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -o p -- python3 "$R/bench.py" --full --steps 1 --warmup 0 --raster-iters 5 --no-cpu-baseline --no-sub-benchmarks --no-kernel-trace > "$OUT/write.log" 2>&1 || { echo "[profiles] WRITE_SIZE pass FAILED:"; tail -20 "$OUT/write.log"; exit 3; }
 echo "[profiles] WRITE_SIZE pass done"
 # SQ / GRBM passes: matrix-pipe busy cycles, instruction mix, LDS bank conflicts per kernel family.
 # Counter sets are intersected with what `rocprofv3 -L` lists on this box; each pass is its own run (program directly after --).
@@ -21,8 +21,8 @@ pick() { local out=""; for c in "$@"; do if grep -qw "$c" <<< "$AVAIL"; then out
 SET_A=$(pick SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE)
 SET_B=$(pick SQ_INSTS_VALU SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE)
 echo "[profiles] SQ pass A:$SET_A" ; echo "[profiles] SQ pass B:$SET_B"
-timeout -k 10 150 rocprofv3 --kernel-trace --pmc $SET_A --output-format csv -d "$OUT/sqa" -o p -- python3 "$R/bench.py" --steps 1 --warmup 0 --raster-iters 5 --no-cpu-baseline --no-sub-benchmarks --no-kernel-trace > "$OUT/sqa.log" 2>&1 || { echo "[profiles] SQ pass A FAILED:"; tail -20 "$OUT/sqa.log"; }
-timeout -k 10 150 rocprofv3 --kernel-trace --pmc $SET_B --output-format csv -d "$OUT/sqb" -o p -- python3 "$R/bench.py" --steps 1 --warmup 0 --raster-iters 5 --no-cpu-baseline --no-sub-benchmarks --no-kernel-trace > "$OUT/sqb.log" 2>&1 || { echo "[profiles] SQ pass B FAILED:"; tail -20 "$OUT/sqb.log"; }
+timeout -k 10 150 rocprofv3 --kernel-trace --pmc $SET_A --output-format csv -d "$OUT/sqa" -o p -- python3 "$R/bench.py" --full --steps 1 --warmup 0 --raster-iters 5 --no-cpu-baseline --no-sub-benchmarks --no-kernel-trace > "$OUT/sqa.log" 2>&1 || { echo "[profiles] SQ pass A FAILED:"; tail -20 "$OUT/sqa.log"; }
+timeout -k 10 150 rocprofv3 --kernel-trace --pmc $SET_B --output-format csv -d "$OUT/sqb" -o p -- python3 "$R/bench.py" --full --steps 1 --warmup 0 --raster-iters 5 --no-cpu-baseline --no-sub-benchmarks --no-kernel-trace > "$OUT/sqb.log" 2>&1 || { echo "[profiles] SQ pass B FAILED:"; tail -20 "$OUT/sqb.log"; }
 SQ_FILES=$(ls "$OUT"/sqa/p_counter_collection.csv "$OUT"/sqb/p_counter_collection.csv 2>/dev/null || true)
 if [ -n "$SQ_FILES" ]; then
   python3 "$R/tools/pmc_families.py" "$OUT/pmc_counters_by_kernel.json" "$OUT/pmc_counters_by_kernel.csv" $SQ_FILES > /dev/null
