@@ -588,6 +588,32 @@ int syn3r_photo_loss_backward(const float* image, const float* target, int C, in
 int syn3r_photo_loss_step(const float* image, const float* target, int C, int H, int W, float lambda_dssim, float weight,
                           const float* grad_loss, float* loss3, float* grad_image, void* ws, size_t ws_bytes, void* stream);
 
+/* FSGS' depth-correlation regulariser (Zhu et al., ECCV 2024, "geometry guidance"; the reference's batch scripts switch FSGS'
+ * depth terms on, bash_scripts/batch_{llff,dl3dv}_train.sh --svd_depth_warmup 1; FSGS' trainer is not vendored) on one rendered
+ * depth map d and one monocular prior p, n = H*W fp32 values each:
+ *   branch A: t = -p;  branch B: t = 1 / (p + offset);  r_X = S_dt / sqrt(S_dd S_tt) (centred sums, clamped to [-1, 1])
+ *   loss = weight * min(1 - r_A, 1 - r_B) (SYN3R_DCORR_MIN; A on a tie) or one branch (SYN3R_DCORR_A / _B)
+ * The two-transform minimum and offset = 200 are recalled from FSGS' train.py (not available): UNPINNED, hence arguments.
+ * A branch with S_dd == 0 or S_tt == 0 has r = 0, loss 1 and a zero gradient (no NaN).  fp64 centred moments merged in a fixed
+ * order: bitwise repeatable.  parts (device, 16-byte aligned, 4 floats): [loss, r_A, r_B (0 in mode A), branch (0 = A, 1 = B)].
+ * ws: syn3r_depth_corr_loss_workspace_bytes(n) bytes (0 for n outside [2, 2^30]); it holds the statistics the backward
+ * reads, so syn3r_depth_corr_loss_backward takes the SAME workspace.  Rejections: SYN3R_E_INVALID, or SYN3R_E_WORKSPACE for
+ * a short workspace. */
+#define SYN3R_DCORR_MIN 0
+#define SYN3R_DCORR_A 1
+#define SYN3R_DCORR_B 2
+size_t syn3r_depth_corr_loss_workspace_bytes(long long n);
+/* value only: two launches (statistics, one-block combine) */
+int syn3r_depth_corr_loss(const float* depth, const float* prior, long long n, float weight, float offset, int mode, float* parts,
+                          void* ws, size_t ws_bytes, void* stream);
+/* grad_depth = grad_loss[0] * d loss / d depth through the chosen branch (grad_loss: device scalar, NULL = 1); one launch */
+int syn3r_depth_corr_loss_backward(const float* depth, const float* prior, long long n, float weight, float offset, int mode,
+                                   const float* grad_loss, const void* ws, size_t ws_bytes, float* grad_depth, void* stream);
+/* Value AND gradient in two launches: the statistics pass, then the gradient pass, whose block 0 writes parts (every block of
+ * it combines the statistics in the same fixed order).  Same bits as syn3r_depth_corr_loss + syn3r_depth_corr_loss_backward. */
+int syn3r_depth_corr_loss_step(const float* depth, const float* prior, long long n, float weight, float offset, int mode,
+                               const float* grad_loss, float* parts, float* grad_depth, void* ws, size_t ws_bytes, void* stream);
+
 /* One torch.optim.Adam update (no weight decay, no amsgrad) of n fp32 parameters in place, in torch's
  * operation order: exp_avg.lerp_(g, 1-beta1); exp_avg_sq = beta2*exp_avg_sq + (1-beta2)*g*g;
  * param -= lr/(1-beta1^step) * exp_avg / (sqrt(exp_avg_sq)/sqrt(1-beta2^step) + eps).  step is 1-based. */

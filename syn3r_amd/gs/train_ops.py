@@ -123,6 +123,81 @@ def photometric_loss_step(image: torch.Tensor, target: torch.Tensor, lambda_dssi
     return parts[0], parts, grad
 
 
+_DCORR_MODES = {"min": 0, "A": 1, "B": 2}      # SYN3R_DCORR_MIN / _A / _B
+
+
+def _dcorr_args(who: str, depth: torch.Tensor, prior: torch.Tensor, mode: str):
+    """(depth, prior) as contiguous fp32 [H*W] views and the mode tag; depth [1,H,W] or [H,W], prior [H,W] or [1,H,W]."""
+    L.require_gpu(depth, prior)
+    if depth.dtype != torch.float32 or prior.dtype != torch.float32:
+        raise ValueError(f"{who}: depth and prior must be float32")
+    hw = lambda t: tuple(t.shape[1:]) if t.dim() == 3 and t.shape[0] == 1 else (tuple(t.shape) if t.dim() == 2 else None)
+    if hw(depth) is None or hw(prior) is None or hw(depth) != hw(prior):
+        raise ValueError(f"{who}: depth [1,H,W] or [H,W] and prior [H,W] or [1,H,W] of the same H, W; got "
+                         f"{tuple(depth.shape)} and {tuple(prior.shape)}")
+    if mode not in _DCORR_MODES:
+        raise ValueError(f"{who}: mode must be one of {sorted(_DCORR_MODES)}, got {mode!r}")
+    return depth.detach().contiguous(), prior.detach().contiguous(), _DCORR_MODES[mode]
+
+
+class _DepthCorrLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth: torch.Tensor, prior: torch.Tensor, weight: float, offset: float, mode: str):
+        d, p, m = _dcorr_args("depth_correlation_loss", depth, prior, mode)
+        lib = L.load()
+        n = d.numel()
+        # own buffer, not the shared workspace cache: the statistics must survive until backward
+        ws = torch.empty(max(lib.syn3r_depth_corr_loss_workspace_bytes(n), 256), dtype=torch.uint8, device=d.device)
+        parts = torch.empty(4, dtype=torch.float32, device=d.device)
+        L.check(lib.syn3r_depth_corr_loss(L.ptr(d), L.ptr(p), n, float(weight), float(offset), m, L.ptr(parts), L.ptr(ws),
+                                          ws.numel(), L.stream_ptr(d.device)), "depth_corr_loss")
+        ctx.save_for_backward(d, p, ws)
+        ctx.args = (float(weight), float(offset), m, depth.shape)
+        ctx.mark_non_differentiable(parts)
+        return parts[0].clone(), parts
+
+    @staticmethod
+    def backward(ctx, grad_loss: torch.Tensor, _grad_parts):
+        L.join_active_trace()
+        d, p, ws = ctx.saved_tensors
+        weight, offset, m, shape = ctx.args
+        go = grad_loss.to(torch.float32).contiguous()
+        grad = torch.empty_like(d)
+        L.check(L.load().syn3r_depth_corr_loss_backward(L.ptr(d), L.ptr(p), d.numel(), weight, offset, m, L.ptr(go), L.ptr(ws),
+                                                        ws.numel(), L.ptr(grad), L.stream_ptr(d.device)), "depth_corr_loss_backward")
+        return grad.reshape(shape), None, None, None, None
+
+
+def depth_correlation_loss(depth: torch.Tensor, prior: torch.Tensor, weight: float = 1.0, offset: float = 200.0, mode: str = "min",
+                           return_parts: bool = False):
+    """FSGS' depth-correlation term (Zhu et al., ECCV 2024, "geometry guidance") on one rendered depth map and a monocular prior:
+    `weight * min(1 - r_A, 1 - r_B)`, r = Pearson(depth, t) for t = -prior (A) and t = 1 / (prior + offset) (B); `mode` "A" / "B"
+    keeps one branch.  The two-branch minimum and offset 200 are recalled from FSGS' train.py (not available): UNPINNED.  A flat
+    render or prior gives r = 0 (loss = weight) and a zero gradient, not NaN.  Device scalar, no host synchronisation; backward is
+    the kernel's gradient pass through the chosen branch (csrc/depth_loss.hip).  `return_parts`: also the device tensor
+    [loss, r_A, r_B, branch (0 = A, 1 = B)]."""
+    loss, parts = _DepthCorrLoss.apply(depth, prior, weight, offset, mode)
+    return (loss, parts) if return_parts else loss
+
+
+def depth_correlation_loss_step(depth: torch.Tensor, prior: torch.Tensor, weight: float = 1.0, offset: float = 200.0,
+                                mode: str = "min", grad_loss: torch.Tensor = None, return_parts: bool = False):
+    """Value AND depth gradient of `depth_correlation_loss` without autograd (`syn3r_depth_corr_loss_step`: two launches).  Returns
+    (loss - a view of parts[0] -, grad_depth shaped like depth) [+ parts]; `grad_loss`: device scalar, default 1.  Same bits as
+    the autograd Function's forward + backward."""
+    d, p, m = _dcorr_args("depth_correlation_loss_step", depth, prior, mode)
+    dev = d.device
+    lib = L.load()
+    n = d.numel()
+    ws = L.workspace(dev, lib.syn3r_depth_corr_loss_workspace_bytes(n), "dcorr_step")
+    parts = torch.empty(4, dtype=torch.float32, device=dev)
+    grad = torch.empty_like(d)
+    go = grad_loss.to(torch.float32).contiguous() if grad_loss is not None else None
+    L.check(lib.syn3r_depth_corr_loss_step(L.ptr(d), L.ptr(p), n, float(weight), float(offset), m, L.ptr(go), L.ptr(parts),
+                                           L.ptr(grad), L.ptr(ws), ws.numel(), L.stream_ptr(dev)), "depth_corr_loss_step")
+    return (parts[0], grad, parts) if return_parts else (parts[0], grad)
+
+
 def image_metrics(image: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     """Device tensor [PSNR (dB, peak 1), SSIM] of two float32 [C,H,W] images in [0,1]: the MSE from `syn3r_image_mse`
     (deterministic two-level sum) and the SSIM the fused photometric-loss kernel computes (published 3DGS window).

@@ -20,7 +20,7 @@ import torch
 
 from .. import _lib as L
 from ..raster import GaussianRasterizationSettings, GaussianRasterizer
-from .train_ops import FusedAdam, image_metrics, knn3_mean_dist2, l1_loss, photometric_loss
+from .train_ops import FusedAdam, depth_correlation_loss, image_metrics, knn3_mean_dist2, l1_loss, photometric_loss
 
 SH_C0 = 0.28209479177387814
 
@@ -48,10 +48,12 @@ def _projection(znear: float, zfar: float, fovx: float, fovy: float) -> torch.Te
 class Camera:
     """`FSGS.scene.cameras.Camera(colmap_id, R, T, FoVx, FoVy, image, gt_alpha_mask, image_name, uid, trans, scale,
     data_device, cam_confidence)` as constructed at diffusionGS.py:161-163.  R is camera-to-world rotation and T the
-    world-to-camera translation (COLMAP/3DGS convention)."""
+    world-to-camera translation (COLMAP/3DGS convention).  `depth_image`: the monocular depth prior [H,W] (or [1,H,W]) of the
+    view, named as in FSGS' camera; the trainer's depth-correlation term reads it (None: `GSTrainer.depth_net` fills it in, or
+    the view has no prior)."""
 
     def __init__(self, colmap_id, R, T, FoVx, FoVy, image, gt_alpha_mask=None, image_name="", uid=0,
-                 trans=np.array([0.0, 0.0, 0.0]), scale=1.0, data_device="cuda", cam_confidence: float = 1.0):
+                 trans=np.array([0.0, 0.0, 0.0]), scale=1.0, data_device="cuda", cam_confidence: float = 1.0, depth_image=None):
         self.uid, self.colmap_id, self.image_name = uid, colmap_id, image_name
         self.R, self.T, self.FoVx, self.FoVy = np.asarray(R, np.float32), np.asarray(T, np.float32), FoVx, FoVy
         self.cam_confidence = float(cam_confidence)
@@ -67,6 +69,10 @@ class Camera:
         self.projection_matrix = _projection(self.znear, self.zfar, FoVx, FoVy).transpose(0, 1).to(self.data_device)
         self.full_proj_transform = self.world_view_transform @ self.projection_matrix
         self.camera_center = self.world_view_transform.inverse()[3, :3]
+        self.depth_image = None
+        if depth_image is not None:
+            d = torch.as_tensor(depth_image, dtype=torch.float32).to(self.data_device)
+            self.depth_image = (d[0] if d.dim() == 3 and d.shape[0] == 1 else d).contiguous()
 
     @classmethod
     def from_w2c(cls, w2c: np.ndarray, K: np.ndarray, H: int, W: int, image=None, **kw):
@@ -222,6 +228,9 @@ class OptimizationParams:
     seed: int = 0
     use_lpips_loss: bool = False       # toggled by DiffusionGS.run (diffusionGS.py:1690,1697); see GSTrainer.train_step
     lpips_weight: float = 0.0
+    # FSGS' depth-correlation term (GSTrainer.train_step): weight 0 = off; `depth_offset` is the c of its 1 / (prior + c) branch
+    depth_weight: float = 0.0
+    depth_offset: float = 200.0
     # adaptive density control, published 3DGS defaults (Kerbl et al. 2023 section 5.2 and its released arguments); used when
     # training()/finetune() run with disable_densification=False
     percent_dense: float = 0.01
@@ -260,6 +269,7 @@ class GSTrainer:
         self.dust3r = None                # injected: to(device) / [make_pairs] / run(frames, c2w_poses=, intrinsics=, preset_pairs=)
         self.flow_net = None              # injected: flow_net(image_a [3,H,W], image_b [3,H,W]) -> flow a->b [2,H,W] (GMFlow's role)
         self.lpips = None                 # injected: syn3r_amd.gs.lpips.LPIPS with loaded weights (the `lpips` package's role)
+        self.depth_net = None             # injected: depth_net(image [3,H,W]) -> prior [H,W] (FSGS' monocular DPT / MiDaS role)
         self.checkpoint_iterations: List[int] = list(checkpoint_iterations or [])
         self.iteration = 0
         self.densify = False              # adaptive density control inside train_step (training / finetune set it)
@@ -541,6 +551,20 @@ class GSTrainer:
         cams = self.scene.getTrainCameras()
         return cams[int(self._rng.integers(len(cams)))]
 
+    def depth_prior(self, cam: Camera) -> Optional[torch.Tensor]:
+        """The camera's monocular depth prior [H,W] fp32: `cam.depth_image`, else `depth_net(cam.original_image)` computed ONCE under
+        no_grad and cached on the camera (pseudo-views registered by `update_cameras` included); None without either."""
+        if getattr(cam, "depth_image", None) is None:
+            if self.depth_net is None or cam.original_image is None:
+                return None
+            with torch.no_grad():
+                d = torch.as_tensor(self.depth_net(cam.original_image), dtype=torch.float32).to(cam.original_image.device)
+            cam.depth_image = (d[0] if d.dim() == 3 and d.shape[0] == 1 else d).detach().contiguous()
+        return cam.depth_image
+
+    def _depth_term_prior(self, cam: Camera) -> Optional[torch.Tensor]:
+        return self.depth_prior(cam) if self.opt.depth_weight > 0.0 else None
+
     def _explicit_step(self, cam: Camera) -> Tuple[torch.Tensor, dict]:
         """One optimisation step WITHOUT autograd: raw parameters in, raw-parameter gradients out.  The activations and
         their chain rule run INSIDE the rasteriser's projection kernels (`syn3r_raster_preprocess_raw` / `_backward_raw`, round 6:
@@ -549,13 +573,14 @@ class GSTrainer:
         and no screen-space `means2D` tensor is allocated per render.  Same arithmetic as the autograd path
         (`tests/test_trainer_gpu.py` holds one step of each against the oracle and against each other)."""
         from ..raster import rasterize_backward, rasterize_forward
-        from .train_ops import l1_loss_step, photometric_loss_step
+        from .train_ops import depth_correlation_loss_step, l1_loss_step, photometric_loss_step
         g = self.gaussians
         # this step discards the rasteriser's confidence gradient: the per-Gaussian confidence is data here, as in the call sites
         # (model/diffusionGS.py:139,1640); a trainable one has to take the autograd path
         conf = g.confidence
         if conf is not None and getattr(conf, "requires_grad", False):
             raise ValueError("_explicit_step: a confidence tensor that requires grad needs train_step(explicit=False)")
+        prior = self._depth_term_prior(cam)
         with torch.no_grad():
             st = GaussianRasterizationSettings(
                 image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
@@ -570,7 +595,11 @@ class GSTrainer:
                 loss, _, d_color = photometric_loss_step(color, cam.original_image, self.opt.lambda_dssim, w)
             else:
                 loss, d_color = l1_loss_step(color, cam.original_image, w)
-            d_m3, d_m2, d_sh, d_lg, d_ls, d_rr, _ = rasterize_backward(rstate, d_color)
+            d_depth = None
+            if prior is not None:
+                d_loss, d_depth = depth_correlation_loss_step(depth, prior, self.opt.depth_weight, self.opt.depth_offset)
+                loss = loss + d_loss
+            d_m3, d_m2, d_sh, d_lg, d_ls, d_rr, _ = rasterize_backward(rstate, d_color, d_depth)
             g._xyz.grad, g._features.grad, g._opacity.grad, g._scaling.grad, g._rotation.grad = d_m3, d_sh, d_lg.reshape(g._opacity.shape), d_ls, d_rr
         out = {"render": color, "depth": depth, "alpha": alpha, "viewspace_grad": d_m2, "visibility_filter": None,      # visible = radii > 0: add_densification_stats takes it from `radii` on the device
                "radii": radii}
@@ -588,6 +617,10 @@ class GSTrainer:
         around refine_GS, diffusionGS.py:1690,1697) adds `opt.lpips_weight` x LPIPS-VGG (`syn3r_amd.gs.lpips`, HIP) when the
         trainer has been given an `lpips` model with weights (the pretrained ones are not reachable offline: the caller
         loads them, as for CLIP / VAE / UNet); without one the switch is inert.
+        `opt.depth_weight` > 0 adds FSGS' depth-correlation term `depth_weight * (1 - Pearson(rendered depth, prior))` (the better of
+        its two prior transforms, `train_ops.depth_correlation_loss`) for a camera with a prior (`depth_prior`: `cam.depth_image` or
+        the injected `depth_net`); a camera without one skips it.  As FSGS' `loss += depth_weight * depth_loss` the term is weighted
+        by `depth_weight` alone, not by the camera confidence - UNPINNED for SYN3R's FSGS fork (not vendored).
         `explicit` (default: whenever the LPIPS term is off): the step without autograd (`_explicit_step`)."""
         cam = cam or self._pick_camera()
         lpips_on = self.opt.use_lpips_loss and self.opt.lpips_weight > 0.0 and self.lpips is not None
@@ -608,6 +641,9 @@ class GSTrainer:
                 # whole render, weighted like the photometric term by the camera confidence.  How FSGS applies it is not visible
                 # (un-vendored): UNPINNED.
                 loss = loss + (self.opt.lpips_weight * float(cam.cam_confidence)) * self.lpips(out["render"].clamp(0, 1), cam.original_image)
+            prior = self._depth_term_prior(cam)
+            if prior is not None:
+                loss = loss + depth_correlation_loss(out["depth"], prior, self.opt.depth_weight, self.opt.depth_offset)
             self.optimizer.zero_grad(set_to_none=True)
             loss.backward()
         changed = False

@@ -82,6 +82,9 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                     help="weight of the LPIPS term during refines (bash_scripts/batch_dl3dv_train.sh:84-87 passes 1); needs --lpips_weights")
     ap.add_argument("--lpips_weights", type=str, default=None,
                     help="local state_dict file of lpips.LPIPS(net='vgg') (torch.save format); the package's download is not reachable offline")
+    ap.add_argument("--depth_weight", type=float, default=0.0,
+                    help="weight of FSGS' depth-correlation term, 1 - Pearson(rendered depth, monocular prior), on every training step "
+                         "(0 = off); views need a prior (Camera.depth_image or an injected GSTrainer.depth_net)")
     ap.add_argument("--num_inference_steps", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     # FSGS' parameter groups (scripts/train.py:44-46: -s, --eval, --n_views, --resolution, --use_dust3r ... of the batch scripts)
@@ -106,7 +109,7 @@ FSGS_FLAGS = frozenset([
     "--start_sample_pseudo", "--end_sample_pseudo", "--svd_depth_warmup", "--svd_lpips_weight", "--use_proximity_densify",
     "--percent_dense", "--densify_grad_threshold", "--densify_from_iter", "--densify_until_iter", "--densification_interval",
     "--opacity_reset_interval", "--position_lr_init", "--position_lr_final", "--position_lr_max_steps", "--feature_lr",
-    "--opacity_lr", "--scaling_lr", "--rotation_lr", "--depth_weight", "--depth_pseudo_weight", "--white_background", "--sh_degree",
+    "--opacity_lr", "--scaling_lr", "--rotation_lr", "--depth_pseudo_weight", "--white_background", "--sh_degree",
     "--data_device", "--convert_SHs_python", "--compute_cov3D_python", "--debug", "--checkpoint", "--video", "-a", "-p", "-f", "-d",
 ])
 # the types the orchestrator accepts (model/diffusionGS.py:115-124, :244-255; syn3r_amd/diffusionGS.py raises on the rest)
@@ -136,7 +139,9 @@ def validate(args) -> None:
 
 def synthetic_scene(name: str, args, device) -> dict:
     """`synthetic:<seed>[:<N>]` — a seeded Gaussian cloud rendered from three cameras on a baseline (the views to fit),
-    a perturbed copy of it as the initial model, and two held-out cameras between the inputs for PSNR / SSIM."""
+    a perturbed copy of it as the initial model, and two held-out cameras between the inputs for PSNR / SSIM.  Each training
+    camera carries the truth cloud's disparity as its depth prior (`depth_image`: alpha / depth where alpha >= 0.5, else 0;
+    read only when `--depth_weight` > 0)."""
     from .gs import Camera, GaussianModel, GSTrainer, OptimizationParams
     from .synthetic import synthetic_gaussians
     parts = name.split(":")
@@ -156,7 +161,9 @@ def synthetic_scene(name: str, args, device) -> dict:
 
     gt = GSTrainer(truth, [Camera.from_w2c(pose(0.0), K, H, W, data_device=device)])
     shot = lambda dx: gt.render_view(Camera.from_w2c(pose(dx), K, H, W, data_device=device))["render"].detach().clamp(0, 1)
-    train = [Camera.from_w2c(pose(dx), K, H, W, image=shot(dx), data_device=device) for dx in (-0.15, 0.0, 0.15)]
+    train = [Camera.from_w2c(pose(dx), K, H, W, image=shot(dx), data_device=device,
+                             depth_image=truth_disparity(gt, Camera.from_w2c(pose(dx), K, H, W, data_device=device)))
+             for dx in (-0.15, 0.0, 0.15)]
     test = [Camera.from_w2c(pose(dx), K, H, W, image=shot(dx), data_device=device) for dx in (-0.075, 0.075)]
     g = torch.Generator().manual_seed(seed + 1)
     model = GaussianModel(m + 0.01 * torch.randn(m.shape, generator=g), torch.log(s), q, logit, sh, device=device)
@@ -164,6 +171,16 @@ def synthetic_scene(name: str, args, device) -> dict:
     out_dir = os.path.join(args.model_path, name.replace(":", "_"))
     trainer = GSTrainer(model, train, opt, model_path=out_dir, checkpoint_iterations=args.checkpoint_iterations)
     return dict(trainer=trainer, num_input_views=len(train), test_cameras=test, svd_components=None)
+
+
+@torch.no_grad()
+def truth_disparity(trainer, cam) -> torch.Tensor:
+    """Disparity prior [H,W] of a view from the cloud a trainer holds: the inverse of the alpha-normalised rendered depth,
+    alpha / depth, where the accumulated alpha is >= 0.5 and 0 elsewhere (a stand-in for a monocular network's output)."""
+    out = trainer.render_view(cam)
+    depth, alpha = out["depth"][0], out["alpha"][0]
+    ok = (alpha >= 0.5) & (depth > 0)
+    return torch.where(ok, alpha / torch.where(ok, depth, torch.ones_like(depth)), torch.zeros_like(depth)).contiguous()
 
 
 def _stand_in_svd(device):
@@ -207,6 +224,7 @@ def run_scene(name: str, args, device, factory: Callable) -> List[float]:
         # (model/diffusionGS.py:1089); without it the plumbing stand-ins
         comps = args.svd_dir if args.svd_dir else _stand_in_svd(device)
     trainer.opt.lpips_weight = float(getattr(args, "lpips_weight", 0.0))
+    trainer.opt.depth_weight = float(getattr(args, "depth_weight", 0.0))
     if sc.get("lpips") is not None:
         trainer.lpips = sc["lpips"]
     elif getattr(args, "lpips_weights", None):

@@ -1,0 +1,367 @@
+"""FSGS' depth-correlation term (csrc/depth_loss.hip, train_ops.depth_correlation_loss[_step]) against a float64 restatement,
+its determinism, and the trainer with the term on: explicit step = autograd step, one step = the fp64 oracle step, the default
+leaves every path unchanged, and a run with the term raises the depth correlation."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import raster_oracle as RO
+
+pytestmark = pytest.mark.gpu
+
+
+# ---------------------------------------------------------------- float64 restatement (centred sums, same branch / flat rules)
+def ref_branch(d, t, weight):
+    """(r, dL/dd) of weight * (1 - Pearson(d, t)); r = 0 and a zero gradient for a flat d or t."""
+    if float(d.max()) == float(d.min()) or float(t.max()) == float(t.min()):
+        return 0.0, torch.zeros_like(d)
+    dc, tc = d - d.mean(), t - t.mean()
+    sdd, stt, sdt = (dc * dc).sum(), (tc * tc).sum(), (dc * tc).sum()
+    s = torch.sqrt(sdd * stt)
+    r = float((sdt / s).clamp(-1.0, 1.0))
+    return r, -weight * (tc / s - r * dc / sdd)
+
+
+def ref_dcorr(depth, prior, weight=1.0, offset=200.0, mode="min"):
+    d, p = depth.detach().double().reshape(-1).cpu(), prior.detach().double().reshape(-1).cpu()
+    ra, ga = ref_branch(d, -p, weight)
+    rb, gb = ref_branch(d, 1.0 / (p + offset), weight)
+    la, lb = 1.0 - ra, 1.0 - rb
+    use_b = mode == "B" or (mode == "min" and lb < la)
+    return dict(loss=weight * (lb if use_b else la), ra=ra, rb=rb, branch=int(use_b), grad=(gb if use_b else ga))
+
+
+def ref_dcorr_torch(d, p, weight, offset=200.0):
+    """The same term as a differentiable float64 torch expression (for the oracle training step)."""
+    d, p = d.reshape(-1), p.reshape(-1).to(d.dtype)
+
+    def r_of(t):
+        if float(d.max()) == float(d.min()) or float(t.max()) == float(t.min()):
+            return torch.zeros((), dtype=d.dtype)
+        dc, tc = d - d.mean(), t - t.mean()
+        return ((dc * tc).sum() / torch.sqrt((dc * dc).sum() * (tc * tc).sum())).clamp(-1.0, 1.0)
+    la, lb = 1.0 - r_of(-p), 1.0 - r_of(1.0 / (p + offset))
+    return weight * (lb if float(lb) < float(la) else la)
+
+
+def make_case(kind, H, W, seed):
+    g = torch.Generator().manual_seed(seed)
+    if kind == "random":
+        p = torch.rand(H, W, generator=g) * 5.0
+        d = 3.0 - 0.3 * p + torch.rand(H, W, generator=g) * 2.0 + 1.0
+    elif kind == "cancel":                      # depths at 50 with a spread of 1e-3: sum(x^2) - n mean^2 would cancel
+        z = torch.randn(H, W, generator=g)
+        d = 50.0 + 1e-3 * z
+        p = 0.02 + 1e-4 * (0.7 * z + 0.7 * torch.randn(H, W, generator=g))
+    elif kind == "inv":                         # d ~ 1 / (p + 200): branch B wins
+        p = torch.rand(H, W, generator=g) * 5000.0
+        d = (1.0 / (p + 200.0)) * (1.0 + 0.05 * torch.randn(H, W, generator=g))
+    elif kind == "flat":                        # a constant render (an empty view)
+        p = torch.rand(H, W, generator=g)
+        d = torch.full((H, W), 7.0)
+    else:
+        raise ValueError(kind)
+    return d.float()[None].contiguous(), p.float().contiguous()
+
+
+SHAPES = [(37, 53), (72, 104), (1080, 1920)]
+KINDS = ["random", "cancel", "inv", "flat"]
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("kind", KINDS)
+def test_op_matches_float64_restatement(kind, shape, gpu, measurements):
+    from syn3r_amd.gs.train_ops import depth_correlation_loss, depth_correlation_loss_step
+    H, W = shape
+    d, p = make_case(kind, H, W, seed=H + 7 * KINDS.index(kind))
+    w = 0.3
+    ref = ref_dcorr(d, p, w)
+    if kind == "inv":
+        assert ref["branch"] == 1
+    loss, grad, parts = depth_correlation_loss_step(d.to(gpu), p.to(gpu), w, return_parts=True)
+    parts = parts.cpu()
+    assert loss.shape == () and loss.is_cuda and grad.shape == d.shape
+    assert int(parts[3]) == ref["branch"]
+    assert torch.isfinite(parts).all() and torch.isfinite(grad).all()
+    lerr = abs(float(loss) - ref["loss"]) / abs(ref["loss"])
+    assert lerr <= 1e-5, (float(loss), ref["loss"])
+    assert abs(float(parts[1]) - ref["ra"]) <= 1e-6 and abs(float(parts[2]) - ref["rb"]) <= 1e-6
+    gref = ref["grad"].reshape(d.shape)
+    scale = float(gref.abs().max())
+    gerr = float((grad.cpu().double() - gref).abs().max())
+    measurements("depth_corr_op", kind=kind, shape=list(shape), loss_rel=lerr, grad_rel=gerr / scale if scale else gerr)
+    if kind == "flat":                          # documented: r = 0, loss = weight, zero gradient (no NaN)
+        assert float(loss) == float(np.float32(w)) and float(parts[1]) == 0.0 and float(parts[2]) == 0.0
+        assert int(parts[3]) == 0 and not grad.any()
+    else:
+        assert gerr <= 1e-5 * scale, (gerr, scale)
+    # the autograd op, a prior given as [1,H,W], and single-branch modes
+    x = d.to(gpu).requires_grad_(True)
+    loss2 = depth_correlation_loss(x, p.to(gpu)[None], w)
+    loss2.backward()
+    assert torch.equal(loss2.detach(), loss) and torch.equal(x.grad, grad)
+    for mode in ("A", "B"):
+        r_m = ref_dcorr(d, p, w, mode=mode)
+        l_m = depth_correlation_loss(d.to(gpu), p.to(gpu), w, mode=mode)
+        assert abs(float(l_m) - r_m["loss"]) <= 1e-5 * abs(r_m["loss"])
+
+
+def test_misaligned_inputs_and_ragged_tail(gpu):
+    """Inputs that are not 16-byte aligned take the scalar walk; n not a multiple of 4 leaves a ragged tail."""
+    from syn3r_amd.gs.train_ops import depth_correlation_loss_step
+    H, W = 31, 45
+    d, p = make_case("random", H, W, seed=3)
+    buf_d = torch.zeros(H * W + 1, device=gpu)
+    buf_p = torch.zeros(H * W + 3, device=gpu)
+    buf_d[1:] = d.reshape(-1).to(gpu)
+    buf_p[3:] = p.reshape(-1).to(gpu)
+    dm, pm = buf_d[1:].view(1, H, W), buf_p[3:].view(H, W)
+    assert dm.data_ptr() % 16 and pm.data_ptr() % 16
+    ref = ref_dcorr(d, p, 1.0)
+    for dd, pp in ((dm, pm), (d.to(gpu), p.to(gpu))):
+        loss, grad = depth_correlation_loss_step(dd, pp)
+        assert abs(float(loss) - ref["loss"]) <= 1e-5 * ref["loss"]
+        gref = ref["grad"].reshape(d.shape)
+        assert float((grad.cpu().double() - gref).abs().max()) <= 1e-5 * float(gref.abs().max())
+
+
+def test_bitwise_repeatable_and_grad_loss_scaling(gpu):
+    from syn3r_amd.gs.train_ops import depth_correlation_loss, depth_correlation_loss_step
+    d, p = make_case("random", 270, 480, seed=11)
+    d, p = d.to(gpu), p.to(gpu)
+    l1, g1 = depth_correlation_loss_step(d, p, 0.05)
+    l2, g2 = depth_correlation_loss_step(d, p, 0.05)
+    assert torch.equal(l1, l2) and torch.equal(g1, g2)
+    # value-only entry = step entry; autograd backward = step gradient, bit for bit
+    x = d.clone().requires_grad_(True)
+    la = depth_correlation_loss(x, p, 0.05)
+    la.backward()
+    assert torch.equal(la.detach(), l1) and torch.equal(x.grad, g1)
+    # grad_loss: a power of two scales exactly; any other value equals autograd's upstream scalar
+    two = torch.tensor(2.0, device=gpu)
+    _, g4 = depth_correlation_loss_step(d, p, 0.05, grad_loss=two)
+    assert torch.equal(g4, 2.0 * g1)
+    x.grad = None
+    (depth_correlation_loss(x, p, 0.05) * 0.37).backward()
+    _, g37 = depth_correlation_loss_step(d, p, 0.05, grad_loss=torch.tensor(0.37, device=gpu))
+    assert torch.equal(x.grad, g37)
+    assert float((g37.double() - 0.37 * g1.double()).abs().max()) <= 1e-6 * float(g1.abs().max())
+
+
+def test_op_rejects_bad_shapes(gpu):
+    from syn3r_amd.gs.train_ops import depth_correlation_loss, depth_correlation_loss_step
+    d = torch.rand(1, 8, 8, device=gpu)
+    for bad in (torch.rand(8, 9, device=gpu), torch.rand(2, 8, 8, device=gpu), torch.rand(64, device=gpu),
+                torch.rand(8, 8, device=gpu).half()):
+        with pytest.raises(ValueError):
+            depth_correlation_loss(d, bad)
+        with pytest.raises(ValueError):
+            depth_correlation_loss_step(d, bad)
+    with pytest.raises(ValueError):
+        depth_correlation_loss(torch.rand(3, 8, 8, device=gpu), torch.rand(8, 8, device=gpu))
+    with pytest.raises(ValueError):
+        depth_correlation_loss(d, torch.rand(8, 8, device=gpu), mode="max")
+
+
+# ---------------------------------------------------------------- the trainer with the term on
+def _scene(N, H, W, seed, dev):
+    from tests.test_trainer_gpu import make_scene
+    return make_scene(N, H, W, seed, dev)
+
+
+def _prior(H, W, K, dev, seed=21):
+    """A disparity prior from ANOTHER cloud: correlated with nothing in particular, so the term has work to do."""
+    from syn3r_amd.gs import Camera, GSTrainer
+    from syn3r_amd.launch import truth_disparity
+    gm, _ = _scene(2000, H, W, seed, dev)
+    cam = Camera.from_w2c(np.eye(4, dtype=np.float32), K, H, W, data_device=dev)
+    return truth_disparity(GSTrainer(gm, [cam]), cam)
+
+
+def test_explicit_step_equals_autograd_step_with_depth_term(gpu):
+    from syn3r_amd.gs import Camera, GSTrainer, OptimizationParams
+    N, H, W = 3000, 72, 104
+    w2c = np.eye(4, dtype=np.float32)
+    target = torch.rand(3, H, W, generator=torch.Generator().manual_seed(5))
+    _, K = _scene(N, H, W, 7, gpu)
+    prior = _prior(H, W, K, gpu)
+    grads = {}
+    for explicit in (False, True):
+        gm, K = _scene(N, H, W, 7, gpu)
+        cam = Camera.from_w2c(w2c, K, H, W, image=target, data_device=gpu, cam_confidence=0.7, depth_image=prior)
+        tr = GSTrainer(gm, [cam], OptimizationParams(iterations=1, depth_weight=0.05))
+        if explicit:
+            loss, out = tr._explicit_step(cam)
+        else:
+            from syn3r_amd.gs.train_ops import depth_correlation_loss, photometric_loss
+            out = tr.render_view(cam)
+            loss = photometric_loss(out["render"], cam.original_image, 0.2, 0.7) + depth_correlation_loss(out["depth"], prior, 0.05)
+            loss.backward()
+        grads[explicit] = [float(loss.detach())] + [p.grad.detach().clone() for p in gm.parameters()]
+    assert abs(grads[True][0] - grads[False][0]) < 1e-6
+    for a, b in zip(grads[True][1:], grads[False][1:]):
+        scale = float(b.abs().max()) + 1e-20
+        assert float((a - b).abs().max()) <= 2e-5 * scale, (float((a - b).abs().max()), scale)
+    # the term is in the gradients: without it the position gradient differs
+    gm, K = _scene(N, H, W, 7, gpu)
+    cam = Camera.from_w2c(w2c, K, H, W, image=target, data_device=gpu, cam_confidence=0.7, depth_image=prior)
+    loss0, _ = GSTrainer(gm, [cam], OptimizationParams(iterations=1))._explicit_step(cam)
+    assert float(loss0) < grads[True][0]
+    assert float((gm._xyz.grad - grads[True][1]).abs().max()) > 1e-3 * float(grads[True][1].abs().max())
+    # and train_step takes the same term on the autograd path
+    finals = []
+    for explicit in (None, False):
+        gm, K = _scene(N, H, W, 7, gpu)
+        cam = Camera.from_w2c(w2c, K, H, W, image=target, data_device=gpu, cam_confidence=0.7, depth_image=prior)
+        tr = GSTrainer(gm, [cam], OptimizationParams(iterations=1, depth_weight=0.05))
+        finals.append(float(tr.train_step(cam, explicit=explicit)))
+    assert abs(finals[0] - finals[1]) < 1e-6 and abs(finals[0] - grads[True][0]) < 1e-6
+
+
+def test_one_step_with_depth_term_matches_oracle(gpu, measurements):
+    """One training step with the depth term against the fp64 oracle rasteriser + the restated Pearson term + torch.optim.Adam."""
+    from syn3r_amd.gs import Camera, GSTrainer, OptimizationParams
+    from tests.test_train_ops_gpu import _published_ssim
+    N, H, W = 400, 40, 56
+    gm, K = _scene(N, H, W, 3, gpu)
+    target = torch.rand(3, H, W, generator=torch.Generator().manual_seed(1))
+    prior = _prior(H, W, K, gpu, seed=8)
+    dw = 0.05
+    cam = Camera.from_w2c(np.eye(4, dtype=np.float32), K, H, W, image=target, data_device=gpu, cam_confidence=0.5, depth_image=prior)
+    tr = GSTrainer(gm, [cam], OptimizationParams(iterations=1, depth_weight=dw))
+    P = [p.detach().cpu().double().clone().requires_grad_(True) for p in gm.parameters()]   # xyz, sh, opac, scale, rot
+    oc, _, od, _, _ = RO.rasterize(P[0], torch.exp(P[3]), torch.nn.functional.normalize(P[4]), torch.sigmoid(P[2]), P[1],
+                                   torch.ones(N, dtype=torch.float64), cam.world_view_transform.cpu().double(),
+                                   cam.full_proj_transform.cpu().double(), cam.camera_center.cpu().double(),
+                                   math.tan(cam.FoVx / 2), math.tan(cam.FoVy / 2), H, W, torch.zeros(3, dtype=torch.float64), 3)
+    photo = 0.5 * (0.8 * (oc - target.double()).abs().mean() + 0.2 * (1.0 - _published_ssim(oc, target.double())))
+    dterm = ref_dcorr_torch(od, prior.cpu().double(), dw)
+    loss_o = photo + dterm
+    opt = torch.optim.Adam([{"params": [P[0]], "lr": 1.6e-4}, {"params": [P[1]], "lr": 2.5e-3}, {"params": [P[2]], "lr": 5e-2},
+                            {"params": [P[3]], "lr": 5e-3}, {"params": [P[4]], "lr": 1e-3}], eps=1e-15)
+    loss_o.backward()
+    # the explicit step's raw-parameter gradients against the oracle's (before the update)
+    loss_e, _ = tr._explicit_step(cam)
+    errs = []
+    for a, b in zip(gm.parameters(), P):
+        scale = float(b.grad.abs().max()) + 1e-20
+        errs.append(float((a.grad.detach().cpu().double() - b.grad).abs().max()) / scale)
+    measurements("depth_term_oracle_step", loss_hip=float(loss_e), loss_oracle=float(loss_o), dterm=float(dterm), grad_rel=errs)
+    assert abs(float(loss_e) - float(loss_o)) < 1e-4
+    assert max(errs) < 5e-3, errs
+    opt.step()
+    for p_ in gm.parameters():
+        p_.grad = None
+    loss_h = tr.train_step(cam)
+    assert torch.is_tensor(loss_h) and loss_h.is_cuda
+    assert abs(float(loss_h) - float(loss_o)) < 1e-4
+    for a, b in zip(gm.parameters(), P):
+        d = (a.detach().cpu().double() - b.detach()).abs()
+        assert (d > 1e-6).double().mean() < 2e-2
+
+
+def _step_bits(tr, cam, seen):
+    """The explicit step's loss and the loss gradients it hands the rasteriser's backward (bitwise: both come from fixed-order
+    kernels), and the parameter gradients (the rasteriser's backward accumulates with float atomics: equal to rounding)."""
+    seen.clear()
+    loss, out = tr._explicit_step(cam)
+    (g_color, g_depth), = seen
+    return [loss.clone(), g_color, g_depth], [p.grad.detach().clone() for p in tr.gaussians.parameters()] + [out["viewspace_grad"].clone()]
+
+
+def _same(a, b):
+    bits_a, grads_a = a
+    bits_b, grads_b = b
+    assert torch.equal(bits_a[0], bits_b[0]) and torch.equal(bits_a[1], bits_b[1])
+    assert (bits_a[2] is None) == (bits_b[2] is None) and (bits_a[2] is None or torch.equal(bits_a[2], bits_b[2]))
+    for x, y in zip(grads_a, grads_b):
+        assert float((x - y).abs().max()) <= 2e-5 * (float(y.abs().max()) + 1e-20)
+
+
+def test_default_leaves_the_step_unchanged(gpu, monkeypatch):
+    """depth_weight = 0 (with a prior on the camera), or a camera without a prior and no depth_net: the explicit step's loss and
+    the gradients it forms are bitwise those of a trainer built without any of it, and the rasteriser gets no depth gradient.
+    depth_net runs once per camera, and only with the term on."""
+    from syn3r_amd import raster
+    from syn3r_amd.gs import Camera, GSTrainer, OptimizationParams
+    seen = []
+    real_bwd = raster.rasterize_backward
+
+    def spy(st, g_color, g_depth=None, g_alpha=None):
+        seen.append((g_color.clone(), None if g_depth is None else g_depth.clone()))
+        return real_bwd(st, g_color, g_depth, g_alpha)
+    monkeypatch.setattr(raster, "rasterize_backward", spy)
+    N, H, W = 2000, 48, 64
+    target = torch.rand(3, H, W, generator=torch.Generator().manual_seed(2))
+    _, K = _scene(N, H, W, 4, gpu)
+    prior = _prior(H, W, K, gpu)
+    w2c = np.eye(4, dtype=np.float32)
+
+    def run(opt, **cam_kw):
+        gm, _ = _scene(N, H, W, 4, gpu)
+        cam = Camera.from_w2c(w2c, K, H, W, image=target, data_device=gpu, **cam_kw)
+        tr = GSTrainer(gm, [cam], opt)
+        return tr, cam
+
+    base = _step_bits(*run(OptimizationParams()), seen)
+    assert base[0][2] is None
+    for opt, kw in ((OptimizationParams(depth_weight=0.0), dict(depth_image=prior)),
+                    (OptimizationParams(depth_weight=0.05), {})):
+        _same(base, _step_bits(*run(opt, **kw), seen))
+    calls = []
+
+    def depth_net(img):
+        calls.append(img.shape)
+        return prior.clone()
+
+    tr, cam = run(OptimizationParams(depth_weight=0.0))
+    tr.depth_net = depth_net
+    _same(base, _step_bits(tr, cam, seen))
+    assert not calls and cam.depth_image is None
+    tr, cam = run(OptimizationParams(depth_weight=0.05))
+    tr.depth_net = depth_net
+    on = _step_bits(tr, cam, seen)
+    assert on[0][2] is not None and not torch.equal(on[0][0], base[0][0])
+    _step_bits(tr, cam, seen)
+    assert len(calls) == 1 and calls[0] == (3, H, W) and torch.equal(cam.depth_image, prior)
+    tr2, cam2 = run(OptimizationParams(depth_weight=0.05), depth_image=prior)
+    _same(on, _step_bits(tr2, cam2, seen))
+    # pseudo-views registered by update_cameras get their prior from depth_net the same way
+    tr.update_cameras([target.to(gpu)], [w2c], K, 0.5)
+    pv = tr.pseudo_cameras[0]
+    assert pv.depth_image is None
+    tr._explicit_step(pv)
+    assert len(calls) == 2 and pv.depth_image is not None
+
+
+def _mean_corr(tr, cams):
+    """Mean over the views of 1 - L / weight: the Pearson correlation of the branch the term takes."""
+    from syn3r_amd.gs.train_ops import depth_correlation_loss
+    rs = []
+    with torch.no_grad():
+        for c in cams:
+            _, parts = depth_correlation_loss(tr.render_view(c)["depth"], c.depth_image, 1.0, return_parts=True)
+            rs.append(1.0 - float(parts[0]))
+    return float(np.mean(rs))
+
+
+def test_depth_term_raises_the_correlation(gpu, tmp_path, measurements):
+    from syn3r_amd import launch
+    res = {}
+    for dw in (0.0, 0.5):
+        args = launch.parse(["--scenes", "synthetic:0", "--model_path", str(tmp_path / f"w{dw}"), "--iterations", "300"])
+        sc = launch.synthetic_scene("synthetic:0", args, gpu)
+        tr = sc["trainer"]
+        cams = tr.scene.getTrainCameras()
+        assert all(c.depth_image is not None and c.depth_image.shape == (72, 128) for c in cams)
+        tr.opt.depth_weight = dw
+        r0 = _mean_corr(tr, cams)
+        tr.training(iterations=300, disable_densification=True)
+        res[dw] = (r0, _mean_corr(tr, cams))
+    measurements("depth_term_correlation", r_start=res[0.5][0], r_end_on=res[0.5][1], r_end_off=res[0.0][1])
+    print(f"Pearson at iteration 0: {res[0.5][0]:.5f}; after 300 iterations: term on {res[0.5][1]:.5f}, off {res[0.0][1]:.5f}")
+    assert res[0.0][0] == res[0.5][0]
+    assert res[0.5][1] > res[0.5][0]
+    assert res[0.5][1] > res[0.0][1]
