@@ -331,26 +331,32 @@ int syn3r_sort_pairs(unsigned long long* keys, unsigned* vals, unsigned long lon
  * SVD_2pass_prob_uncertain.py:661-742, in one launch).  rv_group_rows = 0: one group.
  * K % 64 == 0; strides in elements, multiples of 8; pointers 16-byte aligned;
  * bias / rowvec / residual / aux may be NULL.
+ * gn_partials / gn_partials_bytes / gn_written (host, may be NULL): GroupNorm partial sums of the output, see
+ * "GroupNorm statistics out of the PRODUCER's epilogue" below; (NULL, 0, NULL) = no request.
  */
 int syn3r_gemm_f16(const void* A, long long lda, const void* W, void* out, long long ldc, const void* bias,
                    const void* rowvec, long long ldrv, int rows_per_vec, int rv_group_rows, const void* residual, long long ldr,
                    const void* aux, long long ldaux, float s_acc, float s_res, float s_aux, int M, int N, int K,
-                   void* stream);
+                   void* gn_partials, size_t gn_partials_bytes, int* gn_written, void* stream);
 
 /* out[M,N] = [A1 | A2][M, K1+K2] . W[N, K1+K2]^T + bias: the contraction reads the two halves of a channel concatenation
  * in place (resnet.py:316 conv_shortcut applied to torch.cat([hidden, skip], dim=1), unet_3d_blocks.py up blocks), so the
  * concatenated tensor is never written.  K1, K2 % 64 == 0; served by the persistent 256 x 320 kernel only:
- * syn3r_gemm_2src_supported() != 0 is the admission test (otherwise concatenate and call syn3r_gemm_f16). */
+ * syn3r_gemm_2src_supported() != 0 is the admission test (otherwise concatenate and call syn3r_gemm_f16).
+ * gn_partials / gn_partials_bytes / gn_written: as for syn3r_gemm_f16. */
 int syn3r_gemm_2src_supported(int M, int N, int K1, int K2, long long lda1, long long lda2);
 int syn3r_gemm_2src_f16(const void* A1, long long lda1, int K1, const void* A2, long long lda2, int K2, const void* W,
-                        void* out, long long ldc, const void* bias, int M, int N, void* stream);
+                        void* out, long long ldc, const void* bias, int M, int N, void* gn_partials, size_t gn_partials_bytes,
+                        int* gn_written, void* stream);
 
 /* Test / tuning hook, PER CALLING THREAD (thread-local: the library holds no state shared between host threads): the
  * contraction kernel family this thread's next launches use.  0 = chosen per shape (default); -128 / -256 = the 160-column
  * LDS-DMA kernel of that block height; -320 = the persistent 256 x 320 kernel wherever it admits the shape; -322 = the
  * software-pipelined persistent 256 x 320 kernel (dense, two-source and implicit-GEMM convolution modes) wherever it admits
  * the shape.  This hook and the split-K workspace below are the library's only settings, both per calling thread; it reads no
- * environment variable (dispatch switches for A/B measurements exist in -DSYN3R_TUNING developer builds only). */
+ * environment variable (dispatch switches for A/B measurements exist in -DSYN3R_TUNING developer builds only).  They stay
+ * per-thread settings rather than arguments: the hook has to reach launches made deep inside a host's operators, and the
+ * workspace is set once per forward, not per launch. */
 int syn3r_gemm_set_tile(int bm);
 
 /* Split-K scratch, PER CALLING THREAD (round 4).  With a workspace set, the contractions (syn3r_gemm_f16, syn3r_gemm_2src_f16
@@ -458,19 +464,22 @@ int syn3r_layernorm_linear320_f16(const void* x, long long ldx, const void* ln_g
  * (0,1,0,1) — nothing before the first row/column, one zero row/column after the last (downsampling.py:140-143).
  * X [NB,Hi,Wi,Cin], W [Cout, 3, 3, Cin] (= the Conv2d weight permuted to OHWI), Cin % 64 == 0.
  * out [NB*Ho*Wo, Cout] with the gemm epilogue (aux excluded); Ho = (Hg + pad_lo - 2) / stride + 1.
+ * gn_partials / gn_partials_bytes / gn_written: as for syn3r_gemm_f16 (M = NB*Ho*Wo, N = Cout).
  */
 int syn3r_conv2d3x3_f16(const void* X, const void* W, void* out, long long ldc, const void* bias,
                         const void* rowvec, long long ldrv, int rows_per_vec, const void* residual, long long ldr,
                         float s_acc, float s_res, int NB, int Hi, int Wi, int Cin, int Cout, int stride, int upsample,
-                        int pad_lo, void* stream);
+                        int pad_lo, void* gn_partials, size_t gn_partials_bytes, int* gn_written, void* stream);
 
 /*
  * (3,1,1) Conv3d over frames, padding (1,0,0) (resnet.py:571-597) on [B,F,HW,Cin] fp16.
  * W [Cout, 3, Cin] (= the Conv3d weight [Cout,Cin,3,1,1] permuted), Cin % 64 == 0.
+ * gn_partials / gn_partials_bytes / gn_written: as for syn3r_gemm_f16 (M = B*F*HW, N = Cout).
  */
 int syn3r_tconv3_f16(const void* X, const void* W, void* out, long long ldc, const void* bias, const void* rowvec,
                      long long ldrv, int rows_per_vec, const void* residual, long long ldr, float s_acc, float s_res,
-                     int B, int F, int HW, int Cin, int Cout, void* stream);
+                     int B, int F, int HW, int Cin, int Cout, void* gn_partials, size_t gn_partials_bytes, int* gn_written,
+                     void* stream);
 
 /*
  * Self-attention over the S tokens of each of nseq sequences, head dim 64, scale 1/8
@@ -507,21 +516,21 @@ int syn3r_groupnorm_2src_f16(const void* x1, int C1, const void* x2, int C2, voi
  * output -> the next norm1; transformer_temporal.py:235), whose epilogue holds the values in registers: the statistics
  * pass over the activation (one full extra read) is not launched.
  *
- * syn3r_gemm_set_gn_partials(buf, bytes): the NEXT contraction the calling thread launches through syn3r_gemm_f16 /
- * syn3r_gemm_2src_f16 / syn3r_conv2d3x3_f16 / syn3r_tconv3_f16 also writes, for its [M, N] fp16 output as stored,
+ * The request and its answer are arguments of the producing call: syn3r_gemm_f16 / syn3r_gemm_2src_f16 / syn3r_conv2d3x3_f16 /
+ * syn3r_tconv3_f16 given gn_partials = buf (16-byte aligned) and gn_partials_bytes = bytes also write, for their [M, N] fp16
+ * output as stored,
  *     buf[((m / 32) * 2 + q) * (N / 10) + n / 10]   (float; q = 0: sum of x, q = 1: sum of x^2)
  * over rows [32 rb, 32 rb + 32) and columns [10 u, 10 u + 10) - if M % 32 == 0, N % 80 == 0, bytes >=
  * syn3r_gn_partials_bytes(M, N) and the kernel chosen for the shape has the lean epilogue (the persistent 256-row
- * kernels).  The request is consumed by that one call (thread_local, like the split-K workspace; nothing is shared between
- * host threads).  syn3r_gemm_gn_partials_written() tells whether the calling thread's LAST contraction wrote them; if not,
- * the consumer runs syn3r_groupnorm_f16 as before.  Fixed summation order: bitwise reproducible run to run.
+ * kernels).  *gn_written (host, may be NULL) is set on every return of these four entries, errors included: 1 if the launched
+ * kernel writes buf, else 0 - buf is then left untouched and the consumer runs syn3r_groupnorm_f16 as before.  It is known at
+ * launch time: no synchronisation.  (NULL, 0) = no request; a pointer without a size, a size without a pointer or a misaligned
+ * pointer is SYN3R_E_INVALID.  Fixed summation order: bitwise reproducible run to run.
  *
  * syn3r_groupnorm_pre_f16: syn3r_groupnorm_f16 / _2src_f16 (x2 = NULL, C2 = 0: one source) with the statistics folded from
  * such partial sums (part1 for x1, part2 for x2).  rows % 32 == 0, (C1 + C2) / 32 and C1 multiples of 10.  Same workspace.
  */
 size_t syn3r_gn_partials_bytes(int M, int N);
-int syn3r_gemm_set_gn_partials(void* partials, size_t bytes);
-int syn3r_gemm_gn_partials_written(void);
 int syn3r_groupnorm_pre_f16(const void* x1, int C1, const void* part1, const void* x2, int C2, const void* part2, void* y,
                             int samples, int rows, const void* gamma, const void* beta, float eps, int silu,
                             void* workspace, size_t workspace_bytes, void* stream);

@@ -67,7 +67,7 @@ SIGNATURES = {
     "syn3r_gaussian_activate_backward": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "syn3r_densification_stats": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "syn3r_gemm_f16": (c_i, [c_p, c_ll, c_p, c_p, c_ll, c_p, c_p, c_ll, c_i, c_i, c_p, c_ll, c_p, c_ll, c_f, c_f, c_f,
-                             c_i, c_i, c_i, c_p]),
+                             c_i, c_i, c_i, c_p, c_sz, C.POINTER(c_i), c_p]),
     "syn3r_gemm_set_tile": (c_i, [c_i]),
     "syn3r_gemm_geglu_f16": (c_i, [c_p, c_ll, c_p, c_p, c_p, c_ll, c_i, c_i, c_i, c_p]),
     "syn3r_feedforward_workspace_bytes": (c_sz, [c_i, c_i]),
@@ -84,9 +84,9 @@ SIGNATURES = {
                                                 c_f, c_f, c_f, c_i, c_i, c_p]),
     "syn3r_layernorm_linear320_f16": (c_i, [c_p, c_ll, c_p, c_p, c_f, c_p, c_p, c_ll, c_i, c_i, c_i, c_p]),
     "syn3r_conv2d3x3_f16": (c_i, [c_p, c_p, c_p, c_ll, c_p, c_p, c_ll, c_i, c_p, c_ll, c_f, c_f,
-                                  c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+                                  c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_sz, C.POINTER(c_i), c_p]),
     "syn3r_tconv3_f16": (c_i, [c_p, c_p, c_p, c_ll, c_p, c_p, c_ll, c_i, c_p, c_ll, c_f, c_f,
-                               c_i, c_i, c_i, c_i, c_i, c_p]),
+                               c_i, c_i, c_i, c_i, c_i, c_p, c_sz, C.POINTER(c_i), c_p]),
     "syn3r_attention_f16": (c_i, [c_p, c_p, c_p, c_ll, c_p, c_ll, c_i, c_i, c_i, c_p]),
     "syn3r_attention_temporal_f16": (c_i, [c_p, c_p, c_p, c_ll, c_p, c_ll, c_i, c_i, c_i, c_i, c_p]),
     "syn3r_groupnorm_workspace_bytes": (c_sz, [c_i, c_i]),
@@ -94,10 +94,8 @@ SIGNATURES = {
     "syn3r_groupnorm_2src_f16": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_f, c_i, c_p, c_sz, c_p]),
     "syn3r_groupnorm_pre_f16": (c_i, [c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_f, c_i, c_p, c_sz, c_p]),
     "syn3r_gn_partials_bytes": (c_sz, [c_i, c_i]),
-    "syn3r_gemm_set_gn_partials": (c_i, [c_p, c_sz]),
-    "syn3r_gemm_gn_partials_written": (c_i, []),
     "syn3r_gemm_2src_supported": (c_i, [c_i, c_i, c_i, c_i, c_ll, c_ll]),
-    "syn3r_gemm_2src_f16": (c_i, [c_p, c_ll, c_i, c_p, c_ll, c_i, c_p, c_p, c_ll, c_p, c_i, c_i, c_p]),
+    "syn3r_gemm_2src_f16": (c_i, [c_p, c_ll, c_i, c_p, c_ll, c_i, c_p, c_p, c_ll, c_p, c_i, c_i, c_p, c_sz, C.POINTER(c_i), c_p]),
     "syn3r_layernorm_f16": (c_i, [c_p, c_p, c_p, c_p, c_i, c_ll, c_i, c_p, c_p, c_f, c_p]),
     "syn3r_geglu_f16": (c_i, [c_p, c_p, c_ll, c_i, c_p]),
     "syn3r_softmax_rows_f16": (c_i, [c_p, c_p, c_ll, c_i, c_ll, c_f, c_p]),

@@ -25,7 +25,8 @@
 //   k_gemm_dmapd   persistent 256 x 160 tile with a deferred, LDS-free epilogue (gemm_dmapd.h): residual projections, 640 <= K <= 1280
 //   k_gemm_skinny  M <= 16 rows (time embedding, folded cross-attention context)
 // This file is the dispatch: the shape rules (launch_dma), the launchers and the C-ABI entry points; the kernel families live in
-// gemm_common.h / gemm_dma.h / gemm_wide.h / gemm_z.h / gemm_dmap.h / gemm_ffn.h, included below into ONE translation unit.
+// gemm_common.h / gemm_dma.h / gemm_wide.h / gemm_z.h / gemm_dmap.h / gemm_dmapd.h / gemm_g256.h / gemm_ffn.h, included below into
+// ONE translation unit.
 #include "common.h"
 #include <cstdlib>
 #include <algorithm>
@@ -63,23 +64,46 @@ int persistent_blocks() {
     return n;
 }
 
-// GroupNorm partial sums (GemmParams::gn_part) of the CALLING THREAD's next contraction (syn3r_gemm_set_gn_partials): the entry
-// points move the pending buffer into the launch's parameters (gn_take), the launchers of the kernels with the lean epilogue
-// report that they wrote it (syn3r_gemm_gn_partials_written); every other kernel leaves it untouched and the caller runs the
-// statistics pass.
-thread_local void* g_gn_pending = nullptr;
-thread_local size_t g_gn_pending_bytes = 0;
-thread_local bool g_gn_written = false;
+// GroupNorm partial sums of this launch's output (the gn_partials / gn_partials_bytes arguments of the four entries that serve them):
+// the request reaches the kernel as GemmParams::gn_part when the shape has whole 32-row blocks and 80-column groups; the kernels
+// with the lean epilogue write it and say so (launch_tiles, gn_written), every other kernel leaves the buffer untouched and the
+// caller runs the statistics pass.
 size_t gn_partials_bytes(long long M, long long N) { return (size_t)(M / 32) * 2 * (size_t)(N / 10) * sizeof(float); }
-// entry points whose kernels never write partial sums: a request left pending by the caller must not reach a later, unrelated launch
-void gn_drop() { g_gn_pending = nullptr; g_gn_pending_bytes = 0; g_gn_written = false; }
-void gn_take(GemmParams& p) {
-    g_gn_written = false;
-    void* buf = g_gn_pending;
-    const size_t bytes = g_gn_pending_bytes;
-    g_gn_pending = nullptr; g_gn_pending_bytes = 0;
-    if (!buf || p.M % 32 != 0 || p.N % 80 != 0 || p.geglu_D > 0 || p.out_tiled || bytes < gn_partials_bytes(p.M, p.N)) return;
+int gn_request(GemmParams& p, void* buf, size_t bytes, const char* who) {
+    SYN3R_REQUIRE((buf == nullptr) == (bytes == 0), "%s: gn_partials pointer and size must both be given or both be zero", who);
+    SYN3R_REQUIRE(((uintptr_t)buf % 16) == 0, "%s: the gn_partials buffer must be 16-byte aligned", who);
+    if (!buf || p.M % 32 != 0 || p.N % 80 != 0 || p.geglu_D > 0 || p.out_tiled || bytes < gn_partials_bytes(p.M, p.N)) return SYN3R_OK;
     p.gn_part = (float*)buf; p.gn_units = p.N / 10;
+    return SYN3R_OK;
+}
+
+// What every tile-kernel launch shares: the large-LDS attribute once per (kernel, device), the trace name (`base`, a format of up
+// to two ints; in detail mode followed by the shape and the epilogue: e2 = gated, e1 = residual), the launch and its check
+// (`family` names the kernel in the error message of either).
+// gn_written: where a kernel with the lean epilogue reports that it wrote GemmParams::gn_part (host, may be null); the launchers
+// of every other kernel pass null.
+template <void (*KERNEL)(GemmParams)>
+int launch_tiles(const char* family, size_t lds, long long grid, int block, hipStream_t stream, const GemmParams& q, int* gn_written,
+                 const char* base, int b0 = 0, int b1 = 0) {
+    static DevOnce once;       // (one per instantiation = per kernel)
+    if (int rc = set_max_lds(once, (const void*)KERNEL, (int)lds, family)) return rc;
+    char name[96];
+    if (trace_on()) {
+        const int n = snprintf(name, sizeof(name), base, b0, b1);
+        if (trace_detail()) snprintf(name + n, sizeof(name) - n, "[M%d,N%d,K%d,e%d]", q.M, q.N, q.K, q.geglu_D > 0 ? 2 : (q.residual != nullptr));
+    }
+    SYN3R_LAUNCH_NAMED(name, KERNEL, dim3((unsigned)grid), dim3(block), lds, stream, q);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("%s launch: %s", family, hipGetErrorString(e)); return SYN3R_E_HIP; }
+    if (gn_written) *gn_written = q.gn_part != nullptr;
+    return SYN3R_OK;
+}
+
+// tiles of the persistent 256 x 320 kernels, and whether they fill the 256 CUs (last round >= 80 % full)
+long long wide_tiles(const GemmParams& p) { return (long long)((p.M + WBM - 1) / WBM) * ((p.N + WBN - 1) / WBN); }
+bool wide_fills(const GemmParams& p) {
+    const long long tiles = wide_tiles(p), rounds = (tiles + 255) / 256;
+    return tiles * 10 >= rounds * 256 * 8;
 }
 
 // Tile columns per band of the persistent 256 x 320 kernels' tile order (bands of `band` tile columns, row-major inside a band: the
@@ -95,24 +119,12 @@ int band_width(const GemmParams& p) {
     return ((p.N + WBN - 1) / WBN > 4 && p.K <= 640) ? 3 : 4;
 }
 
-int launch_widep(const GemmParams& p, hipStream_t stream) {
+int launch_widep(const GemmParams& p, hipStream_t stream, int* gn_written) {
     constexpr size_t lds = (size_t)2 * W_STAGE + 16384;   // 163,840 B: the ring + the tail the epilogue staging runs into
     static_assert(8 * WM * EPI_LD * sizeof(__half) <= lds - W_STAGE, "epilogue staging must fit behind ring slot 0");
-    static DevOnce once;
-    if (int rc = set_max_lds(once, (const void*)k_gemm_widep, (int)(lds), "hipFuncSetAttribute(gemm_widep)")) return rc;
-    int tiles = ((p.M + WBM - 1) / WBM) * ((p.N + WBN - 1) / WBN);
-    const int blocks = std::min(tiles, persistent_blocks());
-    char name[96];
-    if (trace_on()) {
-        if (trace_detail()) snprintf(name, sizeof(name), "k_gemm_widep[M%d,N%d,K%d,e%d]", p.M, p.N, p.K, p.geglu_D > 0 ? 2 : (p.residual != nullptr));
-        else snprintf(name, sizeof(name), "k_gemm_widep");
-    }
     GemmParams q = p;
     q.band = band_width(p);
-    SYN3R_LAUNCH_NAMED(name, k_gemm_widep, dim3(blocks), dim3(512), lds, stream, q);
-    SYN3R_LAUNCH_CHECK("gemm_widep launch");
-    g_gn_written = p.gn_part != nullptr;
-    return SYN3R_OK;
+    return launch_tiles<k_gemm_widep>("gemm_widep", lds, std::min<long long>(wide_tiles(p), persistent_blocks()), 512, stream, q, gn_written, "k_gemm_widep");
 }
 
 // k_gemm_g256 (gemm_g256.h): the gated projection on whole 256 x 256 tiles into the A-tiled hidden activation
@@ -122,54 +134,32 @@ bool g256_admits(const GemmParams& p) {
            (long long)p.N * p.K < (1ll << 31);
 }
 int launch_g256(const GemmParams& p, hipStream_t stream) {
-    static DevOnce once;
-    if (int rc = set_max_lds(once, (const void*)k_gemm_g256, G_LDS, "hipFuncSetAttribute(gemm_g256)")) return rc;
     const int tiles = ((p.M + 255) / 256) * (p.N / 256);
-    const int blocks = std::min(tiles, persistent_blocks());
     GemmParams q = p;
     static const int band_env = tune_env("SYN3R_G256_BAND", 0);
     q.band = band_env > 0 ? band_env : 4;
-    char name[96];
-    if (trace_on()) {
-        if (trace_detail()) snprintf(name, sizeof(name), "k_gemm_g256[M%d,N%d,K%d,e2]", p.M, p.N, p.K);
-        else snprintf(name, sizeof(name), "k_gemm_g256");
-    }
-    SYN3R_LAUNCH_NAMED(name, k_gemm_g256, dim3(blocks), dim3(512), G_LDS, stream, q);
-    SYN3R_LAUNCH_CHECK("gemm_g256 launch");
-    return SYN3R_OK;
+    return launch_tiles<k_gemm_g256>("gemm_g256", G_LDS, std::min(tiles, persistent_blocks()), 512, stream, q, nullptr, "k_gemm_g256");
 }
 
 template <int MODE = MODE_DENSE>
-int launch_z(const GemmParams& p, hipStream_t stream) {
-    static DevOnce once, once2;
-    if (int rc = set_max_lds(once, (const void*)k_gemm_z<false, MODE>, Z_LDS, "hipFuncSetAttribute(gemm_z)")) return rc;
-    if constexpr (MODE == MODE_DENSE) { if (int rc = set_max_lds(once2, (const void*)k_gemm_z<true, MODE_DENSE>, Z_LDS, "hipFuncSetAttribute(gemm_z)")) return rc; }
-    if constexpr (MODE == MODE_CONV2D) { if (int rc = set_max_lds(once2, (const void*)k_gemm_z<false, MODE_CONV2D, true>, Z_LDS, "hipFuncSetAttribute(gemm_z)")) return rc; }
-    int tiles = ((p.M + WBM - 1) / WBM) * ((p.N + WBN - 1) / WBN);
-    const int blocks = std::min(tiles, persistent_blocks());
+int launch_z(const GemmParams& p, hipStream_t stream, int* gn_written) {
+    const long long blocks = std::min<long long>(wide_tiles(p), persistent_blocks());
     GemmParams q = p;
     q.band = band_width(p);
     if constexpr (MODE == MODE_CONV2D) q.a_bytes = (unsigned)((long long)(p.M / (p.Ho * p.Wo)) * p.Hi * p.Wi * p.Cin * 2);      // (launch_dma: < 2^32 - 2^20)
     if constexpr (MODE == MODE_TCONV) q.a_bytes = (unsigned)((long long)p.M * p.Cin * 2);
-    const GemmParams& p_ = q;
-    char name[96];
-    if (trace_on()) {
-        if (trace_detail()) snprintf(name, sizeof(name), "k_gemm_z<%d>[M%d,N%d,K%d,e%d]", MODE, p.M, p.N, p.K, p.geglu_D > 0 ? 2 : (p.residual != nullptr));
-        else snprintf(name, sizeof(name), "k_gemm_z<%d>", MODE);
-    }
     if constexpr (MODE == MODE_DENSE) {
-        if (p.A2) { SYN3R_LAUNCH_NAMED(name, (k_gemm_z<true, MODE_DENSE>), dim3(blocks), dim3(512), Z_LDS, stream, p_); SYN3R_LAUNCH_CHECK("gemm_z launch"); g_gn_written = p.gn_part != nullptr; return SYN3R_OK; }
+        if (p.A2) return launch_tiles<k_gemm_z<true, MODE_DENSE>>("gemm_z", Z_LDS, blocks, 512, stream, q, gn_written, "k_gemm_z<%d>", MODE);
     }
     if constexpr (MODE == MODE_CONV2D) {
-        if (p.ups) { SYN3R_LAUNCH_NAMED(name, (k_gemm_z<false, MODE_CONV2D, true>), dim3(blocks), dim3(512), Z_LDS, stream, p_); SYN3R_LAUNCH_CHECK("gemm_z launch"); g_gn_written = p.gn_part != nullptr; return SYN3R_OK; }
+        if (p.ups) return launch_tiles<k_gemm_z<false, MODE_CONV2D, true>>("gemm_z", Z_LDS, blocks, 512, stream, q, gn_written, "k_gemm_z<%d>", MODE);
     }
-    SYN3R_LAUNCH_NAMED(name, (k_gemm_z<false, MODE>), dim3(blocks), dim3(512), Z_LDS, stream, p_);
-    SYN3R_LAUNCH_CHECK("gemm_z launch");
-    g_gn_written = p.gn_part != nullptr;
-    return SYN3R_OK;
+    return launch_tiles<k_gemm_z<false, MODE>>("gemm_z", Z_LDS, blocks, 512, stream, q, gn_written, "k_gemm_z<%d>", MODE);
 }
 
-// Kernel family forced by the CALLING THREAD (syn3r_gemm_set_tile, see launch_dma); thread_local: no state shared between host threads
+// Kernel family forced by the CALLING THREAD (syn3r_gemm_set_tile; tests and tuning tools): 0 = by shape, 128 / 256 = the
+// 160-column LDS-DMA kernel of that block height, -320 = the persistent 256 x 320 kernel k_gemm_widep wherever it admits the
+// shape, -322 = the software-pipelined 256 x 320 kernel k_gemm_z (dense, two-source, convolutions).  thread_local: no state shared between host threads (SURVEY.md 8b).
 thread_local int g_dma_bm = 0;
 // Split-K scratch of the CALLING THREAD (syn3r_gemm_set_splitk_workspace): null = no split-K
 thread_local void* g_splitk_ws = nullptr;
@@ -179,10 +169,10 @@ thread_local size_t g_splitk_bytes = 0;
 // profiles/r04/gemm_z_ab.txt) the software-pipelined k_gemm_z is 1.6..3.5 % faster on the gated projections and 1..5 %
 // slower on the residual-add ones, a wash on their sum (74.33 against 74.23 ms): it takes the gated shapes.
 // SYN3R_GEMM_Z overrides (tuning): 0 = never, 1 = every shape the 256 x 320 tile is chosen for.
-int wide_launch(const GemmParams& p, hipStream_t stream) {
+int wide_launch(const GemmParams& p, hipStream_t stream, int* gn_written) {
     static const int z_env = tune_env("SYN3R_GEMM_Z", -1);
     const bool z = g_dma_bm == -322 ? true : (g_dma_bm == -320 ? false : (z_env < 0 ? p.geglu_D > 0 : z_env != 0));
-    return z ? launch_z<MODE_DENSE>(p, stream) : launch_widep(p, stream);
+    return z ? launch_z<MODE_DENSE>(p, stream, gn_written) : launch_widep(p, stream, gn_written);
 }
 
 // Does the persistent 256 x 320 kernel take this contraction?  Lean epilogue (no row vector together with a gate, aux only
@@ -195,24 +185,10 @@ bool widep_admits(const GemmParams& p) {
     return lean && small && p.M % 8 == 0 && p.N % 8 == 0 && p.M >= 8 && p.N >= 8;
 }
 
-// Kernel family forced by the CALLING THREAD (syn3r_gemm_set_tile; tests and tuning tools): 0 = by shape, 128 / 256 = the
-// 160-column LDS-DMA kernel of that block height, -320 = the persistent 256 x 320 kernel k_gemm_widep wherever it admits the
-// shape, -322 = the software-pipelined 256 x 320 kernel k_gemm_z (dense, two-source, convolutions).  thread_local: no state shared between host threads (SURVEY.md 8b).
-
 int launch_dmapd(const GemmParams& p, hipStream_t stream) {
     constexpr size_t lds = (size_t)3 * (256 * BK * 2 + DMA_B_BYTES);   // 159,744 B
-    static DevOnce once;
-    if (int rc = set_max_lds(once, (const void*)k_gemm_dmapd, (int)lds, "hipFuncSetAttribute(gemm_dmapd)")) return rc;
     const int tiles = ((p.M + 255) / 256) * ((p.N + BN - 1) / BN);
-    const int blocks = std::min(tiles, persistent_blocks());
-    char name[96];
-    if (trace_on()) {
-        if (trace_detail()) snprintf(name, sizeof(name), "k_gemm_dmapd[M%d,N%d,K%d,e%d]", p.M, p.N, p.K, p.residual != nullptr);
-        else snprintf(name, sizeof(name), "k_gemm_dmapd");
-    }
-    SYN3R_LAUNCH_NAMED(name, k_gemm_dmapd, dim3(blocks), dim3(512), lds, stream, p);
-    SYN3R_LAUNCH_CHECK("gemm_dmapd launch");
-    return SYN3R_OK;
+    return launch_tiles<k_gemm_dmapd>("gemm_dmapd", lds, std::min(tiles, persistent_blocks()), 512, stream, p, nullptr, "k_gemm_dmapd");
 }
 
 // Does the deferred-epilogue kernel take this contraction?  Dense, row-major output, WHOLE 256 x 160 tiles (no row / column clamps in
@@ -225,32 +201,21 @@ bool dmapd_admits(const GemmParams& p) {
 }
 
 template <int MODE>
-int launch_dmap(const GemmParams& p, hipStream_t stream) {
+int launch_dmap(const GemmParams& p, hipStream_t stream, int* gn_written) {
     constexpr size_t lds = (size_t)3 * (256 * BK * 2 + DMA_B_BYTES);   // 159,744 B
     static_assert(8 * 32 * EPI_LD * sizeof(__half) <= 256 * BK * 2 + DMA_B_BYTES, "the two-pass epilogue staging must fit in one ring slot");
-    static DevOnce once;
-    if (int rc = set_max_lds(once, (const void*)k_gemm_dmap<MODE>, (int)(lds), "hipFuncSetAttribute(gemm_dmap)")) return rc;
     const int tiles = ((p.M + 255) / 256) * ((p.N + BN - 1) / BN);
-    const int blocks = std::min(tiles, persistent_blocks());
-    char name[96];
-    if (trace_on()) {
-        if (trace_detail()) snprintf(name, sizeof(name), "k_gemm_dmap<%d>[M%d,N%d,K%d,e%d]", MODE, p.M, p.N, p.K, p.residual != nullptr);
-        else snprintf(name, sizeof(name), "k_gemm_dmap<%d>", MODE);
-    }
     GemmParams q = p;
     q.tc_pb = q.tc_nf = 0;
     if constexpr (MODE == MODE_TCONV) {
         static const int tc_env = tune_env("SYN3R_TCONV_ORDER", 1);       // 0: rows in memory order (tuning builds)
         if (tc_env != 0 && p.HW % 256 == 0 && p.M % p.HW == 0 && p.M / p.HW > 1) { q.tc_pb = p.HW / 256; q.tc_nf = p.M / p.HW; }
     }
-    SYN3R_LAUNCH_NAMED(name, (k_gemm_dmap<MODE>), dim3(blocks), dim3(512), lds, stream, q);
-    SYN3R_LAUNCH_CHECK("gemm_dmap launch");
-    g_gn_written = p.gn_part != nullptr;
-    return SYN3R_OK;
+    return launch_tiles<k_gemm_dmap<MODE>>("gemm_dmap", lds, std::min(tiles, persistent_blocks()), 512, stream, q, gn_written, "k_gemm_dmap<%d>", MODE);
 }
 
 template <int MODE, int BM>
-int launch_dma_bm(const GemmParams& p, hipStream_t stream) {
+int launch_dma_bm(const GemmParams& p, hipStream_t stream, int* gn_written) {
     if constexpr (BM == 256) {
         static const int pers_env = tune_env("SYN3R_DMA_PERSISTENT", 1);       // 0: the one-tile-per-block kernel (tuning builds)
         // the lean epilogue: no GEGLU gate, aux only together with a residual, whole 16-byte chunks of columns
@@ -258,21 +223,12 @@ int launch_dma_bm(const GemmParams& p, hipStream_t stream) {
         // projections -11 %, temporal convolutions -1..-5 %, 3x3 convolutions +1..+3 % (their k-loops are 45-360 k-tiles
         // long: nothing to hide at a tile boundary, and the cursor's bookkeeping is in the loop) -> those keep one tile per block
         if (pers_env != 0 && MODE != MODE_CONV2D && p.geglu_D <= 0 && (!p.aux || p.residual) && p.N % 8 == 0 && p.N >= 8)
-            return launch_dmap<MODE>(p, stream);
+            return launch_dmap<MODE>(p, stream, gn_written);
     }
     constexpr size_t lds = (size_t)(BM == 256 ? 3 : 2) * (BM * BK * 2 + DMA_B_BYTES);   // 159,744 B / 73,728 B
     static_assert((BM / 32) * WM * EPI_LD * sizeof(__half) <= lds, "epilogue staging must fit in the ring");
-    static DevOnce once;
-    if (int rc = set_max_lds(once, (const void*)k_gemm_dma<MODE, BM>, (int)lds, "hipFuncSetAttribute(gemm_dma)")) return rc;
-    int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    char name[96];
-    if (trace_on()) {
-        if (trace_detail()) snprintf(name, sizeof(name), "k_gemm_dma<%d,%d>[M%d,N%d,K%d,e%d]", MODE, BM, p.M, p.N, p.K, p.geglu_D > 0 ? 2 : (p.residual != nullptr));
-        else snprintf(name, sizeof(name), "k_gemm_dma<%d,%d>", MODE, BM);
-    }
-    SYN3R_LAUNCH_NAMED(name, (k_gemm_dma<MODE, BM>), dim3(tiles), dim3(BM * 2), lds, stream, p);
-    SYN3R_LAUNCH_CHECK("gemm_dma launch");
-    return SYN3R_OK;
+    const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
+    return launch_tiles<k_gemm_dma<MODE, BM>>("gemm_dma", lds, tiles, BM * 2, stream, p, nullptr, "k_gemm_dma<%d,%d>", MODE, BM);
 }
 
 // Split-K for the contractions whose grid leaves most of the chip idle (level 3 of the UNet at F = 14: M = 4 032 rows = 128
@@ -290,16 +246,11 @@ int launch_splitk(const GemmParams& p, hipStream_t stream, bool* done) {
         p.geglu_D > 0 || p.out_tiled || (p.A2 && (MODE != MODE_DENSE || p.a_tiled || (p.K1 / BK) % (nkt_all / S) != 0)))
         return SYN3R_OK;
     constexpr size_t lds = (size_t)3 * (256 * BK * 2 + DMA_B_BYTES);
-    static DevOnce once;
-    if (int rc = set_max_lds(once, (const void*)k_gemm_dma<MODE, 256>, (int)lds, "hipFuncSetAttribute(gemm_dma)")) return rc;
     GemmParams q = p;
     q.ksplit = S; q.split_ws = (float*)g_splitk_ws;
-    char name[96];
-    if (trace_on()) {
-        if (trace_detail()) snprintf(name, sizeof(name), "k_gemm_dma<%d,256>/%d[M%d,N%d,K%d,e%d]", MODE, S, p.M, p.N, p.K, p.residual != nullptr);
-        else snprintf(name, sizeof(name), "k_gemm_dma<%d,256>/k", MODE);
-    }
-    SYN3R_LAUNCH_NAMED(name, (k_gemm_dma<MODE, 256>), dim3((unsigned)(tiles256 * S)), dim3(512), lds, stream, q);
+    if (int rc = launch_tiles<k_gemm_dma<MODE, 256>>("gemm split-K", lds, tiles256 * S, 512, stream, q, nullptr,
+                                                     trace_detail() ? "k_gemm_dma<%d,256>/%d" : "k_gemm_dma<%d,256>/k", MODE, S))
+        return rc;
     const long long chunks = (long long)p.M * (p.N / 8);
     SYN3R_LAUNCH(k_splitk_finish, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, stream, q);
     SYN3R_LAUNCH_CHECK("gemm split-K launch");
@@ -308,7 +259,7 @@ int launch_splitk(const GemmParams& p, hipStream_t stream, bool* done) {
 }
 
 template <int MODE>
-int launch_dma(const GemmParams& p, hipStream_t stream) {
+int launch_dma(const GemmParams& p, hipStream_t stream, int* gn_written = nullptr) {
     static const int wide_env = tune_env("SYN3R_GEMM_WIDE", -1);       // -1 = by shape, 0 = never, 1 = always (tuning builds)
     if constexpr (MODE == MODE_DENSE) {
         // Round 6: the residual projections with 640 <= K <= 1280 (attn1 / attn2 to_out, proj_out at levels 1-2: [64512,640,640],
@@ -325,23 +276,21 @@ int launch_dma(const GemmParams& p, hipStream_t stream) {
             return launch_dmapd(p, stream);
     }
     const bool wide_ok = MODE == MODE_DENSE && widep_admits(p);
-    if (g_dma_bm == -320 && wide_ok) return launch_widep(p, stream);                              // syn3r_gemm_set_tile(-320)
-    if (g_dma_bm == -322 && wide_ok) return launch_z<MODE_DENSE>(p, stream);                      // syn3r_gemm_set_tile(-322)
+    if (g_dma_bm == -320 && wide_ok) return launch_widep(p, stream, gn_written);                              // syn3r_gemm_set_tile(-320)
+    if (g_dma_bm == -322 && wide_ok) return launch_z<MODE_DENSE>(p, stream, gn_written);                      // syn3r_gemm_set_tile(-322)
     if (g_dma_bm == 0 && wide_env != 0 && wide_ok) {
         // measured on MI355X inside the UNet (tools/gemm_ab.py, same box): the 256 x 320 tile is 7..14 % faster on
         // the dense contractions whenever its tiles fill the 256 CUs (last round >= 80 % full), except the
         // residual-add projections with K <= 320, whose time is their epilogue;
         // the implicit-GEMM convolutions are within 3 % either way and keep the 160-column kernel
-        const long long tiles = (long long)((p.M + WBM - 1) / WBM) * ((p.N + WBN - 1) / WBN);
-        const long long rounds = (tiles + 255) / 256;
-        const bool fills = tiles * 10 >= rounds * 256 * 8;
+        const bool fills = wide_fills(p);
         // (round 2: with the persistent kernel's epilogue - row vector, all ten residual requests in flight at once - the
         // K = 640 / 1280 residual projections are 3..4 % faster on the wide tile; K = 320 stays 4 % slower there)
         const bool short_residual = p.residual != nullptr && p.K <= 320;
         if (wide_env == 1 || (fills && !short_residual)) {
             // (the 128 x 320 two-blocks-per-CU variant that took the K <= 320, N > 640 shapes until round 4 is gone: the level-0
             // feed-forward and q / k / v projections it was built for run in k_ffn320r / k_lnlin320)
-            return wide_launch(p, stream);
+            return wide_launch(p, stream, gn_written);
         }
     }
     // Convolutions on the 256 x 320 tile (round 4, k_gemm_z<MODE>): lean epilogue (no ReLU options, aux only with a residual),
@@ -353,9 +302,7 @@ int launch_dma(const GemmParams& p, hipStream_t stream) {
     // columns: stays).  SYN3R_CONV_Z=0: never; 1: every admissible shape (tests, tuning).
     if constexpr (MODE != MODE_DENSE) {
         static const int cz_env = tune_env("SYN3R_CONV_Z", -1);
-        const long long tiles = (long long)((p.M + WBM - 1) / WBM) * ((p.N + WBN - 1) / WBN);
-        const long long rounds = (tiles + 255) / 256;
-        const bool fills = tiles * 10 >= rounds * 256 * 8;
+        const bool fills = wide_fills(p);
         const long long in_bytes = MODE == MODE_CONV2D ? (long long)(p.M / (p.Ho * p.Wo)) * p.Hi * p.Wi * p.Cin * 2 : (long long)p.M * p.Cin * 2;
         static const int czu_env = tune_env("SYN3R_CONV_Z_UPS", 1);       // 0: the fused-upsample convolutions stay on the 160-column kernel (tuning builds)
         const bool lean = !p.relu && !p.relu_mask && (!p.aux || p.residual) && p.geglu_D <= 0 && !p.A2 && !p.a_tiled &&
@@ -364,8 +311,8 @@ int launch_dma(const GemmParams& p, hipStream_t stream) {
         const bool ok = lean && p.M % 8 == 0 && p.N % 8 == 0 && p.M >= 8 && p.N >= 8 && p.M < (1 << 24) && in_bytes < (1ll << 32) - (1 << 20) &&
                         (long long)p.N * p.K < (1ll << 31) && p.Cin % BK == 0;
         const bool pays = MODE == MODE_CONV2D && p.N >= 320;
-        if (g_dma_bm == -322 && ok) return launch_z<MODE>(p, stream);                             // syn3r_gemm_set_tile(-322)
-        if (g_dma_bm == 0 && cz_env != 0 && ok && (cz_env == 1 || (fills && pays))) return launch_z<MODE>(p, stream);
+        if (g_dma_bm == -322 && ok) return launch_z<MODE>(p, stream, gn_written);                             // syn3r_gemm_set_tile(-322)
+        if (g_dma_bm == 0 && cz_env != 0 && ok && (cz_env == 1 || (fills && pays))) return launch_z<MODE>(p, stream, gn_written);
     }
     // 256-row blocks (eight wavefronts, wavefronts 4-7 staggered by half a k-tile against their SIMD partners) against
     // two independent 128-row blocks per CU, measured inside the UNet unit on MI355X (tools/unet_breakdown.py with
@@ -377,11 +324,8 @@ int launch_dma(const GemmParams& p, hipStream_t stream) {
     int rc = launch_splitk<MODE>(p, stream, &split);
     if (split || rc) return rc;
     int bm = g_dma_bm > 0 ? g_dma_bm : ((MODE != MODE_DENSE || tiles256 >= 256) ? 256 : 128);
-    return bm == 128 ? launch_dma_bm<MODE, 128>(p, stream) : launch_dma_bm<MODE, 256>(p, stream);
+    return bm == 128 ? launch_dma_bm<MODE, 128>(p, stream, gn_written) : launch_dma_bm<MODE, 256>(p, stream, gn_written);
 }
-
-template <int MODE>
-int launch(const GemmParams& p, hipStream_t stream) { return launch_dma<MODE>(p, stream); }
 
 int check_common(const GemmParams& p, const char* who) {
     SYN3R_REQUIRE(p.A && p.W && p.out, "%s: null operand", who);
@@ -395,6 +339,26 @@ int check_common(const GemmParams& p, const char* who) {
     SYN3R_REQUIRE(((uintptr_t)p.A | (uintptr_t)p.W | (uintptr_t)p.out | (uintptr_t)p.residual | (uintptr_t)p.aux) % 16 == 0,
                   "%s: operands must be 16-byte aligned", who);
     return SYN3R_OK;
+}
+
+// the workspace check and net.2 of the two FeedForward entries (`who`: the entry's name in error messages)
+int ffn_workspace_check(const char* who, const void* workspace, size_t workspace_bytes, size_t need) {
+    if (!workspace || workspace_bytes < need) {
+        set_error("%s: workspace %zu < %zu", who, workspace_bytes, need);
+        return SYN3R_E_WORKSPACE;
+    }
+    SYN3R_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", who);
+    return SYN3R_OK;
+}
+int ffn_net2(const char* who, const void* hidden_tiled, int D, const void* w2, const void* b2, void* out, long long ldc, const void* residual,
+             long long ldr, const void* aux, long long ldaux, float s_acc, float s_res, float s_aux, int M, int C_out, hipStream_t stream) {
+    GemmParams q{};
+    q.A = (const __half*)hidden_tiled; q.lda = D; q.a_tiled = 1; q.W = (const __half*)w2; q.out = (__half*)out; q.ldc = ldc;
+    q.bias = (const __half*)b2; q.residual = (const __half*)residual; q.ldr = ldr; q.aux = (const __half*)aux; q.ldaux = ldaux;
+    q.s_acc = s_acc; q.s_res = s_res; q.s_aux = s_aux; q.M = M; q.N = C_out; q.K = D;
+    int rc = check_common(q, who);
+    if (rc) return rc;
+    return launch_dma<MODE_DENSE>(q, stream);
 }
 
 }  // namespace
@@ -411,16 +375,6 @@ extern "C" size_t syn3r_gn_partials_bytes(int M, int N) {
     if (!SYN3R_DIM_OK(M) || !SYN3R_DIM_OK(N) || M % 32 != 0 || N % 80 != 0) return 0;
     return gn_partials_bytes(M, N);
 }
-
-extern "C" int syn3r_gemm_set_gn_partials(void* partials, size_t bytes) {
-    SYN3R_REQUIRE((partials == nullptr) == (bytes == 0), "gemm_set_gn_partials: pointer and size must both be given or both be zero");
-    SYN3R_REQUIRE(((uintptr_t)partials % 16) == 0, "gemm_set_gn_partials: the buffer must be 16-byte aligned");
-    g_gn_pending = partials;
-    g_gn_pending_bytes = bytes;
-    return SYN3R_OK;
-}
-
-extern "C" int syn3r_gemm_gn_partials_written(void) { return g_gn_written ? 1 : 0; }
 
 extern "C" int syn3r_gemm_set_tile(int bm) {
     SYN3R_REQUIRE(bm == 0 || bm == -128 || bm == -256 || bm == -320 || bm == -322, "gemm_set_tile: bm must be 0, -128, -256, -320 or -322");
@@ -494,31 +448,36 @@ int launch_skinny(const GemmParams& p, hipStream_t stream) {
 extern "C" int syn3r_gemm_f16(const void* A, long long lda, const void* W, void* out, long long ldc, const void* bias,
                               const void* rowvec, long long ldrv, int rows_per_vec, int rv_group_rows, const void* residual,
                               long long ldr, const void* aux, long long ldaux, float s_acc, float s_res, float s_aux,
-                              int M, int N, int K, void* stream) {
+                              int M, int N, int K, void* gn_partials, size_t gn_partials_bytes, int* gn_written, void* stream) {
+    if (gn_written) *gn_written = 0;
     GemmParams p{};
     p.A = (const __half*)A; p.lda = lda; p.W = (const __half*)W; p.out = (__half*)out; p.ldc = ldc;
     p.bias = (const __half*)bias; p.rowvec = (const __half*)rowvec; p.ldrv = ldrv; p.rows_per_vec = rows_per_vec;
     p.rv_group = rv_group_rows;
     p.residual = (const __half*)residual; p.ldr = ldr; p.aux = (const __half*)aux; p.ldaux = ldaux;
     p.s_acc = s_acc; p.s_res = s_res; p.s_aux = s_aux; p.M = M; p.N = N; p.K = K;
-    gn_take(p);
-    int rc = check_common(p, "gemm_f16");
+    int rc = gn_request(p, gn_partials, gn_partials_bytes, "gemm_f16");
+    if (rc) return rc;
+    rc = check_common(p, "gemm_f16");
     if (rc) return rc;
     SYN3R_REQUIRE(lda % 8 == 0 && lda >= K, "gemm_f16: lda=%lld must be >= K and a multiple of 8", lda);
     if (M <= SKINNY_MAX_M && !p.rowvec && !p.residual && !p.aux && g_dma_bm == 0)
         return launch_skinny(p, (hipStream_t)stream);
-    return launch<MODE_DENSE>(p, (hipStream_t)stream);
+    return launch_dma<MODE_DENSE>(p, (hipStream_t)stream, gn_written);
 }
 
 extern "C" int syn3r_gemm_2src_f16(const void* A1, long long lda1, int K1, const void* A2, long long lda2, int K2, const void* W,
-                                   void* out, long long ldc, const void* bias, int M, int N, void* stream) {
+                                   void* out, long long ldc, const void* bias, int M, int N, void* gn_partials, size_t gn_partials_bytes,
+                                   int* gn_written, void* stream) {
+    if (gn_written) *gn_written = 0;
     GemmParams p{};
     SYN3R_REQUIRE(A2 != nullptr && SYN3R_DIM_OK(K1) && SYN3R_DIM_OK(K2) && K1 % BK == 0 && K2 % BK == 0, "gemm_2src: K1=%d, K2=%d must be positive multiples of %d", K1, K2, BK);
     p.A = (const __half*)A1; p.lda = lda1; p.A2 = (const __half*)A2; p.lda2 = lda2; p.K1 = K1;
     p.W = (const __half*)W; p.out = (__half*)out; p.ldc = ldc; p.bias = (const __half*)bias;
     p.s_acc = 1.0f; p.s_res = 1.0f; p.s_aux = 1.0f; p.M = M; p.N = N; p.K = K1 + K2;
-    gn_take(p);
-    int rc = check_common(p, "gemm_2src_f16");
+    int rc = gn_request(p, gn_partials, gn_partials_bytes, "gemm_2src_f16");
+    if (rc) return rc;
+    rc = check_common(p, "gemm_2src_f16");
     if (rc) return rc;
     SYN3R_REQUIRE(lda1 % 8 == 0 && lda1 >= K1 && lda2 % 8 == 0 && lda2 >= K2 && ((uintptr_t)A2 % 16) == 0, "gemm_2src: bad strides / alignment");
     // only the persistent 256 x 320 kernel reads two sources; syn3r_gemm_2src_supported() is its admission test
@@ -527,12 +486,11 @@ extern "C" int syn3r_gemm_2src_f16(const void* A1, long long lda1, int K1, const
     bool split = false;
     rc = launch_splitk<MODE_DENSE>(p, (hipStream_t)stream, &split);     // a grid of a quarter of the chip: the two sources as K parts
     if (split || rc) return rc;
-    return wide_launch(p, (hipStream_t)stream);
+    return wide_launch(p, (hipStream_t)stream, gn_written);
 }
 
 extern "C" int syn3r_gemm_geglu_f16(const void* A, long long lda, const void* Wpacked, const void* bias_packed, void* out,
                                     long long ldc, int M, int D, int K, void* stream) {
-    gn_drop();
     GemmParams p{};
     SYN3R_REQUIRE(SYN3R_DIM_OK(D), "gemm_geglu_f16: bad D=%d", D);
     const int tiles = (D + WN - 1) / WN;
@@ -545,7 +503,7 @@ extern "C" int syn3r_gemm_geglu_f16(const void* A, long long lda, const void* Wp
     if (rc) return rc;
     p.ldc = save;
     SYN3R_REQUIRE(lda % 8 == 0 && lda >= K, "gemm_geglu_f16: lda=%lld must be >= K and a multiple of 8", lda);
-    return launch<MODE_DENSE>(p, (hipStream_t)stream);
+    return launch_dma<MODE_DENSE>(p, (hipStream_t)stream);
 }
 
 extern "C" size_t syn3r_feedforward_workspace_bytes(int M, int D) {
@@ -558,16 +516,11 @@ extern "C" int syn3r_feedforward_f16(const void* x, long long ldx, const void* w
                                      long long ldr, const void* aux, long long ldaux, float s_acc, float s_res,
                                      float s_aux, int M, int C_in, int C_out, void* workspace, size_t workspace_bytes,
                                      void* stream) {
-    gn_drop();
     SYN3R_REQUIRE(x && w1_packed && b1_packed && w2 && out, "feedforward_f16: null operand");
     SYN3R_REQUIRE(M > 0 && D > 0 && D % BK == 0 && C_in > 0 && C_out > 0, "feedforward_f16: bad sizes M=%d D=%d C_in=%d C_out=%d (D must be a multiple of %d)",
                   M, D, C_in, C_out, BK);
     const size_t need = syn3r_feedforward_workspace_bytes(M, D);
-    if (!workspace || workspace_bytes < need) {
-        set_error("feedforward_f16: workspace %zu < %zu", workspace_bytes, need);
-        return SYN3R_E_WORKSPACE;
-    }
-    SYN3R_REQUIRE((uintptr_t)workspace % 16 == 0, "feedforward_f16: workspace must be 16-byte aligned");
+    if (int rc = ffn_workspace_check("feedforward_f16", workspace, workspace_bytes, need)) return rc;
     // net.0 (GEGLU projection) -> the gated hidden activation in the A-tiled layout ...
     GemmParams p{};
     const int tiles = (D + WN - 1) / WN;
@@ -577,16 +530,10 @@ extern "C" int syn3r_feedforward_f16(const void* x, long long ldx, const void* w
     int rc = check_common(p, "feedforward_f16(net.0)");
     if (rc) return rc;
     SYN3R_REQUIRE(ldx % 8 == 0 && ldx >= C_in, "feedforward_f16: ldx=%lld must be >= C_in and a multiple of 8", ldx);
-    rc = launch<MODE_DENSE>(p, (hipStream_t)stream);
+    rc = launch_dma<MODE_DENSE>(p, (hipStream_t)stream);
     if (rc) return rc;
     // ... which net.2 reads as its A operand
-    GemmParams q{};
-    q.A = (const __half*)workspace; q.lda = D; q.a_tiled = 1; q.W = (const __half*)w2; q.out = (__half*)out; q.ldc = ldc;
-    q.bias = (const __half*)b2; q.residual = (const __half*)residual; q.ldr = ldr; q.aux = (const __half*)aux; q.ldaux = ldaux;
-    q.s_acc = s_acc; q.s_res = s_res; q.s_aux = s_aux; q.M = M; q.N = C_out; q.K = D;
-    rc = check_common(q, "feedforward_f16(net.2)");
-    if (rc) return rc;
-    return launch<MODE_DENSE>(q, (hipStream_t)stream);
+    return ffn_net2("feedforward_f16(net.2)", workspace, D, w2, b2, out, ldc, residual, ldr, aux, ldaux, s_acc, s_res, s_aux, M, C_out, (hipStream_t)stream);
 }
 
 extern "C" int syn3r_feedforward_p64_supported(int M, int D, int C_in) {
@@ -599,16 +546,11 @@ extern "C" int syn3r_feedforward_p64_f16(const void* x, long long ldx, const voi
                                          long long ldr, const void* aux, long long ldaux, float s_acc, float s_res,
                                          float s_aux, int M, int C_in, int C_out, void* workspace, size_t workspace_bytes,
                                          void* stream) {
-    gn_drop();
     SYN3R_REQUIRE(x && w1_packed64 && b1_packed64 && w2 && out, "feedforward_p64_f16: null operand");
     SYN3R_REQUIRE(syn3r_feedforward_p64_supported(M, D, C_in) != 0 && C_out > 0 && ldx == C_in,
                   "feedforward_p64_f16: shape M=%d D=%d C_in=%d not served (syn3r_feedforward_p64_supported; x must be dense rows)", M, D, C_in);
     const size_t need = syn3r_feedforward_workspace_bytes(M, D);
-    if (!workspace || workspace_bytes < need) {
-        set_error("feedforward_p64_f16: workspace %zu < %zu", workspace_bytes, need);
-        return SYN3R_E_WORKSPACE;
-    }
-    SYN3R_REQUIRE((uintptr_t)workspace % 16 == 0, "feedforward_p64_f16: workspace must be 16-byte aligned");
+    if (int rc = ffn_workspace_check("feedforward_p64_f16", workspace, workspace_bytes, need)) return rc;
     GemmParams p{};
     p.A = (const __half*)x; p.lda = ldx; p.W = (const __half*)w1_packed64; p.out = (__half*)workspace; p.ldc = 2ll * D;
     p.bias = (const __half*)b1_packed64; p.s_acc = 1.0f; p.M = M; p.N = 2 * D; p.K = C_in; p.geglu_D = D; p.out_tiled = 1;
@@ -618,13 +560,7 @@ extern "C" int syn3r_feedforward_p64_f16(const void* x, long long ldx, const voi
     SYN3R_REQUIRE(g256_admits(p), "feedforward_p64_f16: shape not admitted by the 256 x 256 kernel");
     rc = launch_g256(p, (hipStream_t)stream);
     if (rc) return rc;
-    GemmParams q{};
-    q.A = (const __half*)workspace; q.lda = D; q.a_tiled = 1; q.W = (const __half*)w2; q.out = (__half*)out; q.ldc = ldc;
-    q.bias = (const __half*)b2; q.residual = (const __half*)residual; q.ldr = ldr; q.aux = (const __half*)aux; q.ldaux = ldaux;
-    q.s_acc = s_acc; q.s_res = s_res; q.s_aux = s_aux; q.M = M; q.N = C_out; q.K = D;
-    rc = check_common(q, "feedforward_p64_f16(net.2)");
-    if (rc) return rc;
-    return launch<MODE_DENSE>(q, (hipStream_t)stream);
+    return ffn_net2("feedforward_p64_f16(net.2)", workspace, D, w2, b2, out, ldc, residual, ldr, aux, ldaux, s_acc, s_res, s_aux, M, C_out, (hipStream_t)stream);
 }
 
 namespace {
@@ -667,7 +603,6 @@ int feedforward_fused(const void* x, long long ldx, const void* ln_gamma, const 
                       const void* b1_chunked, int D, const void* w2, const void* b2, void* out, long long ldc, const void* residual,
                       long long ldr, const void* aux, long long ldaux, float s_acc, float s_res, float s_aux, int M, int C, void* stream,
                       const void* addvec, int rows_per_vec) {
-    gn_drop();
     SYN3R_REQUIRE(x && w1_chunked && b1_chunked && w2 && out, "feedforward_fused_f16: null operand");
     SYN3R_REQUIRE(C == F_C, "feedforward_fused_f16: the fused kernel is built for C = %d channels (got %d): use syn3r_feedforward_f16", F_C, C);
     SYN3R_REQUIRE(M > 0 && D >= F_HC && D % F_HC == 0, "feedforward_fused_f16: bad sizes M=%d D=%d (D must be a multiple of %d)", M, D, F_HC);
@@ -689,7 +624,6 @@ int feedforward_fused(const void* x, long long ldx, const void* ln_gamma, const 
 
 extern "C" int syn3r_layernorm_linear320_f16(const void* x, long long ldx, const void* ln_gamma, const void* ln_beta, float ln_eps,
                                              const void* W, void* out, long long ldc, int M, int N, int C, void* stream) {
-    gn_drop();
     SYN3R_REQUIRE(x && ln_gamma && ln_beta && W && out, "layernorm_linear320_f16: null operand");
     SYN3R_REQUIRE(C == F_C, "layernorm_linear320_f16: the kernel is built for C = %d channels (got %d): use syn3r_layernorm_f16 + syn3r_gemm_f16", F_C, C);
     SYN3R_REQUIRE(SYN3R_DIM_OK(M) && SYN3R_DIM_OK(N) && N % F_C == 0, "layernorm_linear320_f16: bad sizes M=%d N=%d (N must be a multiple of %d)", M, N, F_C);
@@ -706,7 +640,9 @@ extern "C" int syn3r_layernorm_linear320_f16(const void* x, long long ldx, const
 extern "C" int syn3r_conv2d3x3_f16(const void* X, const void* W, void* out, long long ldc, const void* bias,
                                    const void* rowvec, long long ldrv, int rows_per_vec, const void* residual,
                                    long long ldr, float s_acc, float s_res, int NB, int Hi, int Wi, int Cin, int Cout,
-                                   int stride, int upsample, int pad_lo, void* stream) {
+                                   int stride, int upsample, int pad_lo, void* gn_partials, size_t gn_partials_bytes, int* gn_written,
+                                   void* stream) {
+    if (gn_written) *gn_written = 0;
     SYN3R_REQUIRE(NB > 0 && Hi > 0 && Wi > 0 && Cin > 0 && Cout > 0, "conv2d3x3: bad sizes");
     SYN3R_REQUIRE(pad_lo == 0 || pad_lo == 1, "conv2d3x3: pad_lo must be 0 or 1");
     SYN3R_REQUIRE(stride == 1 || stride == 2, "conv2d3x3: stride must be 1 or 2");
@@ -724,15 +660,15 @@ extern "C" int syn3r_conv2d3x3_f16(const void* X, const void* W, void* out, long
     long long M = (long long)NB * p.Ho * p.Wo;
     SYN3R_REQUIRE(M < (1ll << 31), "conv2d3x3: too many output pixels");
     p.M = (int)M; p.N = Cout; p.K = 9 * Cin;
-    gn_take(p);
-    int rc = check_common(p, "conv2d3x3");
+    int rc = gn_request(p, gn_partials, gn_partials_bytes, "conv2d3x3");
     if (rc) return rc;
-    return launch<MODE_CONV2D>(p, (hipStream_t)stream);
+    rc = check_common(p, "conv2d3x3");
+    if (rc) return rc;
+    return launch_dma<MODE_CONV2D>(p, (hipStream_t)stream, gn_written);
 }
 
 extern "C" int syn3r_conv2d3x3_act_f16(const void* X, const void* W, void* out, const void* bias, int relu, const void* relu_mask,
                                        int NB, int Hi, int Wi, int Cin, int Cout, void* stream) {
-    gn_drop();
     SYN3R_REQUIRE(NB > 0 && Hi > 0 && Wi > 0 && Cin > 0 && Cout > 0, "conv2d3x3_act: bad sizes");
     SYN3R_REQUIRE(Cin % BK == 0 && Cout % 8 == 0, "conv2d3x3_act: Cin=%d must be a multiple of %d, Cout=%d of 8", Cin, BK, Cout);
     GemmParams p{};
@@ -747,13 +683,14 @@ extern "C" int syn3r_conv2d3x3_act_f16(const void* X, const void* W, void* out, 
     if (rc) return rc;
     SYN3R_REQUIRE(((uintptr_t)relu_mask % 16) == 0, "conv2d3x3_act: mask must be 16-byte aligned");
     // the persistent kernels have their own (lean) epilogue: the convolution modes never use them (launch_dma_bm)
-    return launch<MODE_CONV2D>(p, (hipStream_t)stream);
+    return launch_dma<MODE_CONV2D>(p, (hipStream_t)stream);
 }
 
 extern "C" int syn3r_tconv3_f16(const void* X, const void* W, void* out, long long ldc, const void* bias,
                                 const void* rowvec, long long ldrv, int rows_per_vec, const void* residual,
                                 long long ldr, float s_acc, float s_res, int B, int F, int HW, int Cin, int Cout,
-                                void* stream) {
+                                void* gn_partials, size_t gn_partials_bytes, int* gn_written, void* stream) {
+    if (gn_written) *gn_written = 0;
     SYN3R_REQUIRE(B > 0 && F > 0 && HW > 0 && Cin > 0 && Cout > 0, "tconv3: bad sizes");
     SYN3R_REQUIRE(Cin % BK == 0, "tconv3: Cin=%d must be a multiple of %d", Cin, BK);
     GemmParams p{};
@@ -764,10 +701,11 @@ extern "C" int syn3r_tconv3_f16(const void* X, const void* W, void* out, long lo
     long long M = (long long)B * F * HW;
     SYN3R_REQUIRE(M < (1ll << 31), "tconv3: too many rows");
     p.M = (int)M; p.N = Cout; p.K = 3 * Cin;
-    gn_take(p);
-    int rc = check_common(p, "tconv3");
+    int rc = gn_request(p, gn_partials, gn_partials_bytes, "tconv3");
     if (rc) return rc;
-    return launch<MODE_TCONV>(p, (hipStream_t)stream);
+    rc = check_common(p, "tconv3");
+    if (rc) return rc;
+    return launch_dma<MODE_TCONV>(p, (hipStream_t)stream, gn_written);
 }
 
 #ifdef SYN3R_TIMING

@@ -633,9 +633,9 @@ struct Arena {
     }
 };
 
-// an activation [rows, cols] in the arena; gnp: the GroupNorm partial sums its producer was asked for (syn3r_gemm_set_gn_partials),
-// gn_ok: the kernel that ran wrote them
-struct T { __half* p = nullptr; long long rows = 0; int cols = 0; float* gnp = nullptr; bool gn_ok = false; };
+// an activation [rows, cols] in the arena; gnp: the GroupNorm partial sums its producer was asked for (the gn_partials argument of
+// the contractions), gn_ok: the kernel that ran wrote them (their gn_written answer)
+struct T { __half* p = nullptr; long long rows = 0; int cols = 0; float* gnp = nullptr; int gn_ok = 0; };
 
 struct Epi {                                                              // the fused epilogue of syn3r_gemm_f16 and friends
     const __half* rowvec = nullptr; long long ldrv = 0; int rows_per_vec = 0, rv_group = 0;
@@ -669,22 +669,17 @@ struct Run {
         if (!t.p) { set_error("unet_forward: workspace too small (needs syn3r_unet_workspace_bytes)"); rc = SYN3R_E_WORKSPACE; }
         return t;
     }
-    void drop(T& t) { ar.release(t.p); t.p = nullptr; ar.release(t.gnp); t.gnp = nullptr; t.gn_ok = false; }
+    void drop(T& t) { ar.release(t.p); t.p = nullptr; ar.release(t.gnp); t.gnp = nullptr; t.gn_ok = 0; }
     // GroupNorm statistics from the producer's epilogue (model.py: gn_stats=TUNE["gn_epilogue"]): the buffer is part of the
     // allocation sequence whenever the shape can carry partial sums (dry runs see the same sequence); whether the kernel chosen
-    // for the shape wrote them is known after the launch
-    void gn_begin(T& out, bool want) {
+    // for the shape wrote them is the launch's answer (out.gn_ok).  Returns the size of out.gnp.
+    size_t gn_begin(T& out, bool want) {
         static const int gn_env = tune_env("SYN3R_GN_EPILOGUE", 1);
         const size_t nb = (want && gn_env != 0 && out.rows <= SYN3R_DIM_MAX) ? syn3r_gn_partials_bytes((int)out.rows, out.cols) : 0;
-        if (!nb || !ok()) return;
+        if (!nb || !ok()) return 0;
         out.gnp = (float*)ar.alloc(nb);
-        if (!out.gnp) { set_error("unet_forward: workspace too small (needs syn3r_unet_workspace_bytes)"); rc = SYN3R_E_WORKSPACE; return; }
-        if (go()) chk(syn3r_gemm_set_gn_partials(out.gnp, nb));
-    }
-    void gn_end(T& out) {
-        if (!out.gnp || !go()) return;
-        out.gn_ok = syn3r_gemm_gn_partials_written() != 0;
-        if (!out.gn_ok) syn3r_gemm_set_gn_partials(nullptr, 0);
+        if (!out.gnp) { set_error("unet_forward: workspace too small (needs syn3r_unet_workspace_bytes)"); rc = SYN3R_E_WORKSPACE; return 0; }
+        return nb;
     }
     void chk(int r) { if (r && !rc) rc = r; }
     bool go() const { return ok() && !dry; }
@@ -694,12 +689,11 @@ struct Run {
         const Wt* wt = W(wname);
         const __half* b = bias_name ? Wp(bias_name) : nullptr;
         T out = make(x.rows, wt ? (int)wt->rows : 0);
-        gn_begin(out, gn);
+        const size_t gnb = gn_begin(out, gn);
         if (go())
             chk(syn3r_gemm_f16(x.p, ldx, wt->p, out.p, out.cols, b, e.rowvec, e.ldrv, e.rows_per_vec, e.rv_group,
                                e.residual ? e.residual->p : nullptr, e.residual ? e.residual->cols : 0, e.aux ? e.aux->p : nullptr,
-                               e.aux ? e.aux->cols : 0, e.s_acc, e.s_res, e.s_aux, (int)x.rows, out.cols, K, stream));
-        gn_end(out);
+                               e.aux ? e.aux->cols : 0, e.s_acc, e.s_res, e.s_aux, (int)x.rows, out.cols, K, out.gnp, gnb, &out.gn_ok, stream));
         return out;
     }
     T linear(const T& x, const std::string& wname, const std::string& bname, const Epi& e = Epi(), bool gn = false) {
@@ -710,7 +704,7 @@ struct Run {
         const int N = wt ? (int)wt->rows : 0;
         if (ok() && syn3r_gemm_2src_supported((int)x1.rows, N, x1.cols, x2.cols, x1.cols, x2.cols)) {
             T out = make(x1.rows, N);
-            if (go()) chk(syn3r_gemm_2src_f16(x1.p, x1.cols, x1.cols, x2.p, x2.cols, x2.cols, wt->p, out.p, N, Wp(bname), (int)x1.rows, N, stream));
+            if (go()) chk(syn3r_gemm_2src_f16(x1.p, x1.cols, x1.cols, x2.p, x2.cols, x2.cols, wt->p, out.p, N, Wp(bname), (int)x1.rows, N, nullptr, 0, nullptr, stream));
             return out;
         }
         T cat = make(x1.rows, x1.cols + x2.cols);
@@ -731,22 +725,20 @@ struct Run {
         if (Ho_) *Ho_ = Ho;
         if (Wo_) *Wo_ = Wo;
         T out = make((long long)NB * Ho * Wo, Cout);
-        gn_begin(out, gn);
+        const size_t gnb = gn_begin(out, gn);
         if (go())
             chk(syn3r_conv2d3x3_f16(x.p, wt->p, out.p, Cout, Wp(bname), e.rowvec, e.ldrv, e.rows_per_vec, e.residual ? e.residual->p : nullptr,
-                                    e.residual ? Cout : 0, e.s_acc, e.s_res, NB, Hi, Wi, Cin, Cout, stride, ups ? 1 : 0, 1, stream));
-        gn_end(out);
+                                    e.residual ? Cout : 0, e.s_acc, e.s_res, NB, Hi, Wi, Cin, Cout, stride, ups ? 1 : 0, 1, out.gnp, gnb, &out.gn_ok, stream));
         return out;
     }
     T tconv3(const T& x, const std::string& wname, const std::string& bname, int HW, const Epi& e) {
         const Wt* wt = W(wname);
         const int Cout = wt ? (int)wt->rows : 0;
         T out = make(x.rows, Cout);
-        gn_begin(out, true);                     // (every temporal convolution's output is a GroupNorm input, model.py:_resblock)
+        const size_t gnb = gn_begin(out, true);  // (every temporal convolution's output is a GroupNorm input, model.py:_resblock)
         if (go())
             chk(syn3r_tconv3_f16(x.p, wt->p, out.p, Cout, Wp(bname), e.rowvec, e.ldrv, e.rows_per_vec, e.residual ? e.residual->p : nullptr,
-                                 e.residual ? Cout : 0, e.s_acc, e.s_res, B, F, HW, x.cols, Cout, stream));
-        gn_end(out);
+                                 e.residual ? Cout : 0, e.s_acc, e.s_res, B, F, HW, x.cols, Cout, out.gnp, gnb, &out.gn_ok, stream));
         return out;
     }
     T groupnorm(const T& x, const std::string& pre, int samples, float eps, bool silu, const T* x2 = nullptr) {

@@ -6,6 +6,7 @@ No CPU fallback: CPU tensors raise `Syn3rError`.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import torch
@@ -32,27 +33,20 @@ def _chk(*ts):
 
 
 def _gn_request(dev, M: int, N: int, want: bool):
-    """Ask the NEXT contraction of this thread for GroupNorm partial sums of its [M, N] output (include/syn3r_hip.h
-    syn3r_gemm_set_gn_partials): returns the buffer, or None when the shape has no whole 32-row blocks / 80-column groups."""
-    if not want:
-        return None
-    lib = L.load()
-    nb = lib.syn3r_gn_partials_bytes(int(M), int(N))
+    """The gn_partials / gn_partials_bytes / gn_written arguments of a contraction with an [M, N] output (include/syn3r_hip.h,
+    "GroupNorm statistics out of the PRODUCER's epilogue"): the buffer and (its pointer, bytes, written flag), or None and
+    (None, 0, None) = no request when the shape has no whole 32-row blocks / 80-column groups."""
+    nb = L.load().syn3r_gn_partials_bytes(int(M), int(N)) if want else 0
     if not nb:
-        return None
+        return None, (None, 0, None)
     part = torch.empty(nb // 4, dtype=torch.float32, device=dev)
-    L.check(lib.syn3r_gemm_set_gn_partials(part.data_ptr(), nb), "syn3r_gemm_set_gn_partials")
-    return part
+    return part, (part.data_ptr(), nb, ctypes.c_int(0))
 
 
-def _gn_collect(out: torch.Tensor, part) -> torch.Tensor:
+def _gn_collect(out: torch.Tensor, part, written) -> torch.Tensor:
     """Attach the partial sums to `out` (attribute `gn_part`) if the kernel that ran wrote them."""
-    if part is not None:
-        lib = L.load()
-        if lib.syn3r_gemm_gn_partials_written():
-            out.gn_part = part
-        else:
-            lib.syn3r_gemm_set_gn_partials(None, 0)        # (an entry that returned before consuming the request)
+    if part is not None and written.value:
+        out.gn_part = part
     return out
 
 
@@ -91,16 +85,16 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     if out is None:
         out = torch.empty((M, N), dtype=H, device=dev)
     lib = L.load()
-    part = _gn_request(dev, M, N, gn_stats and out.stride(0) == N)
+    part, gn = _gn_request(dev, M, N, gn_stats and out.stride(0) == N)
     rc = lib.syn3r_gemm_f16(x.data_ptr(), x.stride(0), L.ptr(weight), out.data_ptr(), out.stride(0), L.ptr(bias),
                             rv_ptr, rv_ld, int(rows_per_vec), int(rv_group_rows),
                             residual.data_ptr() if residual is not None else None,
                             residual.stride(0) if residual is not None else 0,
                             aux.data_ptr() if aux is not None else None, aux.stride(0) if aux is not None else 0,
-                            float(s_acc), float(s_res), float(s_aux), M, N, K, L.stream_ptr(dev))
+                            float(s_acc), float(s_res), float(s_aux), M, N, K, *gn, L.stream_ptr(dev))
     L.check(rc, "syn3r_gemm_f16")
     _count("gemm", 2.0 * M * N * K)
-    return _gn_collect(out, part)
+    return _gn_collect(out, part, gn[2])
 
 
 def pack_geglu(weight: torch.Tensor, bias: torch.Tensor):
@@ -257,14 +251,14 @@ def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] 
     Ho, Wo = (Hg + pad_lo - 2) // stride + 1, (Wg + pad_lo - 2) // stride + 1
     out = torch.empty((NB, Ho, Wo, Cout), dtype=H, device=dev)
     lib = L.load()
-    part = _gn_request(dev, NB * Ho * Wo, Cout, gn_stats)
+    part, gn = _gn_request(dev, NB * Ho * Wo, Cout, gn_stats)
     rc = lib.syn3r_conv2d3x3_f16(L.ptr(x), L.ptr(weight), L.ptr(out), Cout, L.ptr(bias), rv_ptr, rv_ld, int(rows_per_vec),
                                  L.ptr(residual), Cout if residual is not None else 0, float(s_acc), float(s_res),
-                                 NB, Hi, Wi, Cin, Cout, int(stride), 1 if upsample else 0, int(pad_lo),
+                                 NB, Hi, Wi, Cin, Cout, int(stride), 1 if upsample else 0, int(pad_lo), *gn,
                                  L.stream_ptr(dev))
     L.check(rc, "syn3r_conv2d3x3_f16")
     _count("gemm", 2.0 * NB * Ho * Wo * Cout * 9 * Cin)
-    return _gn_collect(out, part)
+    return _gn_collect(out, part, gn[2])
 
 
 def tconv3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], B: int, F: int, HW: int, *,
@@ -279,13 +273,13 @@ def tconv3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], 
         raise ValueError("tconv3: shape mismatch")
     out = torch.empty((M, Cout), dtype=H, device=dev)
     lib = L.load()
-    part = _gn_request(dev, M, Cout, gn_stats)
+    part, gn = _gn_request(dev, M, Cout, gn_stats)
     rc = lib.syn3r_tconv3_f16(L.ptr(x), L.ptr(weight), L.ptr(out), Cout, L.ptr(bias), rv_ptr, rv_ld, int(rows_per_vec), L.ptr(residual),
-                              Cout if residual is not None else 0, float(s_acc), float(s_res), B, F, HW, Cin, Cout,
+                              Cout if residual is not None else 0, float(s_acc), float(s_res), B, F, HW, Cin, Cout, *gn,
                               L.stream_ptr(dev))
     L.check(rc, "syn3r_tconv3_f16")
     _count("gemm", 2.0 * M * Cout * 3 * Cin)
-    return _gn_collect(out, part)
+    return _gn_collect(out, part, gn[2])
 
 
 def attention(qkv: torch.Tensor, nseq: int, S: int, heads: int) -> torch.Tensor:
@@ -374,7 +368,7 @@ def linear_cat(x1: torch.Tensor, x2: torch.Tensor, weight: torch.Tensor, bias: O
         return linear(torch.cat([x1, x2], dim=1), weight, bias)
     out = torch.empty((M, N), dtype=H, device=dev)
     rc = lib.syn3r_gemm_2src_f16(x1.data_ptr(), x1.stride(0), K1, x2.data_ptr(), x2.stride(0), K2, L.ptr(weight), out.data_ptr(),
-                                 out.stride(0), L.ptr(bias), M, N, L.stream_ptr(dev))
+                                 out.stride(0), L.ptr(bias), M, N, None, 0, None, L.stream_ptr(dev))
     L.check(rc, "syn3r_gemm_2src_f16")
     _count("gemm", 2.0 * M * N * (K1 + K2))
     return out

@@ -1,5 +1,5 @@
-"""GroupNorm statistics out of the producing contraction's epilogue (round 6; include/syn3r_hip.h
-syn3r_gemm_set_gn_partials / syn3r_groupnorm_pre_f16, csrc/gemm_wide.h gn_tile_stats, csrc/norm.hip k_gn_finalize_parts).
+"""GroupNorm statistics out of the producing contraction's epilogue (round 6; include/syn3r_hip.h: the gn_partials /
+gn_partials_bytes / gn_written arguments of the contractions, syn3r_groupnorm_pre_f16, csrc/gemm_wide.h gn_tile_stats, csrc/norm.hip k_gn_finalize_parts).
 
 Reference semantics: GroupNorm(32) of resnet.py:272,286,574,588 and transformer_temporal.py:235 on the output of the
 contraction in front of it.  Checked here: the partial sums the kernels leave behind equal the sums over the fp16 output
@@ -7,6 +7,8 @@ as stored (per 32-row block and 10-column unit), on every kernel family with the
 (plain, row vector, residual, residual + aux); GroupNorm from the partial sums equals torch's fp32 group_norm of that
 output within the bar of the statistics-pass form; two-source groups that straddle the sources; bitwise repeatability;
 shapes / kernels that cannot serve the request fall back silently to the statistics pass."""
+import ctypes
+
 import pytest
 import torch
 import torch.nn.functional as Fn
@@ -50,6 +52,20 @@ def gn_ref(x2d: torch.Tensor, samples: int, ga, be, eps, silu):
     if silu:
         ref = Fn.silu(ref)
     return ref.permute(0, 2, 1).reshape(M, C)
+
+
+def with_request(fn, head, part_ptr, nbytes):
+    """One of the four contraction entries straight through ctypes: `head` (its arguments in front of the GroupNorm request), then
+    the request, gn_written preset to a sentinel, the null stream.  Returns (status, gn_written)."""
+    written = ctypes.c_int(7)
+    rc = fn(*head, part_ptr, nbytes, ctypes.byref(written), None)
+    return rc, written.value
+
+
+def gemm_head(x, w, out):
+    """syn3r_gemm_f16's arguments for out = x @ w^T, no bias, no epilogue operands."""
+    (M, K), N = x.shape, w.shape[0]
+    return (x.data_ptr(), K, w.data_ptr(), out.data_ptr(), N, None, None, 0, 0, 0, None, 0, None, 0, 1.0, 1.0, 1.0, M, N, K)
 
 
 @pytest.mark.parametrize("tile", [0, -320, -322, -256])
@@ -199,24 +215,40 @@ def test_requests_that_cannot_be_served_fall_back(gpu):
     finally:
         lib.syn3r_gemm_set_tile(0)
     assert getattr(y, "gn_part", None) is None
-    assert lib.syn3r_gemm_gn_partials_written() == 0
-    # the request did not leak into the next launch
     z = ops.linear(x, w)
-    assert lib.syn3r_gemm_gn_partials_written() == 0 and getattr(z, "gn_part", None) is None
-    # a request followed by an entry point that never writes partial sums (the gated projection): dropped there, not kept for the
-    # next contraction of the thread
-    part = torch.zeros(lib.syn3r_gn_partials_bytes(1024, 320) // 4, dtype=torch.float32, device=gpu)
-    _lib.check(lib.syn3r_gemm_set_gn_partials(part.data_ptr(), part.numel() * 4), "set_gn_partials")
-    wg, bg = rnd(g, 2 * 160, 64, scale=0.125, dev=gpu), rnd(g, 2 * 160, dev=gpu)
-    wp, bp, _ = ops.pack_geglu(wg, bg)
-    ops.linear_geglu(x, wp, bp, 160)
+    assert getattr(z, "gn_part", None) is None
+    # the same through the C-ABI: a kernel that does not write the partial sums says so and leaves the buffer alone ...
+    nb = lib.syn3r_gn_partials_bytes(1024, 320)
+    part = torch.zeros(nb // 4, dtype=torch.float32, device=gpu)
+    out = torch.empty(1024, 320, dtype=H, device=gpu)
+    x16, out16 = rnd(g, 16, 64, dev=gpu), torch.empty(16, 320, dtype=H, device=gpu)
+    try:
+        _lib.check(lib.syn3r_gemm_set_tile(-128), "set_tile")
+        assert with_request(lib.syn3r_gemm_f16, gemm_head(x, w, out), part.data_ptr(), nb) == (0, 0)         # the 128-row blocks
+    finally:
+        lib.syn3r_gemm_set_tile(0)
+    assert with_request(lib.syn3r_gemm_f16, gemm_head(x16, w, out16), part.data_ptr(), nb) == (0, 0)         # M <= 16: the skinny kernel
+    torch.cuda.synchronize()
+    assert float(part.abs().sum()) == 0.0
+    assert torch.equal(out, y), "asking for the partial sums changed the output"
+    # ... one that writes them says that
     try:
         _lib.check(lib.syn3r_gemm_set_tile(-256), "set_tile")
+        assert with_request(lib.syn3r_gemm_f16, gemm_head(x, w, out), part.data_ptr(), nb) == (0, 1)
+        torch.cuda.synchronize()
+        out.gn_part = part
+        check_partials(out, 320)
+        # and nothing of the request outlives its call: the launches that follow without one (the gated projection, the same
+        # contraction on the same kernel) leave the zeroed buffer untouched
+        part.zero_()
+        wg, bg = rnd(g, 2 * 160, 64, scale=0.125, dev=gpu), rnd(g, 2 * 160, dev=gpu)
+        wp, bp, _ = ops.pack_geglu(wg, bg)
+        ops.linear_geglu(x, wp, bp, 160)
         ops.linear(x, w)
     finally:
         lib.syn3r_gemm_set_tile(0)
     torch.cuda.synchronize()
-    assert lib.syn3r_gemm_gn_partials_written() == 0 and float(part.abs().sum()) == 0.0
+    assert float(part.abs().sum()) == 0.0
     ga, be = rnd(g, 320, dev=gpu), rnd(g, 320, dev=gpu)
     close(ops.groupnorm(y, ga, be, 4, 1e-5, False), gn_ref(y, 4, ga, be, 1e-5, False))
     # rows per sample not a multiple of 32 with partial sums present: the statistics pass
@@ -227,6 +259,31 @@ def test_requests_that_cannot_be_served_fall_back(gpu):
         lib.syn3r_gemm_set_tile(0)
     assert getattr(y, "gn_part", None) is not None
     close(ops.groupnorm(y, ga, be, 64, 1e-5, False), gn_ref(y, 64, ga, be, 1e-5, False))
+
+
+def test_two_source_partials(gpu):
+    """syn3r_gemm_2src_f16 with a request, on k_gemm_widep."""
+    from syn3r_amd import _lib
+    from syn3r_amd.unet import ops
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(21)
+    M, N, K1, K2 = 4096, 640, 64, 64
+    x1, x2 = rnd(g, M, K1, dev=gpu), rnd(g, M, K2, dev=gpu)
+    w, b = rnd(g, N, K1 + K2, scale=(K1 + K2) ** -0.5, dev=gpu), rnd(g, N, dev=gpu)
+    out = torch.empty(M, N, dtype=H, device=gpu)
+    nb = lib.syn3r_gn_partials_bytes(M, N)
+    part = torch.zeros(nb // 4, dtype=torch.float32, device=gpu)
+    head = (x1.data_ptr(), K1, K1, x2.data_ptr(), K2, K2, w.data_ptr(), out.data_ptr(), N, b.data_ptr(), M, N)
+    try:
+        _lib.check(lib.syn3r_gemm_set_tile(-320), "set_tile")
+        assert with_request(lib.syn3r_gemm_2src_f16, head, part.data_ptr(), nb) == (0, 1)
+        plain = ops.linear_cat(x1, x2, w, b)
+    finally:
+        lib.syn3r_gemm_set_tile(0)
+    torch.cuda.synchronize()
+    assert torch.equal(out, plain), "asking for the partial sums changed the output"
+    out.gn_part = part
+    check_partials(out, N)
 
 
 def test_groupnorm_pre_rejects_bad_input(gpu):
@@ -240,6 +297,11 @@ def test_groupnorm_pre_rejects_bad_input(gpu):
                                       ws.data_ptr(), ws.numel(), None)
     assert lib.syn3r_groupnorm_pre_f16(*args(32, 2, None)) != 0 and b"partial sums" in lib.syn3r_last_error()
     assert lib.syn3r_groupnorm_pre_f16(*args(16, 4, part.data_ptr())) != 0 and b"rows" in lib.syn3r_last_error()
-    assert lib.syn3r_gemm_set_gn_partials(part.data_ptr(), 0) != 0
+    # a request with a pointer and no size, or a pointer that is not 16-byte aligned: refused, and gn_written says nothing was written
+    a, o = torch.zeros(64, 64, dtype=H, device=gpu), torch.zeros(64, 64, dtype=H, device=gpu)
+    rc, written = with_request(lib.syn3r_gemm_f16, gemm_head(a, a, o), part.data_ptr(), 0)
+    assert rc != 0 and written == 0 and b"gn_partials" in lib.syn3r_last_error()
+    rc, written = with_request(lib.syn3r_gemm_f16, gemm_head(a, a, o), part.data_ptr() + 4, part.numel() * 4 - 4)
+    assert rc != 0 and written == 0 and b"16-byte aligned" in lib.syn3r_last_error()
     assert lib.syn3r_gn_partials_bytes(1000, 320) == 0 and lib.syn3r_gn_partials_bytes(1024, 320) == 32 * 2 * 32 * 4
     torch.cuda.synchronize()
