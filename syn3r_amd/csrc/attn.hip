@@ -143,7 +143,7 @@ __global__ void __launch_bounds__(ATHREADS, ATTN_WAVES) k_attn_spatial(AttnParam
     const int l16 = lane & 15, g4 = lane >> 4;
     const int qblocks = (p.S + BQ - 1) / BQ;
     // all query blocks of one (sequence, head) share its K/V (2.4 MB at S = 9216): keep them on one XCD's L2
-    int bid = (int)xcd_chunk_remap(blockIdx.x, gridDim.x);
+    int bid = (int)xcd_remap(blockIdx.x, gridDim.x);
     const int qb = bid % qblocks; bid /= qblocks;
     const int hd = bid % p.heads;
     const int seq = bid / p.heads;

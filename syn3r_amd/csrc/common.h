@@ -99,7 +99,7 @@ constexpr int tune_env(const char*, int dflt) { return dflt; }
 
 // Workgroups are dealt to the 8 XCDs round-robin by blockIdx; this bijection hands every XCD one CONTIGUOUS
 // chunk of logical ids, so neighbouring tiles (which share operands) meet in the same 4 MB L2.
-__device__ __forceinline__ unsigned xcd_chunk_remap(unsigned bid, unsigned nblk) {
+__device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nblk) {
     unsigned q = nblk / 8, r = nblk % 8, xcd = bid % 8, k = bid / 8;
     unsigned start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return start + k;

@@ -25,7 +25,7 @@
 //   k_gemm_dmapd   persistent 256 x 160 tile with a deferred, LDS-free epilogue (gemm_dmapd.h): residual projections, 640 <= K <= 1280
 //   k_gemm_skinny  M <= 16 rows (time embedding, folded cross-attention context)
 // This file is the dispatch: the shape rules (launch_dma), the launchers and the C-ABI entry points; the kernel families live in
-// gemm_common.h / gemm_dma.h / gemm_wide.h / gemm_z.h / gemm_dmap.h / gemm_dmapd.h / gemm_g256.h / gemm_ffn.h, included below into
+// gemm_common.h / gemm_dma160.h / gemm_dma.h / gemm_wide.h / gemm_z.h / gemm_dmap.h / gemm_dmapd.h / gemm_g256.h / gemm_ffn.h, included below into
 // ONE translation unit.
 #include "common.h"
 #include <cstdlib>
@@ -38,6 +38,7 @@ using namespace syn3r;
 namespace {
 
 #include "gemm_common.h"
+#include "gemm_dma160.h"
 #include "gemm_dma.h"
 #include "gemm_wide.h"
 #include "gemm_z.h"
@@ -185,10 +186,11 @@ bool widep_admits(const GemmParams& p) {
     return lean && small && p.M % 8 == 0 && p.N % 8 == 0 && p.M >= 8 && p.N >= 8;
 }
 
+// tiles of the 256 x 160 kernels (their ring is DMA256_LDS bytes, gemm_dma160.h)
+long long tiles256(const GemmParams& p) { return (long long)((p.M + 255) / 256) * ((p.N + BN - 1) / BN); }
+
 int launch_dmapd(const GemmParams& p, hipStream_t stream) {
-    constexpr size_t lds = (size_t)3 * (256 * BK * 2 + DMA_B_BYTES);   // 159,744 B
-    const int tiles = ((p.M + 255) / 256) * ((p.N + BN - 1) / BN);
-    return launch_tiles<k_gemm_dmapd>("gemm_dmapd", lds, std::min(tiles, persistent_blocks()), 512, stream, p, nullptr, "k_gemm_dmapd");
+    return launch_tiles<k_gemm_dmapd>("gemm_dmapd", DMA256_LDS, std::min<long long>(tiles256(p), persistent_blocks()), 512, stream, p, nullptr, "k_gemm_dmapd");
 }
 
 // Does the deferred-epilogue kernel take this contraction?  Dense, row-major output, WHOLE 256 x 160 tiles (no row / column clamps in
@@ -202,16 +204,14 @@ bool dmapd_admits(const GemmParams& p) {
 
 template <int MODE>
 int launch_dmap(const GemmParams& p, hipStream_t stream, int* gn_written) {
-    constexpr size_t lds = (size_t)3 * (256 * BK * 2 + DMA_B_BYTES);   // 159,744 B
-    static_assert(8 * 32 * EPI_LD * sizeof(__half) <= 256 * BK * 2 + DMA_B_BYTES, "the two-pass epilogue staging must fit in one ring slot");
-    const int tiles = ((p.M + 255) / 256) * ((p.N + BN - 1) / BN);
+    static_assert(8 * 32 * EPI_LD * sizeof(__half) <= DMA256_STAGE, "the two-pass epilogue staging must fit in one ring slot");
     GemmParams q = p;
     q.tc_pb = q.tc_nf = 0;
     if constexpr (MODE == MODE_TCONV) {
         static const int tc_env = tune_env("SYN3R_TCONV_ORDER", 1);       // 0: rows in memory order (tuning builds)
         if (tc_env != 0 && p.HW % 256 == 0 && p.M % p.HW == 0 && p.M / p.HW > 1) { q.tc_pb = p.HW / 256; q.tc_nf = p.M / p.HW; }
     }
-    return launch_tiles<k_gemm_dmap<MODE>>("gemm_dmap", lds, std::min(tiles, persistent_blocks()), 512, stream, q, gn_written, "k_gemm_dmap<%d>", MODE);
+    return launch_tiles<k_gemm_dmap<MODE>>("gemm_dmap", DMA256_LDS, std::min<long long>(tiles256(p), persistent_blocks()), 512, stream, q, gn_written, "k_gemm_dmap<%d>", MODE);
 }
 
 template <int MODE, int BM>
@@ -225,7 +225,7 @@ int launch_dma_bm(const GemmParams& p, hipStream_t stream, int* gn_written) {
         if (pers_env != 0 && MODE != MODE_CONV2D && p.geglu_D <= 0 && (!p.aux || p.residual) && p.N % 8 == 0 && p.N >= 8)
             return launch_dmap<MODE>(p, stream, gn_written);
     }
-    constexpr size_t lds = (size_t)(BM == 256 ? 3 : 2) * (BM * BK * 2 + DMA_B_BYTES);   // 159,744 B / 73,728 B
+    constexpr size_t lds = BM == 256 ? DMA256_LDS : 2 * (BM * BK * 2 + DMA_B_BYTES);      // 159,744 B / 73,728 B
     static_assert((BM / 32) * WM * EPI_LD * sizeof(__half) <= lds, "epilogue staging must fit in the ring");
     const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
     return launch_tiles<k_gemm_dma<MODE, BM>>("gemm_dma", lds, tiles, BM * 2, stream, p, nullptr, "k_gemm_dma<%d,%d>", MODE, BM);
@@ -238,17 +238,16 @@ int launch_dma_bm(const GemmParams& p, hipStream_t stream, int* gn_written) {
 // caller launches one pass.  Two-source A: only when no part straddles the boundary between the sources.
 template <int MODE>
 int launch_splitk(const GemmParams& p, hipStream_t stream, bool* done) {
-    const long long tiles256 = (long long)((p.M + 255) / 256) * ((p.N + BN - 1) / BN);
+    const long long tiles = tiles256(p);
     const int nkt_all = p.K / BK;
-    const int S = (tiles256 * 4 <= 256 && nkt_all % 4 == 0 && nkt_all >= 16) ? 4 : ((tiles256 * 2 <= 256 && nkt_all % 2 == 0 && nkt_all >= 8) ? 2 : 1);
+    const int S = (tiles * 4 <= 256 && nkt_all % 4 == 0 && nkt_all >= 16) ? 4 : ((tiles * 2 <= 256 && nkt_all % 2 == 0 && nkt_all >= 8) ? 2 : 1);
     const size_t need = (size_t)S * p.M * p.N * sizeof(float);
     if (S == 1 || g_dma_bm != 0 || !g_splitk_ws || need > g_splitk_bytes || p.N % 8 != 0 || p.M < 8 || p.relu || p.relu_mask ||
         p.geglu_D > 0 || p.out_tiled || (p.A2 && (MODE != MODE_DENSE || p.a_tiled || (p.K1 / BK) % (nkt_all / S) != 0)))
         return SYN3R_OK;
-    constexpr size_t lds = (size_t)3 * (256 * BK * 2 + DMA_B_BYTES);
     GemmParams q = p;
     q.ksplit = S; q.split_ws = (float*)g_splitk_ws;
-    if (int rc = launch_tiles<k_gemm_dma<MODE, 256>>("gemm split-K", lds, tiles256 * S, 512, stream, q, nullptr,
+    if (int rc = launch_tiles<k_gemm_dma<MODE, 256>>("gemm split-K", DMA256_LDS, tiles * S, 512, stream, q, nullptr,
                                                      trace_detail() ? "k_gemm_dma<%d,256>/%d" : "k_gemm_dma<%d,256>/k", MODE, S))
         return rc;
     const long long chunks = (long long)p.M * (p.N / 8);
@@ -271,8 +270,7 @@ int launch_dma(const GemmParams& p, hipStream_t stream, int* gn_written = nullpt
         const bool won = p.residual ? (p.K >= 640 && p.K <= 1280 && p.N <= 1280) : (p.K == 1280 && p.N == 1280);
         // (a launch asked for GroupNorm partial sums - proj_out, 5 of these 15 launches per level - keeps the lean epilogue, which
         // writes them: the statistics pass it saves costs more than the deferred epilogue gains)
-        if (ddw_env != 0 && g_dma_bm == 0 && !p.gn_part && (ddw_env == 2 ? p.K <= 1280 : won) && dmapd_admits(p) &&
-            (long long)((p.M + 255) / 256) * ((p.N + BN - 1) / BN) >= 256)
+        if (ddw_env != 0 && g_dma_bm == 0 && !p.gn_part && (ddw_env == 2 ? p.K <= 1280 : won) && dmapd_admits(p) && tiles256(p) >= 256)
             return launch_dmapd(p, stream);
     }
     const bool wide_ok = MODE == MODE_DENSE && widep_admits(p);
@@ -319,11 +317,10 @@ int launch_dma(const GemmParams& p, hipStream_t stream, int* gn_written = nullpt
     // SYN3R_SET_TILE=-256, round 2): every implicit-GEMM convolution and temporal convolution -1..-10 % (-3.7 % on their
     // sum), the residual-add projections -5..-6 %; only grids that leave CUs without a 256-row block (dense, M = 4032)
     // stay with the 128-row blocks.  (Before the stagger the 128-row pairs won everywhere but N >= 5120.)
-    const long long tiles256 = (long long)((p.M + 255) / 256) * ((p.N + BN - 1) / BN);
     bool split = false;
     int rc = launch_splitk<MODE>(p, stream, &split);
     if (split || rc) return rc;
-    int bm = g_dma_bm > 0 ? g_dma_bm : ((MODE != MODE_DENSE || tiles256 >= 256) ? 256 : 128);
+    int bm = g_dma_bm > 0 ? g_dma_bm : ((MODE != MODE_DENSE || tiles256(p) >= 256) ? 256 : 128);
     return bm == 128 ? launch_dma_bm<MODE, 128>(p, stream, gn_written) : launch_dma_bm<MODE, 256>(p, stream, gn_written);
 }
 

@@ -88,10 +88,16 @@ __device__ __forceinline__ long long tiled_off(int m, int d, int D) {
     return ((long long)(m >> 7) * (D >> 6) + (d >> 6)) * 8192 + (m & 127) * 64 + (d & 63);
 }
 
-__device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nblk) {
-    unsigned q = nblk / 8, r = nblk % 8, xcd = bid % 8, k = bid / 8;
-    unsigned start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return start + k;
+// The tile list of a block of a persistent kernel: its XCD's contiguous chunk [start, start + len) of the nblk tiles (xcd_remap's
+// chunks, common.h), shared with the other blocks of that XCD - block b walks positions b / 8, b / 8 + stride, ... of it.
+struct XcdTiles { unsigned start, len, stride; };
+__device__ __forceinline__ XcdTiles xcd_tiles(unsigned nblk) {
+    const unsigned xcd = blockIdx.x % 8, q8 = nblk / 8, r8 = nblk % 8;
+    XcdTiles t;
+    t.start = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
+    t.len = q8 + (xcd < r8 ? 1u : 0u);
+    t.stride = (gridDim.x - xcd + 7) / 8;
+    return t;
 }
 
 __device__ __forceinline__ int swz(int row, int chunk) { return row * BK + ((chunk ^ (row & 7)) << 3); }

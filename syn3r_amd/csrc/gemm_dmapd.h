@@ -1,7 +1,7 @@
 // k_gemm_dmapd: the persistent 256 x 160 dense kernel with a deferred, LDS-free epilogue (built in round 5, dispatched in round 6
 // for the shapes it won on: profiles/r05/dmapd_deferred_epilogue.txt).
 // Included by gemm.hip inside its anonymous namespace (one translation unit; the kernels share GemmParams, the epilogues and the
-// LDS-DMA typedefs of gemm_common.h / gemm_dma.h).
+// LDS-DMA pieces of gemm_common.h / gemm_dma160.h).
 
 // ---------------------------------------------------------------------------------------------
 // k_gemm_dmapd (round 5): the persistent 256 x 160 dense kernel with a DEFERRED, LDS-free epilogue.  The K <= 1280 projections
@@ -20,9 +20,7 @@
 struct DmapdParked { int gm0, gn0, valid; };
 
 __global__ void __launch_bounds__(512, 2) k_gemm_dmapd(GemmParams p) {
-    constexpr int BM = 256;
-    constexpr int DMA_A_BYTES = BM * BK * 2;                  // 32,768
-    constexpr int STAGE = DMA_A_BYTES + DMA_B_BYTES;          // 53,248
+    constexpr int BM = 256, DMA_A_BYTES = DMA256_A_BYTES, STAGE = DMA256_STAGE;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     typedef _Float16 half4e __attribute__((ext_vector_type(4)));
     const int tid = threadIdx.x, lane = tid & 63;
@@ -30,11 +28,7 @@ __global__ void __launch_bounds__(512, 2) k_gemm_dmapd(GemmParams p) {
     const int wm = wv >> 1, wn = wv & 1;
     const int tiles_n = (p.N + BN - 1) / BN;
     const int tiles_m = (p.M + BM - 1) / BM;
-    const unsigned nblk = (unsigned)(tiles_m * tiles_n);
-    const unsigned xcd = blockIdx.x % 8, q8 = nblk / 8, r8 = nblk % 8;
-    const unsigned t_start = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-    const unsigned t_len = q8 + (xcd < r8 ? 1u : 0u);
-    const unsigned t_stride = (gridDim.x - xcd + 7) / 8;
+    const XcdTiles tiles = xcd_tiles((unsigned)(tiles_m * tiles_n));
     const int nkt = p.K / BK;
 
     // ---- issue cursor (as k_gemm_dmap, dense mode).  Whole tiles only (M % 256 == 0, N % 160 == 0: dmapd_admits), so the four A
@@ -58,8 +52,8 @@ __global__ void __launch_bounds__(512, 2) k_gemm_dmapd(GemmParams p) {
         b_cur = p.W + (long long)(n0 + b_first * 8 + prow) * p.K + csrc * 8;
     };
     auto issue_next = [&]() -> bool {
-        if (itl >= t_len) return false;
-        if (ikt == 0) setup_issue_tile(t_start + itl);
+        if (itl >= tiles.len) return false;
+        if (ikt == 0) setup_issue_tile(tiles.start + itl);
         char* st = smem_raw + islot * STAGE;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -69,16 +63,14 @@ __global__ void __launch_bounds__(512, 2) k_gemm_dmapd(GemmParams p) {
         for (int j = 0; j < 3; ++j)
             if (j < nb) __builtin_amdgcn_global_load_lds((gbl_void_t*)(b_cur + j * b_piece), (lds_void_t*)(st + DMA_A_BYTES + (b_first + j) * 1024), 16, 0, 0);
         b_cur += BK;
-        if (++ikt == nkt) { ikt = 0; itl += t_stride; }
+        if (++ikt == nkt) { ikt = 0; itl += tiles.stride; }
         if (++islot == 3) islot = 0;
         return true;
     };
 
     const int fr = lane & 15, fq = lane >> 4;
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem_raw;
-    const unsigned a_row = (unsigned)((wm * WM + fr) * 128);
-    const unsigned b_row = (unsigned)(DMA_A_BYTES + (wn * WN + fr) * 128);
-    const unsigned sw0 = (unsigned)(((0 + fq) ^ (fr & 7)) << 4), sw1 = (unsigned)(((4 + fq) ^ (fr & 7)) << 4);
+    const unsigned lds0 = lds_addr(smem_raw);
+    const Frag160 frag(lane, wm, wn, DMA_A_BYTES);
     const bool defer = wv >= 4;           // stagger of the SIMD partners (see k_gemm_widep)
 
     // ---- the parked tile and its four units (one per 16-row tile: two 16-byte pieces + one 8-byte piece per lane)
@@ -87,11 +79,12 @@ __global__ void __launch_bounds__(512, 2) k_gemm_dmapd(GemmParams p) {
     // column (inside the wavefront's 80) of this lane's piece: pairs give 8 halfs from column 32 c + (fq even ? 4 fq : 16 + 4 (fq - 1)),
     // the fifth column tile 4 halfs from column 64 + 4 fq
     const int pair_col = (fq & 1) ? 16 + 4 * (fq - 1) : 4 * fq;
+    constexpr int UNIT_STORES = 3;        // store instructions of a unit: one per piece
     half8 lres[2];                        // residual pieces of the unit of the current k-tile: two 16-byte ...
     half4e lres4;                         // ... and one 8-byte piece per lane (aux blends keep the one-pass kernel: registers)
     // The loads are inline asm: hipcc cannot count the LDS-DMA instructions issued behind them (they sit under wave-uniform
     // branches), so a visible load would be waited for with vmcnt(0) - which drains the DMA stream every k-tile.  Issued BEFORE the
-    // k-tile's DMA, the 6-7 DMA instructions are all that is younger: the counted wait in front of their use is vmcnt(6).
+    // k-tile's DMA, the 6-7 DMA instructions are all that is younger: the counted wait in front of their use is vmcnt(DMA_PIECES_MIN).
     auto unit_load = [&](int i) __attribute__((always_inline)) {
         const int m = park.gm0 + i * 16 + fr;
 #pragma unroll
@@ -108,7 +101,7 @@ __global__ void __launch_bounds__(512, 2) k_gemm_dmapd(GemmParams p) {
     // three up (30 v_mov per unit) - one copy of this code with static register indices instead of a four-way switch.
     auto unit_store_rt = [&](int i) __attribute__((always_inline)) {
         if (p.residual)                   // the unit's loads have landed (younger: this k-tile's DMA only)
-            asm volatile("s_waitcnt vmcnt(6)" : "+v"(lres[0]), "+v"(lres[1]), "+v"(lres4) :: "memory");
+            asm volatile("s_waitcnt vmcnt(%[dma])" : "+v"(lres[0]), "+v"(lres[1]), "+v"(lres4) : [dma] "i"(DMA_PIECES_MIN) : "memory");
         const int m = park.gm0 + i * 16 + fr;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -150,8 +143,8 @@ __global__ void __launch_bounds__(512, 2) k_gemm_dmapd(GemmParams p) {
     int cslot = 0;
     bool first_tile = true;
     int prev_stores = 0;                  // stores this wavefront issued in the previous k-tile iteration (wave-uniform)
-    for (unsigned tl = blockIdx.x / 8; tl < t_len; tl += t_stride) {
-        const unsigned tile = t_start + tl;
+    for (unsigned tl = blockIdx.x / 8; tl < tiles.len; tl += tiles.stride) {
+        const unsigned tile = tiles.start + tl;
         const int m0 = (int)(tile / (unsigned)tiles_n) * BM, n0 = (int)(tile % (unsigned)tiles_n) * BN;
         float4v acc[TM][TN];
 #pragma unroll
@@ -163,13 +156,6 @@ __global__ void __launch_bounds__(512, 2) k_gemm_dmapd(GemmParams p) {
         for (int i = 0; i < TM; ++i) { asm volatile("" : "=v"(a0[i])); asm volatile("" : "=v"(a1[i])); }
 #pragma unroll
         for (int j = 0; j < TN; ++j) { asm volatile("" : "=v"(b0[j])); asm volatile("" : "=v"(b1[j])); }
-        auto mma1 = [&]() {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b1[j], a1[i], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        };
         for (int kt = 0; kt < nkt; ++kt) {
             // the unit of the parked tile that belongs to this k-tile: unit u runs in k-tile (u nkt) / 4 (nkt >= 4: at most one per k-tile)
             int unit = -1;
@@ -177,36 +163,15 @@ __global__ void __launch_bounds__(512, 2) k_gemm_dmapd(GemmParams p) {
 #pragma unroll
                 for (int u = 0; u < TM; ++u) if ((u * nkt) / TM == kt) unit = u;
             }
-            if ((kt == 0 && !first_tile) || issued - consumed < 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (prev_stores) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");     // the previous k-tile's three stores may stay in flight
-            else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            if ((kt == 0 && !first_tile) || issued - consumed < 2) WAIT_VMCNT(0);
+            else if (prev_stores) WAIT_VMCNT(DMA_PIECES_MIN + UNIT_STORES);        // the previous k-tile's three stores may stay in flight
+            else WAIT_VMCNT(DMA_PIECES_MIN);
             __builtin_amdgcn_s_barrier();
-            if (defer && kt > 0) mma1();
+            if (defer && kt > 0) mma160(acc, a1, b1);
             if (unit >= 0) unit_load(unit);                                // (before the DMA in program order: see the vmcnt note)
             if (issue_next()) ++issued;
-            const unsigned sb = lds0 + (unsigned)cslot * STAGE;
-            {
-                const unsigned aa = sb + a_row + sw0, ba = sb + b_row + sw0;
-                DS_READ128(a0[0], aa, 0); DS_READ128(a0[1], aa, 2048); DS_READ128(a0[2], aa, 4096); DS_READ128(a0[3], aa, 6144);
-                DS_READ128(b0[0], ba, 0); DS_READ128(b0[1], ba, 2048); DS_READ128(b0[2], ba, 4096); DS_READ128(b0[3], ba, 6144);
-                DS_READ128(b0[4], ba, 8192);
-            }
-            {
-                const unsigned aa = sb + a_row + sw1, ba = sb + b_row + sw1;
-                DS_READ128(a1[0], aa, 0); DS_READ128(a1[1], aa, 2048); DS_READ128(a1[2], aa, 4096); DS_READ128(a1[3], aa, 6144);
-                DS_READ128(b1[0], ba, 0); DS_READ128(b1[1], ba, 2048); DS_READ128(b1[2], ba, 4096); DS_READ128(b1[3], ba, 6144);
-                DS_READ128(b1[4], ba, 8192);
-            }
-            asm volatile("s_waitcnt lgkmcnt(9)"
-                         : "+v"(a0[0]), "+v"(a0[1]), "+v"(a0[2]), "+v"(a0[3]), "+v"(b0[0]), "+v"(b0[1]), "+v"(b0[2]), "+v"(b0[3]), "+v"(b0[4]));
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b0[j], a0[i], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(0)"
-                         : "+v"(a1[0]), "+v"(a1[1]), "+v"(a1[2]), "+v"(a1[3]), "+v"(b1[0]), "+v"(b1[1]), "+v"(b1[2]), "+v"(b1[3]), "+v"(b1[4]));
-            if (!defer) mma1();
+            ktile160(lds0 + (unsigned)cslot * STAGE, frag, acc, a0, b0, a1, b1);
+            if (!defer) mma160(acc, a1, b1);
             prev_stores = 0;
             if (unit >= 0) {                                               // behind this k-tile's MFMAs
                 unit_store_rt(unit);
@@ -216,7 +181,7 @@ __global__ void __launch_bounds__(512, 2) k_gemm_dmapd(GemmParams p) {
             ++consumed;
             if (++cslot == 3) cslot = 0;
         }
-        if (defer) mma1();
+        if (defer) mma160(acc, a1, b1);
         first_tile = false;
         // ---- park this tile: fp16((acc + bias + row vector) * s_acc), the one-pass epilogue's first rounding.  Every bias / row-vector
         // piece is requested before the first one is used (one exposed latency per tile, not twenty-five)
@@ -253,11 +218,11 @@ __global__ void __launch_bounds__(512, 2) k_gemm_dmapd(GemmParams p) {
     }
     // ---- the last tile's epilogue: its four units
     if (park.valid) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        WAIT_VMCNT(0);
 #pragma unroll
         for (int u = 0; u < TM; ++u) {
             unit_load(u);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (nothing younger than the loads here: the counted wait inside would not cover them)
+            WAIT_VMCNT(0);                                        // (nothing younger than the loads here: the counted wait inside would not cover them)
             unit_store_rt(u);
         }
     }

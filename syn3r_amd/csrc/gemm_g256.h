@@ -41,6 +41,7 @@ __global__ void __launch_bounds__(512, 2) k_gemm_g256(GemmParams p) {
     const int wm = wv >> 1, wn = wv & 1;
     const int tiles_n = p.N / 256, tiles_m = (p.M + 255) / 256;  // (launch_g256: M a multiple of 128 - the last row tile may be a half: its rows 128-255 re-read valid rows and are never stored)
     const unsigned nblk = (unsigned)(tiles_m * tiles_n);
+    // (xcd_tiles(nblk) of gemm_common.h, written out: through the helper hipcc reorders this kernel's instructions)
     const unsigned xcd = blockIdx.x % 8, q8 = nblk / 8, r8 = nblk % 8;
     const unsigned t_start = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
     const unsigned t_len = q8 + (xcd < r8 ? 1u : 0u);

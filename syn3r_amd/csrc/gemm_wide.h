@@ -246,10 +246,7 @@ __global__ void __launch_bounds__(512, 2) k_gemm_widep(GemmParams p) {
     const int tiles_n = (p.N + WBN - 1) / WBN;
     const int tiles_m = (p.M + WBM - 1) / WBM;
     const unsigned nblk = (unsigned)(tiles_m * tiles_n);
-    const unsigned xcd = blockIdx.x % 8, q8 = nblk / 8, r8 = nblk % 8;
-    const unsigned t_start = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-    const unsigned t_len = q8 + (xcd < r8 ? 1u : 0u);
-    const unsigned t_stride = (gridDim.x - xcd + 7) / 8;
+    const XcdTiles tiles = xcd_tiles(nblk);
 
     // wave-uniform BYTE offsets (from p.A / p.W; launch_widep checks that both operands span < 4 GB) of the 4 A and
     // 5 B pieces this wavefront stages: 9 scalar registers, advanced on the scalar ALU
@@ -332,7 +329,7 @@ __global__ void __launch_bounds__(512, 2) k_gemm_widep(GemmParams p) {
 #define PSTAMP(i)
 #endif
     bool staged = false;                  // stage 0 of the tile about to start is already in flight
-    for (unsigned tl = blockIdx.x / 8; tl < t_len; tl += t_stride) {
+    for (unsigned tl = blockIdx.x / 8; tl < tiles.len; tl += tiles.stride) {
         {   // everything derived from the lane id is rebuilt per tile behind an opaque copy: hoisted out of the tile
             // loop it would be carried through the epilogue in registers the 160 accumulators do not leave
             int lo = lane;
@@ -347,7 +344,7 @@ __global__ void __launch_bounds__(512, 2) k_gemm_widep(GemmParams p) {
             swz[0] = (unsigned)(((0 + fq) ^ (fr & 7)) << 4);
             swz[1] = (unsigned)(((4 + fq) ^ (fr & 7)) << 4);
         }
-        setup_tile(t_start + tl);
+        setup_tile(tiles.start + tl);
         if (staged) {
             issue_stage(0, std::false_type{});      // stage 0 was requested during the previous tile's last k-tile
         } else {
@@ -399,8 +396,8 @@ __global__ void __launch_bounds__(512, 2) k_gemm_widep(GemmParams p) {
             __builtin_amdgcn_s_barrier();
             if (defer && kt > 0) mma();                          // second k-half of stage kt-1 (deferred wavefronts)
             if (kt + 1 < nkt) issue_stage(buf ^ 1, std::true_type{});   // the slot every wavefront finished reading in iteration kt-1
-            else if (xpf && tl + t_stride < t_len) {
-                setup_tile(t_start + tl + t_stride);             // (rebuilt at the top of the next tile: nothing stays live)
+            else if (xpf && tl + tiles.stride < tiles.len) {
+                setup_tile(tiles.start + tl + tiles.stride);     // (rebuilt at the top of the next tile: nothing stays live)
                 issue_stage(0, std::true_type{});
                 staged = true;
             }

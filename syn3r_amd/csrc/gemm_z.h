@@ -82,10 +82,7 @@ __global__ void __launch_bounds__(512, 2) k_gemm_z(GemmParams p) {
     const int tiles_n = (p.N + WBN - 1) / WBN;
     const int tiles_m = (p.M + WBM - 1) / WBM;
     const unsigned nblk = (unsigned)(tiles_m * tiles_n);
-    const unsigned xcd = blockIdx.x % 8, q8 = nblk / 8, r8 = nblk % 8;
-    const unsigned t_start = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-    const unsigned t_len = q8 + (xcd < r8 ? 1u : 0u);
-    const unsigned t_stride = (gridDim.x - xcd + 7) / 8;
+    const XcdTiles tiles = xcd_tiles(nblk);
     const int nkt = p.K / BK;
     // tile order: bands of 4 tile columns, row-major inside a band (as k_gemm_widep: the 32 tiles an XCD holds at a time are
     // 8 rows x 4 columns and the band's weight panel is what that XCD's L2 keeps)
@@ -207,10 +204,10 @@ __global__ void __launch_bounds__(512, 2) k_gemm_z(GemmParams p) {
         }
     };
     auto cursor_begin = [&]() {
-        if (c_tl >= t_len) return;                             // exhausted: the previous stage's offsets again
+        if (c_tl >= tiles.len) return;                         // exhausted: the previous stage's offsets again
         if (c_ks == 0) {
             int n0_, tn_;
-            tile_origin(t_start + c_tl, c_m0, n0_, tn_);
+            tile_origin(tiles.start + c_tl, c_m0, n0_, tn_);
             abase = (const char*)p.A;
             second = false;
             if constexpr (MODE != MODE_DENSE) { c_tap = 0; c_left = 0; c_chunk = 0; }
@@ -269,7 +266,7 @@ __global__ void __launch_bounds__(512, 2) k_gemm_z(GemmParams p) {
             }
             --c_left;
         }
-        if (++c_ks == nkt) { c_ks = 0; c_tl += t_stride; }
+        if (++c_ks == nkt) { c_ks = 0; c_tl += tiles.stride; }
     };
     auto cursor_end = [&]() { c_slot = c_slot ? 0u : (unsigned)Z_SLOT1; };
     // piece IDX of the stage the cursor points at: 0-3 = A, 4-8 = B
@@ -371,9 +368,9 @@ __global__ void __launch_bounds__(512, 2) k_gemm_z(GemmParams p) {
 #else
 #define ZSTAMP(i)
 #endif
-    for (unsigned tl = blockIdx.x / 8; tl < t_len; tl += t_stride) {
+    for (unsigned tl = blockIdx.x / 8; tl < tiles.len; tl += tiles.stride) {
         int m0, n0, tile_n;
-        tile_origin(t_start + tl, m0, n0, tile_n);
+        tile_origin(tiles.start + tl, m0, n0, tile_n);
         // Convolution modes (round 6): the per-lane gather state of THIS tile is rebuilt here (it was built once already, one k-tile
         // before the previous tile's epilogue, for the cross-tile request of stage 0).  Carried across the epilogue instead, hipcc
         // kept it in scratch for the whole kernel and reloaded it inside the k-loop - scratch_load + s_waitcnt vmcnt(0) in front of

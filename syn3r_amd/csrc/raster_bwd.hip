@@ -29,12 +29,6 @@ namespace {
 constexpr int kGradSlots = 16;
 enum { G_R = 0, G_G, G_B, G_DEPTH, G_MX, G_MY, G_CXX, G_CXY, G_CYY, G_OP, G_USED = 10 };
 
-__device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nblk) {
-    unsigned q = nblk / 8, r = nblk % 8, xcd = bid % 8, k = bid / 8;
-    unsigned start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return start + k;
-}
-
 // Sum each of the 10 per-lane gradient terms over the 64 lanes.  Returns, on lane l with column c = l & 15 and 16-lane row q = l >> 4,
 // the total of value base(q) + c for c < 3 (even rows) / c < 2 (odd rows), base = 0, 3, 5, 8: row 0 owns values 0-2, row 1 values 3-4,
 // row 2 values 5-7, row 3 values 8-9 (reduce_slot below).

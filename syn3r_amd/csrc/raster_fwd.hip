@@ -846,13 +846,6 @@ __global__ void __launch_bounds__(256) k_tile_write(int gx, int tiles, int ss, i
     }
 }
 
-// contiguous-chunk-per-XCD remap of a 1-D block id (bijective for any block count)
-__device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nblk) {
-    unsigned q = nblk / 8, r = nblk % 8, xcd = bid % 8, k = bid / 8;
-    unsigned start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return start + k;
-}
-
 // Two pixels per lane (see k_render_bwd in raster_bwd.hip): a 16 x 16 tile is a block of TWO wavefronts, wavefront w
 // owns the 16 x 8 half (rows 8w .. 8w+7) and lane l the pixels (l & 15, 8w + (l >> 4)) and (.., + 4).  The
 // quadratic form, the exponent argument, the weights and the colour / depth accumulation are float2 arithmetic

@@ -568,6 +568,35 @@ def test_persistent_lds_dma_kernel_many_tiles(gpu):
         lib.syn3r_gemm_set_tile(0)
 
 
+@pytest.mark.parametrize("M,N,K,with_res", [(64512, 640, 640, True), (16128, 1280, 1280, True), (16128, 1280, 1280, False)])
+def test_deferred_epilogue_kernel_equals_one_pass(M, N, K, with_res, gpu):
+    """k_gemm_dmapd (persistent 256 x 160 tile, deferred LDS-free epilogue): the shapes the default dispatch gives it (kernel
+    trace), bit for bit against the one-pass 160-column kernel that `syn3r_gemm_set_tile(-256)` forces on the same operands
+    (same roundings in the same order), and against the fp32 product."""
+    from syn3r_amd.unet import ops
+    from syn3r_amd import _lib
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(M + N + with_res)
+    x, w, b = rnd(g, M, K, dev=gpu), rnd(g, N, K, scale=K ** -0.5, dev=gpu), rnd(g, N, dev=gpu)
+    res = rnd(g, M, N, dev=gpu) if with_res else None
+    kw = dict(residual=res, s_acc=0.7, s_res=1.3) if with_res else {}
+    with _lib.kernel_trace() as tr:
+        deferred = ops.linear(x, w, b, **kw)
+        torch.cuda.synchronize()
+    assert any("k_gemm_dmapd" in k for k in tr.result), list(tr.result)
+    try:
+        _lib.check(lib.syn3r_gemm_set_tile(-256), "set_tile")
+        with _lib.kernel_trace() as tr1:
+            one_pass = ops.linear(x, w, b, **kw)
+            torch.cuda.synchronize()
+    finally:
+        lib.syn3r_gemm_set_tile(0)
+    assert not any("k_gemm_dmapd" in k for k in tr1.result) and any("k_gemm_dma" in k for k in tr1.result), list(tr1.result)
+    assert torch.equal(deferred, one_pass)
+    y = x.float() @ w.float().T + b.float()
+    close(deferred, 0.7 * y + 1.3 * res.float() if with_res else y)
+
+
 @pytest.mark.parametrize("NB,Hi,Wi,Cin,Cout", [(4, 8, 8, 128, 160), (28, 9, 16, 1280, 1280), (3, 6, 10, 128, 328), (2, 8, 8, 256, 160)])
 def test_conv3x3_split_k(NB, Hi, Wi, Cin, Cout, gpu):
     """syn3r_gemm_set_splitk_workspace: the small-grid convolutions as two or four K parts (cut inside a filter tap too) + the finishing
