@@ -663,6 +663,38 @@ int syn3r_densification_stats(int N, const int* radii, const float* viewspace_gr
 size_t syn3r_knn3_workspace_bytes(int n);
 int syn3r_knn3_mean_dist2(const float* points, int n, float* out, void* ws, size_t ws_bytes, void* stream);
 
+/* The directed 3-nearest-neighbour graph of a cloud (points [n,3] fp32, 4 <= n <= 2^24): for point i the three OTHER points with
+ * the smallest d2 = (dx*dx + dy*dy) + dz*dz (no fused multiply-add), ascending by the pair (d2, original index) - the index breaks
+ * ties, so the answer is unique.  dist2 [n,3] fp32, index [n,3] int32.  ((dist2[i,0] + dist2[i,1]) + dist2[i,2]) / 3 is
+ * syn3r_knn3_mean_dist2's out[i] bit for bit (same search, same boxes; that entry keeps only the distances).  Replaces the
+ * neighbour query behind FSGS' proximity-guided densification (Zhu et al., ECCV 2024, section 3.2: "a directed graph connecting
+ * each Gaussian to its K = 3 nearest neighbours"; switched by --use_proximity_densify in bash_scripts/batch_{llff,dl3dv}_train.sh;
+ * FSGS' trainer is not vendored).  ws: syn3r_knn3_graph_workspace_bytes(n) bytes, 256-byte aligned (0 for n outside the range). */
+size_t syn3r_knn3_graph_workspace_bytes(int n);
+int syn3r_knn3_graph(const float* points, int n, float* dist2, int* index, void* ws, size_t ws_bytes, void* stream);
+
+/* FSGS' proximity-guided Gaussian unpooling on that graph (same section of the paper; what FSGS' densification does between the
+ * split and the prune when --use_proximity_densify is set; source not available, so every constant is an argument: UNPINNED).
+ *   count: Gaussian i is a source iff ((dist2[i,0] + dist2[i,1]) + dist2[i,2]) / 3 > score_thresh AND
+ *          max_c log_scales[i,c] > log_scale_thresh (raw log-scales against a host-computed log(threshold); -inf switches the second
+ *          test off).  Leaves the number of sources S in *count (device, one int32) and flags + ordered offsets in ws.
+ *   emit:  for the S sources in ascending index order and for each its neighbours nearest first, row 3 * rank + t of the outputs:
+ *          xyz = (xyz_src + xyz_dst) * 0.5f, log-scales / opacity logit / confidence of the DESTINATION, rotation (1, 0, 0, 0); one row
+ *          per directed edge, 3 S rows, no de-duplication.  SH coefficients of the new Gaussians are zero: the caller's buffers.
+ *          The order is fixed by an ordered scan (no atomics): two runs are bitwise equal.
+ * The host reads *count ONCE between the two calls (the only synchronisation) and passes it as n_sources; capacity = rows the output
+ * buffers hold: capacity < 3 * n_sources is SYN3R_E_INVALID with nothing written (the kernel also drops rows >= capacity).
+ * ws: syn3r_gaussian_unpool_workspace_bytes(n) bytes, 256-byte aligned, the SAME buffer for both calls.  Rejected on the host
+ * before any HIP call: null pointers, n outside [4, 2^24], a misaligned workspace, NaN thresholds (SYN3R_E_INVALID), a short
+ * workspace (SYN3R_E_WORKSPACE; syn3r_knn3_graph likewise). */
+size_t syn3r_gaussian_unpool_workspace_bytes(int n);
+int syn3r_gaussian_unpool_count(const float* dist2, const float* log_scales, int n, float score_thresh, float log_scale_thresh,
+                                int* count, void* ws, size_t ws_bytes, void* stream);
+int syn3r_gaussian_unpool_emit(const float* xyz, const float* log_scales, const float* opacity_logits, const float* confidence,
+                               const int* index, int n, int n_sources, int capacity, float* out_xyz, float* out_log_scales,
+                               float* out_opacity_logits, float* out_rotations, float* out_confidence, const void* ws,
+                               size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * LPIPS (VGG16) perceptual loss term of the trainer (the reference raises `opt.use_lpips_loss` around every refine,
  * model/diffusionGS.py:1690,1697; the loss lives in un-vendored FSGS and calls the `lpips` package: the PUBLISHED

@@ -172,6 +172,156 @@ __global__ void __launch_bounds__(kThreads) k_knn3(const float4* __restrict__ so
 }
 
 // ----------------------------------------------------------------------------------------------------------------
+// FSGS' proximity-guided Gaussian unpooling (Zhu et al., ECCV 2024, section 3.2; FSGS' source is not available - every choice the
+// paper leaves open is an argument or is stated here, UNPINNED):
+//   graph     point i -> the three OTHER points with the smallest d2 = (dx*dx + dy*dy) + dz*dz (no fused multiply-add), ascending
+//             by the pair (d2, original index): the index breaks ties, so the graph is unique whatever order the search visits;
+//   score     ((d2_0 + d2_1) + d2_2) / 3, the quantity k_knn3 returns (simple-knn's distCUDA2), bit for bit;
+//   source    score_i > score_thresh AND max_c log_scale[i,c] > log_scale_thresh (raw log-scales: no exp at the boundary);
+//   emission  for the S sources in ascending index order, neighbours nearest first: row 3 * rank + t gets
+//             xyz = (xyz_src + xyz_dst) * 0.5f, log-scales / opacity logit / confidence of the DESTINATION, rotation (1,0,0,0).
+//             One new Gaussian per directed edge (a -> b and b -> a both grow one).  SH coefficients are zero: the caller's.
+// The search is k_knn3's (same boxes, same pruning test, wave-uniform scans); a lane keeps three 64-bit keys (d2 bits << 32) | index
+// - d2 >= 0, so unsigned order on the bits is numeric order and ONE compare gives the (d2, index) order - inserted without a branch
+// (min / max on the keys), so that the triple stays in registers.
+typedef unsigned long long u64;
+
+__global__ void __launch_bounds__(kThreads) k_gather_idx(const float* __restrict__ pts, const unsigned* __restrict__ order, int n,
+                                                        float4* __restrict__ sorted) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const unsigned s = order[i];                           // the point's original index rides in the w lane (bits, never arithmetic)
+    sorted[i] = make_float4(pts[(size_t)s * 3], pts[(size_t)s * 3 + 1], pts[(size_t)s * 3 + 2], __uint_as_float(s));
+}
+
+__device__ __forceinline__ u64 kmin(u64 a, u64 b) { return a < b ? a : b; }
+__device__ __forceinline__ u64 kmax(u64 a, u64 b) { return a < b ? b : a; }
+
+__device__ __forceinline__ void keep3_key(u64 k, u64& b0, u64& b1, u64& b2) {     // b0 <= b1 <= b2
+    b2 = kmin(kmax(k, b1), b2);
+    b1 = kmin(kmax(k, b0), b1);
+    b0 = kmin(k, b0);
+}
+
+__global__ void __launch_bounds__(kThreads) k_knn3_graph(const float4* __restrict__ sorted, const Bounds* __restrict__ boxes, int n,
+                                                        int nboxes, float* __restrict__ dist2_out, int* __restrict__ index_out) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    const bool live = i < n;
+    const float4 p = sorted[live ? i : n - 1];
+    // "nothing yet": k_knn3's 3.0e38f with the largest index, above every real key.  The point itself gets all-ones distance
+    // bits - a mask formed from the LOADED index, so the load does not depend on the comparison and four of them issue together.
+    const u64 far = ((u64)__float_as_uint(3.0e38f) << 32) | 0xffffffffull;
+    const unsigned self = __float_as_uint(p.w);
+    u64 b0 = far, b1 = far, b2 = far;
+    auto insert = [&](const float4& q) {
+        const unsigned id = __float_as_uint(q.w);
+        const unsigned hi = __float_as_uint(dist2(p, q)) | (id == self ? 0xffffffffu : 0u);
+        keep3_key(((u64)hi << 32) | (u64)id, b0, b1, b2);
+    };
+    auto scan = [&](int b) {
+        const int first = b * kBox, last = min(n, first + kBox);
+        int j = first;
+        for (; j + 4 <= last; j += 4) {                    // wave-uniform addresses
+            const float4 q0 = sorted[j], q1 = sorted[j + 1], q2 = sorted[j + 2], q3 = sorted[j + 3];
+            insert(q0); insert(q1); insert(q2); insert(q3);
+        }
+        for (; j < last; ++j) insert(sorted[j]);
+    };
+    const int own_u = __builtin_amdgcn_readfirstlane((live ? i : n - 1) / kBox);
+    scan(own_u);
+    for (int b = 0; b < nboxes; ++b) {
+        if (b == own_u) continue;
+        const float bd = box_dist2(boxes[b], p);
+        // k_knn3's test: `<=` and the slack keep a box that could hold an equally distant point of smaller index
+        const bool need = live && bd <= __uint_as_float((unsigned)(b2 >> 32)) * 1.0001f;
+        if (__ballot(need) == 0ull) continue;
+        scan(b);
+    }
+    if (live) {
+        const size_t o = (size_t)__float_as_uint(p.w) * 3;
+        dist2_out[o] = __uint_as_float((unsigned)(b0 >> 32));
+        dist2_out[o + 1] = __uint_as_float((unsigned)(b1 >> 32));
+        dist2_out[o + 2] = __uint_as_float((unsigned)(b2 >> 32));
+        index_out[o] = (int)(unsigned)b0; index_out[o + 1] = (int)(unsigned)b1; index_out[o + 2] = (int)(unsigned)b2;
+    }
+}
+
+// Selection: flag per Gaussian and the number of sources per block of kThreads consecutive Gaussians
+__global__ void __launch_bounds__(kThreads) k_unpool_flag(const float* __restrict__ dist2, const float* __restrict__ log_scales, int n,
+                                                         float score_thresh, float log_scale_thresh,
+                                                         unsigned char* __restrict__ flags, int* __restrict__ block_counts) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    bool sel = false;
+    if (i < n) {
+        const float score = ((dist2[(size_t)i * 3] + dist2[(size_t)i * 3 + 1]) + dist2[(size_t)i * 3 + 2]) / 3.0f;
+        const float ls = fmaxf(fmaxf(log_scales[(size_t)i * 3], log_scales[(size_t)i * 3 + 1]), log_scales[(size_t)i * 3 + 2]);
+        sel = score > score_thresh && ls > log_scale_thresh;
+        flags[i] = sel ? 1 : 0;
+    }
+    __shared__ int s[kThreads / 64];
+    const int c = __popcll(__ballot(sel));
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+// ONE block: exclusive scan of the block counts in block order (a thread sums a contiguous run, the runs are scanned in thread
+// order), total -> *count.  No atomics: the offsets, and with them the order of the new rows, do not depend on scheduling.
+__global__ void __launch_bounds__(kThreads) k_unpool_scan(const int* __restrict__ block_counts, int nblocks, int* __restrict__ offsets,
+                                                         int* __restrict__ count) {
+    __shared__ int s[kThreads];
+    const int per = (nblocks + kThreads - 1) / kThreads;
+    const int first = min(nblocks, (int)threadIdx.x * per), last = min(nblocks, first + per);
+    int sum = 0;
+    for (int b = first; b < last; ++b) sum += block_counts[b];
+    s[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0;
+        for (int t = 0; t < kThreads; ++t) { const int v = s[t]; s[t] = run; run += v; }
+        *count = run;
+    }
+    __syncthreads();
+    int run = s[threadIdx.x];
+    for (int b = first; b < last; ++b) { offsets[b] = run; run += block_counts[b]; }
+}
+
+// One lane per Gaussian; a source writes its three rows at 3 * (block offset + rank inside the block).  Rows beyond `capacity` and
+// neighbour indices outside the cloud are not written (the host has checked both; this keeps a wrong argument inside the buffers).
+__global__ void __launch_bounds__(kThreads) k_unpool_emit(const float* __restrict__ xyz, const float* __restrict__ log_scales,
+                                                         const float* __restrict__ opacity, const float* __restrict__ confidence,
+                                                         const int* __restrict__ index, int n, const unsigned char* __restrict__ flags,
+                                                         const int* __restrict__ offsets, int capacity, float* __restrict__ o_xyz,
+                                                         float* __restrict__ o_ls, float* __restrict__ o_op, float* __restrict__ o_rot,
+                                                         float* __restrict__ o_conf) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    const bool sel = i < n && flags[i] != 0;
+    __shared__ int s[kThreads / 64];
+    const unsigned long long m = __ballot(sel);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) s[wave] = __popcll(m);
+    __syncthreads();
+    if (!sel) return;
+    int rank = __popcll(m & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) rank += s[w];
+    const long long row0 = 3ll * ((long long)offsets[blockIdx.x] + rank);
+    const float sx = xyz[(size_t)i * 3], sy = xyz[(size_t)i * 3 + 1], sz = xyz[(size_t)i * 3 + 2];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        const long long r = row0 + t;
+        const int d = index[(size_t)i * 3 + t];
+        if (r >= capacity || (unsigned)d >= (unsigned)n) continue;
+        o_xyz[r * 3] = (sx + xyz[(size_t)d * 3]) * 0.5f;
+        o_xyz[r * 3 + 1] = (sy + xyz[(size_t)d * 3 + 1]) * 0.5f;
+        o_xyz[r * 3 + 2] = (sz + xyz[(size_t)d * 3 + 2]) * 0.5f;
+        o_ls[r * 3] = log_scales[(size_t)d * 3]; o_ls[r * 3 + 1] = log_scales[(size_t)d * 3 + 1]; o_ls[r * 3 + 2] = log_scales[(size_t)d * 3 + 2];
+        o_op[r] = opacity[d];
+        o_conf[r] = confidence[d];
+        *(float4*)(o_rot + r * 4) = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------------------
 // Statistical outlier removal of a point cloud: what the reference runs on the dust3r cloud,
 // `down_pcd.remove_statistical_outlier(nb_neighbors=20, std_ratio=3.0)` (model/diffusionGS.py:321, open3d 0.17.0 - not in
 // /root/reference).  Published algorithm (Open3D `PointCloud::RemoveStatisticalOutliers`), restated:
@@ -361,6 +511,16 @@ __global__ void __launch_bounds__(kThreads) k_outlier_keep(const double* __restr
     keep[i] = (v > 0.0 && v < stats[2]) ? 1 : 0;
 }
 
+// workspace checks of the graph / unpooling entries: short -> SYN3R_E_WORKSPACE, misaligned -> SYN3R_E_INVALID
+int ws_check(const char* who, const void* ws, size_t have, size_t need) {
+    if (have < need) {
+        set_error("%s: workspace too small (%zu < %zu)", who, have, need);
+        return SYN3R_E_WORKSPACE;
+    }
+    SYN3R_REQUIRE(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+    return SYN3R_OK;
+}
+
 }  // namespace
 
 extern "C" size_t syn3r_pcd_outlier_workspace_bytes(int n) {
@@ -454,5 +614,89 @@ extern "C" int syn3r_knn3_mean_dist2(const float* points, int n, float* out, voi
     // 4. search
     SYN3R_LAUNCH(k_knn3, dim3(blocks), dim3(kThreads), 0, stream, sorted, order, boxes, n, nbox, out);
     SYN3R_LAUNCH_CHECK("knn3");
+    return SYN3R_OK;
+}
+
+extern "C" size_t syn3r_knn3_graph_workspace_bytes(int n) { return syn3r_knn3_workspace_bytes(n); }      // the same layout
+
+extern "C" int syn3r_knn3_graph(const float* points, int n, float* dist2, int* index, void* ws, size_t ws_bytes, void* stream_) {
+    SYN3R_REQUIRE(points && dist2 && index && ws, "knn3_graph: null pointer");
+    SYN3R_REQUIRE(n >= 4 && n <= SYN3R_DIM_MAX, "knn3_graph: needs 4 .. %d points (3 neighbours), got n=%d", SYN3R_DIM_MAX, n);
+    if (int rc = ws_check("knn3_graph", ws, ws_bytes, syn3r_knn3_graph_workspace_bytes(n))) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t nn = (size_t)n;
+    const int nbox = (int)((nn + kBox - 1) / kBox);
+    char* w = (char*)ws;
+    unsigned* codes_a = (unsigned*)w; w += align256(nn * 4);
+    unsigned* codes_b = (unsigned*)w; w += align256(nn * 4);
+    unsigned* order_a = (unsigned*)w; w += align256(nn * 4);
+    unsigned* order_b = (unsigned*)w; w += align256(nn * 4);
+    float4* sorted = (float4*)w; w += align256(nn * 16);
+    Bounds* part = (Bounds*)w; w += align256((size_t)(nbox + 1) * sizeof(Bounds));
+    Bounds* boxes = (Bounds*)w; w += align256((size_t)(nbox + 1) * sizeof(Bounds));
+    void* sort_ws = w;
+    // the preparation of syn3r_knn3_mean_dist2 (cloud bounds, Morton order, per-box bounds); the gather also carries the index
+    SYN3R_LAUNCH(k_aabb, dim3(nbox), dim3(kThreads), 0, stream, points, 3, n, kBox, part);
+    SYN3R_LAUNCH(k_aabb_final, dim3(1), dim3(kThreads), 0, stream, part, nbox, boxes + nbox);
+    const int blocks = (n + kThreads - 1) / kThreads;
+    SYN3R_LAUNCH(k_morton, dim3(blocks), dim3(kThreads), 0, stream, points, n, boxes + nbox, codes_a);
+    int in_b = 0;
+    int rc = argsort_depth_u32(codes_a, order_a, codes_b, order_b, nn, sort_ws, stream, &in_b);
+    if (rc != SYN3R_OK) return rc;
+    const unsigned* order = in_b ? order_b : order_a;
+    SYN3R_LAUNCH(k_gather_idx, dim3(blocks), dim3(kThreads), 0, stream, points, order, n, sorted);
+    SYN3R_LAUNCH(k_aabb, dim3(nbox), dim3(kThreads), 0, stream, (const float*)sorted, 4, n, kBox, boxes);
+    SYN3R_LAUNCH(k_knn3_graph, dim3(blocks), dim3(kThreads), 0, stream, sorted, boxes, n, nbox, dist2, index);
+    SYN3R_LAUNCH_CHECK("knn3_graph");
+    return SYN3R_OK;
+}
+
+extern "C" size_t syn3r_gaussian_unpool_workspace_bytes(int n) {
+    if (!SYN3R_DIM_OK(n)) return 0;
+    const size_t nblk = ((size_t)n + kThreads - 1) / kThreads;
+    return align256(nblk * 4) * 2 + align256((size_t)n) + 256;      // block counts, block offsets, flags
+}
+
+extern "C" int syn3r_gaussian_unpool_count(const float* dist2, const float* log_scales, int n, float score_thresh,
+                                           float log_scale_thresh, int* count, void* ws, size_t ws_bytes, void* stream_) {
+    SYN3R_REQUIRE(dist2 && log_scales && count && ws, "gaussian_unpool_count: null pointer");
+    SYN3R_REQUIRE(n >= 4 && n <= SYN3R_DIM_MAX, "gaussian_unpool_count: needs 4 .. %d Gaussians, got n=%d", SYN3R_DIM_MAX, n);
+    SYN3R_REQUIRE(score_thresh == score_thresh && log_scale_thresh == log_scale_thresh, "gaussian_unpool_count: NaN threshold");
+    if (int rc = ws_check("gaussian_unpool_count", ws, ws_bytes, syn3r_gaussian_unpool_workspace_bytes(n))) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int nblk = (n + kThreads - 1) / kThreads;
+    char* w = (char*)ws;
+    int* counts = (int*)w; w += align256((size_t)nblk * 4);
+    int* offsets = (int*)w; w += align256((size_t)nblk * 4);
+    unsigned char* flags = (unsigned char*)w;
+    SYN3R_LAUNCH(k_unpool_flag, dim3(nblk), dim3(kThreads), 0, stream, dist2, log_scales, n, score_thresh, log_scale_thresh, flags, counts);
+    SYN3R_LAUNCH(k_unpool_scan, dim3(1), dim3(kThreads), 0, stream, (const int*)counts, nblk, offsets, count);
+    SYN3R_LAUNCH_CHECK("gaussian_unpool_count");
+    return SYN3R_OK;
+}
+
+extern "C" int syn3r_gaussian_unpool_emit(const float* xyz, const float* log_scales, const float* opacity_logits,
+                                          const float* confidence, const int* index, int n, int n_sources, int capacity,
+                                          float* out_xyz, float* out_log_scales, float* out_opacity_logits, float* out_rotations,
+                                          float* out_confidence, const void* ws, size_t ws_bytes, void* stream_) {
+    SYN3R_REQUIRE(xyz && log_scales && opacity_logits && confidence && index && ws, "gaussian_unpool_emit: null pointer");
+    SYN3R_REQUIRE(out_xyz && out_log_scales && out_opacity_logits && out_rotations && out_confidence,
+                  "gaussian_unpool_emit: null pointer (output)");
+    SYN3R_REQUIRE(n >= 4 && n <= SYN3R_DIM_MAX, "gaussian_unpool_emit: needs 4 .. %d Gaussians, got n=%d", SYN3R_DIM_MAX, n);
+    SYN3R_REQUIRE(n_sources >= 0 && n_sources <= n, "gaussian_unpool_emit: n_sources=%d outside 0 .. n=%d", n_sources, n);
+    SYN3R_REQUIRE(capacity >= 0 && (long long)capacity >= 3ll * n_sources,
+                  "gaussian_unpool_emit: capacity of %d rows is too small for 3 x %d new Gaussians", capacity, n_sources);
+    if (int rc = ws_check("gaussian_unpool_emit", ws, ws_bytes, syn3r_gaussian_unpool_workspace_bytes(n))) return rc;
+    SYN3R_REQUIRE(((uintptr_t)out_rotations & 15) == 0, "gaussian_unpool_emit: out_rotations must be 16-byte aligned");
+    if (n_sources == 0) return SYN3R_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int nblk = (n + kThreads - 1) / kThreads;
+    const char* w = (const char*)ws;
+    w += align256((size_t)nblk * 4);
+    const int* offsets = (const int*)w; w += align256((size_t)nblk * 4);
+    const unsigned char* flags = (const unsigned char*)w;
+    SYN3R_LAUNCH(k_unpool_emit, dim3(nblk), dim3(kThreads), 0, stream, xyz, log_scales, opacity_logits, confidence, index, n, flags,
+                 offsets, capacity, out_xyz, out_log_scales, out_opacity_logits, out_rotations, out_confidence);
+    SYN3R_LAUNCH_CHECK("gaussian_unpool_emit");
     return SYN3R_OK;
 }

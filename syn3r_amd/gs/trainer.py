@@ -21,6 +21,7 @@ import torch
 from .. import _lib as L
 from ..raster import GaussianRasterizationSettings, GaussianRasterizer
 from .train_ops import FusedAdam, depth_correlation_loss, image_metrics, knn3_mean_dist2, l1_loss, photometric_loss
+from .train_ops import proximity_unpool as _proximity_unpool_op
 
 SH_C0 = 0.28209479177387814
 
@@ -241,6 +242,13 @@ class OptimizationParams:
     densify_grad_threshold: float = 0.0002
     prune_min_opacity: float = 0.005
     prune_screen_size: float = 20.0
+    # FSGS' proximity-guided Gaussian unpooling (GSTrainer.proximity_unpool; the reference's --use_proximity_densify): off by default.
+    # Until iteration 2000, score > 5 x extent, scale > 1 x extent: RECALLED from FSGS' gaussian_model.py, which is not available
+    # to check against - UNPINNED, and scene-scale dependent: set the factors for the scene at hand.
+    use_proximity_densify: bool = False
+    proximity_until_iter: int = 2000
+    proximity_dist_factor: float = 5.0
+    proximity_scale_factor: float = 1.0
 
 
 class _Scene:
@@ -273,6 +281,7 @@ class GSTrainer:
         self.checkpoint_iterations: List[int] = list(checkpoint_iterations or [])
         self.iteration = 0
         self.densify = False              # adaptive density control inside train_step (training / finetune set it)
+        self.last_unpooled = 0            # Gaussians the proximity unpooling added in the last densify_and_prune call
         self.truncated_renders = 0        # renders whose (Gaussian, tile) pair list outgrew the async capacity (see _loop)
         self.background = torch.tensor(background, dtype=torch.float32, device=gaussians._xyz.device)
         self._rng = np.random.default_rng(self.opt.seed)
@@ -409,8 +418,8 @@ class GSTrainer:
     # ------------------------------------------------------------------ adaptive density control
     # FSGS' training loop (un-vendored) densifies with the published 3DGS clone / split / prune rules plus its own
     # proximity-guided unpooling; the published rules are restated here (Kerbl et al. 2023 section 5.2, UNPINNED: checked
-    # against oracle/densify_oracle.py), the FSGS-specific unpooling is not (no source, no description of its constants
-    # in /root/reference).  Everything runs on the device; the optimiser moments follow the Gaussians.
+    # against oracle/densify_oracle.py); the FSGS-specific unpooling follows the paper's section 3.2 (`proximity_unpool`, no source:
+    # its constants are options).  Everything runs on the device; the optimiser moments follow the Gaussians.
     _PARAM_ATTRS = ("_xyz", "_features", "_opacity", "_scaling", "_rotation")     # = order of the optimiser groups
 
     def cameras_extent(self) -> float:
@@ -464,11 +473,34 @@ class GSTrainer:
         return torch.randn((n, 3), generator=self._noise_gen, device=dev)
 
     @torch.no_grad()
+    def proximity_unpool(self, extent: float) -> int:
+        """FSGS' proximity-guided unpooling (Zhu et al., ECCV 2024, section 3.2) on the current model: the HIP operator
+        `train_ops.proximity_unpool` with score_thresh = proximity_dist_factor x extent and log_scale_thresh =
+        log(proximity_scale_factor x extent), the new Gaussians appended with zero SH coefficients and zero Adam moments; the
+        densification statistics restart.  Returns the number appended (3 per source); fewer than 4 Gaussians or no source: 0 and
+        nothing is touched.  One host synchronisation (the source count)."""
+        g, o = self.gaussians, self.opt
+        if g._xyz.shape[0] < 4:
+            return 0
+        scale = float(o.proximity_scale_factor) * float(extent)
+        new = _proximity_unpool_op(g._xyz, g._scaling, g._opacity, g.confidence, float(o.proximity_dist_factor) * float(extent),
+                                   math.log(scale) if scale > 0.0 else -math.inf)
+        m = int(new["count"])
+        if m == 0:
+            return 0
+        feats = torch.zeros((m,) + tuple(g._features.shape[1:]), dtype=g._features.dtype, device=g._features.device)
+        self._append_gaussians({"_xyz": new["xyz"], "_features": feats, "_opacity": new["opacity"].reshape((m,) + tuple(g._opacity.shape[1:])),
+                                "_scaling": new["scaling"], "_rotation": new["rotation"]}, new["confidence"])
+        return m
+
+    @torch.no_grad()
     def densify_and_prune(self, max_grad: float, min_opacity: float, extent: float, max_screen_size: Optional[float]):
         """Published 3DGS `densify_and_prune`: clone small Gaussians with a large view-space gradient, split large ones
         into two (positions sampled from the Gaussian, scales / 1.6), then prune transparent, screen-filling and
-        world-huge ones.  Returns (cloned, split, pruned)."""
+        world-huge ones.  Returns (cloned, split, pruned).  With `opt.use_proximity_densify`, before `opt.proximity_until_iter`,
+        FSGS' `proximity_unpool` runs between the split and the prune; what it added is `self.last_unpooled`."""
         g, o = self.gaussians, self.opt
+        self.last_unpooled = 0
         g.ensure_stats()
         grads = g.xyz_gradient_accum / g.denom
         grads[grads.isnan()] = 0.0
@@ -498,6 +530,10 @@ class GSTrainer:
         keep = ~torch.cat([sel, torch.zeros(N * n_split, dtype=torch.bool, device=sel.device)])
         self._keep_gaussians(keep)
         max_radii = max_radii[keep]
+        # ---- FSGS' proximity-guided unpooling (recalled order of its densification: clone, split, proximity, prune)
+        if o.use_proximity_densify and self.iteration + 1 < o.proximity_until_iter:
+            self.last_unpooled = self.proximity_unpool(extent)
+            max_radii = torch.cat([max_radii, torch.zeros(self.last_unpooled, device=max_radii.device)])
         # ---- prune
         prune = g.get_opacity < min_opacity
         if max_screen_size:

@@ -85,6 +85,9 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--depth_weight", type=float, default=0.0,
                     help="weight of FSGS' depth-correlation term, 1 - Pearson(rendered depth, monocular prior), on every training step "
                          "(0 = off); views need a prior (Camera.depth_image or an injected GSTrainer.depth_net)")
+    ap.add_argument("--use_proximity_densify", type=int, default=0,
+                    help="1: FSGS' proximity-guided Gaussian unpooling inside the density control (bash_scripts/batch_llff_train.sh:37 and "
+                         "batch_dl3dv_train.sh:85 pass 0); thresholds: OptimizationParams.proximity_*")
     ap.add_argument("--num_inference_steps", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     # FSGS' parameter groups (scripts/train.py:44-46: -s, --eval, --n_views, --resolution, --use_dust3r ... of the batch scripts)
@@ -106,7 +109,7 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
 FSGS_FLAGS = frozenset([
     "-s", "--source_path", "-m", "-r", "--resolution", "--images", "-i", "--eval", "--n_views", "--use_dust3r", "--rand_pcd",
     "--num_train_samples", "--sample_pseudo_interval", "--sample_svd_pseudo_interval", "--start_sample_svd_frame",
-    "--start_sample_pseudo", "--end_sample_pseudo", "--svd_depth_warmup", "--svd_lpips_weight", "--use_proximity_densify",
+    "--start_sample_pseudo", "--end_sample_pseudo", "--svd_depth_warmup", "--svd_lpips_weight",
     "--percent_dense", "--densify_grad_threshold", "--densify_from_iter", "--densify_until_iter", "--densification_interval",
     "--opacity_reset_interval", "--position_lr_init", "--position_lr_final", "--position_lr_max_steps", "--feature_lr",
     "--opacity_lr", "--scaling_lr", "--rotation_lr", "--depth_pseudo_weight", "--white_background", "--sh_degree",
@@ -225,6 +228,7 @@ def run_scene(name: str, args, device, factory: Callable) -> List[float]:
         comps = args.svd_dir if args.svd_dir else _stand_in_svd(device)
     trainer.opt.lpips_weight = float(getattr(args, "lpips_weight", 0.0))
     trainer.opt.depth_weight = float(getattr(args, "depth_weight", 0.0))
+    trainer.opt.use_proximity_densify = bool(getattr(args, "use_proximity_densify", 0))
     if sc.get("lpips") is not None:
         trainer.lpips = sc["lpips"]
     elif getattr(args, "lpips_weights", None):
