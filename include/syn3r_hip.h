@@ -719,6 +719,29 @@ int syn3r_lpips_layer_f16(const void* a, const void* b, const float* w, long lon
                           void* ws, size_t ws_bytes, void* stream);
 int syn3r_lpips_layer_bwd_f16(const void* a, const void* b, const float* w, long long P, int C, float gscale, int accumulate,
                               void* grad_a, void* stream);
+/* Split activations (the "fp16x2" precision of gs/lpips.py): a forward activation v - the fp32 accumulator after bias and ReLU -
+ * is stored as the fp16 pair hi = half(v), lo = half(v - float(hi)), channels-last [H*W, 2C] with the hi plane in channels
+ * [0, C) and the lo plane in [C, 2C).  Gradients stay single fp16 tensors [H*W, C] carrying the loss scale.
+ * The 3x3 convolution for such tensors.  Its INPUT X [NB*Hi*Wi, Cin] is read as the plain kernel reads it: a split tensor of C
+ * channels is passed as Cin = 2C under weights duplicated along Cin ([W | W]: fp32 accumulation sums W.hi + W.lo before the one
+ * rounding); the image tensor keeps Cin = 64.  split_out != 0: out [NB*Hi*Wi, ld_out >= 2 Cout] receives the pair of
+ * max(acc + bias, 0) (relu != 0) or of acc + bias; relu_mask must be null.  split_out == 0: out [.., ld_out >= Cout] is one
+ * fp16 result, zeroed where relu_mask [.., ld_mask] <= 0 (nullable; backward-data on the transposed, flipped weights: the mask is
+ * the hi plane of the split activation below, ld_mask = twice its channel count).  Cin % 64 == 0, Cout % 8 == 0, strides % 8 == 0. */
+int syn3r_conv2d3x3_split_f16(const void* X, const void* W, void* out, long long ld_out, const void* bias, int relu, int split_out,
+                              const void* relu_mask, long long ld_mask, int NB, int Hi, int Wi, int Cin, int Cout, void* stream);
+/* image [3,H,W] fp32 in [0,1] -> [H*W, 64] fp16 with the three scaled channels as pairs: hi in channels 0..2, lo in 3..5, rest zero */
+int syn3r_lpips_image_split_f16(const float* img, int H, int W, void* out, void* stream);
+/* nn.MaxPool2d(2, 2) on a split map x [H,W,2C] -> y [H/2,W/2,2C]: cells compared as float(hi) + float(lo), the winning pair copied
+ * (first maximum of the window); its backward takes the same x, gy [H/2,W/2,C] fp16 and writes gx [H,W,C] fp16.  C % 8 == 0. */
+int syn3r_maxpool2_split_f16(const void* x, int H, int W, int C, void* y, void* stream);
+int syn3r_maxpool2_bwd_split_f16(const void* x, const void* gy, int H, int W, int C, void* gx, void* stream);
+/* The LPIPS layer and its backward on split feature maps a, b [P, 2C] (read as float(hi) + float(lo)); grad_a [P, C] fp16, saturated
+ * to the fp16 range like the fp16 entry's.  Same workspace. */
+int syn3r_lpips_layer_split_f16(const void* a, const void* b, const float* w, long long P, int C, int accumulate, float* value,
+                                void* ws, size_t ws_bytes, void* stream);
+int syn3r_lpips_layer_bwd_split_f16(const void* a, const void* b, const float* w, long long P, int C, float gscale, int accumulate,
+                                    void* grad_a, void* stream);
 
 /* Statistical outlier removal of a point cloud: what model/diffusionGS.py:321 asks of open3d
  * (`down_pcd.remove_statistical_outlier(nb_neighbors=20, std_ratio=3.0)`; open3d 0.17.0 is not in the reference tree, the

@@ -129,6 +129,12 @@ SIGNATURES = {
     "syn3r_lpips_layer_workspace_bytes": (c_sz, [c_ll, c_i]),
     "syn3r_lpips_layer_f16": (c_i, [c_p, c_p, c_p, c_ll, c_i, c_i, c_p, c_p, c_sz, c_p]),
     "syn3r_lpips_layer_bwd_f16": (c_i, [c_p, c_p, c_p, c_ll, c_i, c_f, c_i, c_p, c_p]),
+    "syn3r_conv2d3x3_split_f16": (c_i, [c_p, c_p, c_p, c_ll, c_p, c_i, c_i, c_p, c_ll, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "syn3r_lpips_image_split_f16": (c_i, [c_p, c_i, c_i, c_p, c_p]),
+    "syn3r_maxpool2_split_f16": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
+    "syn3r_maxpool2_bwd_split_f16": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p]),
+    "syn3r_lpips_layer_split_f16": (c_i, [c_p, c_p, c_p, c_ll, c_i, c_i, c_p, c_p, c_sz, c_p]),
+    "syn3r_lpips_layer_bwd_split_f16": (c_i, [c_p, c_p, c_p, c_ll, c_i, c_f, c_i, c_p, c_p]),
     "syn3r_pcd_outlier_workspace_bytes": (c_sz, [c_i]),
     "syn3r_pcd_statistical_outlier": (c_i, [c_p, c_i, c_i, c_d, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "syn3r_flow_cycle_mask": (c_i, [c_p, c_p, c_i, c_i, c_i, c_f, c_p, c_p, c_p]),

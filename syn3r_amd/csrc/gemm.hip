@@ -22,6 +22,7 @@
 //   k_lnlin320     LayerNorm + stacked q / k / v projection for C = 320 in one kernel
 //   k_gemm_dma     BM x 160 tile, LDS-DMA 3-stage ring (BM = 256, wavefronts 4-7 staggered; every convolution /
 //                  temporal convolution and the K = 320 residual projections) or 2-stage (BM = 128, small grids)
+//                  (EPI_SPLIT_*: the convolution tile with the split-activation epilogue, fp16 pairs hi + lo: LPIPS "fp16x2")
 //   k_gemm_dmapd   persistent 256 x 160 tile with a deferred, LDS-free epilogue (gemm_dmapd.h): residual projections, 640 <= K <= 1280
 //   k_gemm_skinny  M <= 16 rows (time embedding, folded cross-attention context)
 // This file is the dispatch: the shape rules (launch_dma), the launchers and the C-ABI entry points; the kernel families live in
@@ -681,6 +682,36 @@ extern "C" int syn3r_conv2d3x3_act_f16(const void* X, const void* W, void* out, 
     SYN3R_REQUIRE(((uintptr_t)relu_mask % 16) == 0, "conv2d3x3_act: mask must be 16-byte aligned");
     // the persistent kernels have their own (lean) epilogue: the convolution modes never use them (launch_dma_bm)
     return launch_dma<MODE_CONV2D>(p, (hipStream_t)stream);
+}
+
+// The same convolution for split activations (the LPIPS "fp16x2" mode; split_epilogue in gemm_common.h).  The INPUT side is the
+// plain kernel: a split tensor [P, 2 C] is an ordinary input of Cin = 2 C channels under weights duplicated along Cin, and the
+// fp32 accumulator sums W . hi + W . lo before its one rounding.  split_out: out [P, ld_out >= 2 Cout] = the pair of
+// relu(acc + bias); otherwise out [P, ld_out >= Cout] fp16, zeroed where relu_mask [P, ld_mask] <= 0 (backward-data: the mask is the hi
+// plane of the split activation below).  One 256 x 160 tile per block, no split-K: the K parts' sum would need this epilogue in
+// k_splitk_finish, and the ReLU launches of the fp16 mode do not split either (launch_splitk).
+extern "C" int syn3r_conv2d3x3_split_f16(const void* X, const void* W, void* out, long long ld_out, const void* bias, int relu, int split_out,
+                                         const void* relu_mask, long long ld_mask, int NB, int Hi, int Wi, int Cin, int Cout, void* stream) {
+    SYN3R_REQUIRE(NB > 0 && Hi > 0 && Wi > 0 && Cin > 0 && Cout > 0, "conv2d3x3_split: bad sizes");
+    SYN3R_REQUIRE(Cin % BK == 0 && Cout % 8 == 0, "conv2d3x3_split: Cin=%d must be a multiple of %d, Cout=%d of 8", Cin, BK, Cout);
+    SYN3R_REQUIRE(ld_out >= (split_out ? 2ll : 1ll) * Cout, "conv2d3x3_split: ld_out=%lld is short of %d columns", ld_out, (split_out ? 2 : 1) * Cout);
+    SYN3R_REQUIRE(!(split_out && relu_mask), "conv2d3x3_split: a mask goes with the plain output only");
+    SYN3R_REQUIRE(!relu_mask || (ld_mask >= Cout && ld_mask % 8 == 0 && ld_mask < (1ll << 31)), "conv2d3x3_split: bad mask stride %lld", ld_mask);
+    GemmParams p{};
+    p.A = (const __half*)X; p.W = (const __half*)W; p.out = (__half*)out; p.ldc = ld_out; p.bias = (const __half*)bias;
+    p.s_acc = 1.0f; p.s_res = 0.f; p.s_aux = 0.f;
+    p.relu = relu ? 1 : 0; p.relu_mask = (const __half*)relu_mask; p.ld_mask = (int)ld_mask;
+    p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.stride = 1; p.ups = 0; p.pad = 1; p.Ho = Hi; p.Wo = Wi;
+    long long M = (long long)NB * Hi * Wi;
+    SYN3R_REQUIRE(M < (1ll << 31), "conv2d3x3_split: too many output pixels");
+    p.M = (int)M; p.N = Cout; p.K = 9 * Cin;
+    int rc = check_common(p, "conv2d3x3_split");
+    if (rc) return rc;
+    SYN3R_REQUIRE((((uintptr_t)relu_mask | (uintptr_t)bias) % 16) == 0, "conv2d3x3_split: mask and bias must be 16-byte aligned");
+    static_assert(8 * WM * EPI_LD * sizeof(__half) <= DMA256_LDS, "one staged fp16 plane must fit in the ring");
+    if (split_out)
+        return launch_tiles<k_gemm_dma<MODE_CONV2D, 256, EPI_SPLIT_OUT>>("conv split", DMA256_LDS, tiles256(p), 512, (hipStream_t)stream, p, nullptr, "k_gemm_dma<1,256,split>");
+    return launch_tiles<k_gemm_dma<MODE_CONV2D, 256, EPI_SPLIT_MASK>>("conv split", DMA256_LDS, tiles256(p), 512, (hipStream_t)stream, p, nullptr, "k_gemm_dma<1,256,mask>");
 }
 
 extern "C" int syn3r_tconv3_f16(const void* X, const void* W, void* out, long long ldc, const void* bias,

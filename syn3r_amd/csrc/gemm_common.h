@@ -71,6 +71,7 @@ struct GemmParams {
     // [ksplit][M][N]; k_splitk_finish sums the parts in order and applies the epilogue (launch_dma)
     int ksplit; float* split_ws;
     int relu;                             // result = max(result, 0)
+    int ld_mask;                          // split_epilogue only: row stride of relu_mask (in the 4 bytes that padded `relu`: no field moves)
     const __half* relu_mask;              // [M][ldc]: result zeroed where mask <= 0 (ReLU backward: grad * (activation > 0))
     // GroupNorm partial sums of the OUTPUT (round 6; the lean epilogue of the persistent kernels, gn_tile_stats in gemm_wide.h):
     // gn_part[((m / 32) * 2 + q) * gn_units + n / 10], q = 0: sum of x, q = 1: sum of x^2 over rows [32 rb, 32 rb + 32) and columns
@@ -265,6 +266,85 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, float4v (&acc
             OUT_STORE((half8*)(p.out + (long long)m * p.ldc + n), v);
         } else {
             for (int e = 0; e < 8 && n + e < p.N; ++e) ((_Float16*)p.out)[(long long)m * p.ldc + n + e] = v[e];
+        }
+    }
+}
+
+// The split-activation epilogue (k_gemm_dma<MODE_CONV2D, 256, EPI_SPLIT_*>, gemm_dma.h: the LPIPS convolutions of the "fp16x2" mode).  A value v - the fp32
+// accumulator after bias and ReLU - leaves as the fp16 pair hi = half(v), lo = half(v - float(hi)) (the subtraction is exact in
+// fp32), i.e. 21+ significant bits wherever lo is a normal fp16 number, instead of 11.
+//   SPLIT_OUT  out [M][ldc] holds the hi plane in columns [0, N) and the lo plane in [N, 2 N).  The staging region of a wavefront
+//              holds one fp16 plane, so the tile is staged and stored twice (hi, then lo) from the live accumulators.
+//   otherwise  one fp16 result, zeroed where relu_mask [M][ld_mask] <= 0: the backward-data convolution, whose mask is the hi
+//              plane of a split activation (hi > 0 exactly where the pair's sum is: lo never changes the sign).
+// bias + ReLU only (no row vector, residual, aux, gate or scale), N % 8 == 0.  Entered like gemm_epilogue: by every wavefront,
+// after the last read of the ring.
+template <bool SPLIT_OUT>
+__device__ __forceinline__ void split_epilogue(const GemmParams& p, float4v (&acc)[TM][TN], char* smem_raw, int lane, int wv, int wm,
+                                               int wn, int m0, int n0) {
+    typedef _Float16 half4e __attribute__((ext_vector_type(4)));
+    const int fr = lane & 15, fq = lane >> 4;
+    __half* st = (__half*)smem_raw + wv * (WM * EPI_LD);
+    const int gm0 = m0 + wm * WM, gn0 = n0 + wn * WN;
+    float bias4[TN][4];
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int n = gn0 + j * 16 + fq * 4;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bias4[j][r] = 0.0f;
+        if (p.bias && n < p.N) {                       // (N % 8 == 0: whole quads)
+            const half4e b = *(const half4e*)(p.bias + n);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) bias4[j][r] = (float)b[r];
+        }
+    }
+    constexpr int NQ = WM * (WN / 8) / 64;             // 10 stores per lane and plane
+    // v in place (the bias registers die here); a pair's hi must be finite, or its sum would be a NaN
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = acc[i][j][r] + bias4[j][r];
+                if (p.relu) v = fmaxf(v, 0.0f);
+                acc[i][j][r] = SPLIT_OUT ? fminf(fmaxf(v, -65504.0f), 65504.0f) : v;
+            }
+    // every pass stores the fp16 of what is left of v and keeps the remainder (exact in fp32): hi, then lo
+#pragma nounroll
+    for (int plane = 0; plane < (SPLIT_OUT ? 2 : 1); ++plane) {
+        if (plane) __syncthreads();                    // the hi plane has been read out of the staging tile
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const int row = i * 16 + fr;
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                half4e o;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    o[r] = (_Float16)acc[i][j][r];
+                    if constexpr (SPLIT_OUT) acc[i][j][r] -= (float)o[r];
+                }
+                *(half4e*)(st + row * EPI_LD + j * 16 + fq * 4) = o;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < NQ; ++it) {
+            const int q = lane + it * 64;
+            const int row = q / (WN / 8), ch = q - row * (WN / 8);
+            const int m = gm0 + row, n = gn0 + ch * 8;
+            if (m >= p.M || n >= p.N) continue;
+            half8 v = *(const half8*)(st + row * EPI_LD + ch * 8);
+            if constexpr (!SPLIT_OUT) {
+                if (p.relu_mask) {
+                    const half8 mk = *(const half8*)(p.relu_mask + (long long)m * p.ld_mask + n);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[e] = (float)mk[e] > 0.0f ? v[e] : (_Float16)0.0f;
+                }
+            }
+            *(half8*)(p.out + (long long)m * p.ldc + plane * p.N + n) = v;
         }
     }
 }

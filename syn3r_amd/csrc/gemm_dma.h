@@ -1,8 +1,12 @@
-// k_gemm_dma (BM x 160 tile on an LDS-DMA ring, one tile per block) and k_splitk_finish.
+// k_gemm_dma (BM x 160 tile on an LDS-DMA ring, one tile per block; EPI: its epilogue) and k_splitk_finish.
 // Included by gemm.hip inside its anonymous namespace (one translation unit; the kernels share GemmParams, the epilogues and the
 // LDS-DMA pieces of gemm_common.h / gemm_dma160.h, where the ring and its counted waits are described).
 
-template <int MODE, int BM>
+// EPI: which epilogue the tile leaves through - a compile-time choice, so that the general one carries no branch for the others.
+// The split-activation epilogues (gemm_common.h) serve the LPIPS "fp16x2" mode: MODE_CONV2D, BM = 256, never with split-K.
+enum { EPI_GENERAL = 0, EPI_SPLIT_OUT = 1, EPI_SPLIT_MASK = 2 };      // gemm_epilogue / split_epilogue<true> / split_epilogue<false>
+
+template <int MODE, int BM, int EPI = EPI_GENERAL>
 __global__ void __launch_bounds__(BM * 2, 2) k_gemm_dma(GemmParams p) {
     constexpr int DMA_STAGES = BM == 256 ? 3 : 2;
     constexpr int NWAVES = BM / 32;                          // 8 or 4
@@ -118,7 +122,8 @@ __global__ void __launch_bounds__(BM * 2, 2) k_gemm_dma(GemmParams p) {
         return;
     }
     __syncthreads();   // every wavefront is done reading the ring before the epilogue reuses it
-    gemm_epilogue(p, acc, smem_raw, lane, wv, wm, wn, m0, n0, tile_n);
+    if constexpr (EPI == EPI_GENERAL) gemm_epilogue(p, acc, smem_raw, lane, wv, wm, wn, m0, n0, tile_n);
+    else split_epilogue<EPI == EPI_SPLIT_OUT>(p, acc, smem_raw, lane, wv, wm, wn, m0, n0);
 }
 
 // The second half of a split-K contraction: out = epilogue(sum over the K parts, in order) with gemm_epilogue's arithmetic

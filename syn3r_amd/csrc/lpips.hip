@@ -13,6 +13,12 @@
 // in [0,1] and its gradient leaves in the same form.  Gradients travel through the fp16 convolutions multiplied by a loss
 // scale (they are ~1e-9 unscaled: below fp16's subnormal range) which k_lpips_image_bwd divides out.
 // All kernels are HBM-bound single passes.
+//
+// Split activations (the "fp16x2" mode of gs/lpips.py): a forward activation v is stored as the fp16 pair hi = half(v),
+// lo = half(v - float(hi)), channels-last [H*W, 2C] with the hi plane in channels [0, C) and the lo plane in [C, 2C); every kernel
+// below has a variant that reads such a tensor as float(hi) + float(lo) (exact in fp32).  What rounding an activation to ONE fp16
+// costs is not its 5e-4 of value but the ReLU masks it flips in the layers above, in which the gradient is discontinuous
+// (profiles/README.md, "LPIPS gradient error"); the gradients themselves stay single fp16 tensors [H*W, C] in both modes.
 #include "common.h"
 
 using namespace syn3r;
@@ -37,6 +43,26 @@ __global__ void __launch_bounds__(256) k_lpips_image(const float* __restrict__ i
     if (ch == 0) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[c] = (_Float16)(((2.0f * img[c * hw + p] - 1.0f) - kShift[c]) / kScale[c]);
+    }
+    *(half8*)(out + p * 64 + ch * 8) = v;
+}
+
+// the same with every channel as a pair: hi in channels 0..2, lo in 3..5 (conv1_1's weights are repeated there), 6..63 zero
+__global__ void __launch_bounds__(256) k_lpips_image_split(const float* __restrict__ img, long long hw, __half* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= hw * 8) return;
+    const long long p = i >> 3;
+    const int ch = (int)(i & 7);
+    half8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (_Float16)0.0f;
+    if (ch == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float f = ((2.0f * img[c * hw + p] - 1.0f) - kShift[c]) / kScale[c];
+            v[c] = (_Float16)f;
+            v[3 + c] = (_Float16)(f - (float)v[c]);
+        }
     }
     *(half8*)(out + p * 64 + ch * 8) = v;
 }
@@ -101,10 +127,95 @@ __global__ void __launch_bounds__(256) k_maxpool2_bwd(const __half* __restrict__
     *(half8*)(gx + q * C + ch * 8) = o;
 }
 
-// One LPIPS layer on two feature maps a, b [P, C] fp16 (C = 64 .. 512, a multiple of 64; LPR = C / 8 lanes per pixel):
+// The first maximum of a window in row-major order (torch's rule; k_maxpool2_bwd above spells out the same comparisons)
+__device__ __forceinline__ int first_max4(float va, float vb, float vc, float vd) {
+    int arg = 0;
+    float m = va;
+    if (vb > m) { m = vb; arg = 1; }
+    if (vc > m) { m = vc; arg = 2; }
+    if (vd > m) { m = vd; arg = 3; }
+    return arg;
+}
+
+// the four pairs of a window of a split map x [H,W,2C] at 8 channels: hi[k], lo[k], k = the window's cell in row-major order
+__device__ __forceinline__ void load_window_split(const __half* __restrict__ x, int W, int C, int yo, int xo, int ch, half8 (&hi)[4], half8 (&lo)[4]) {
+    const long long ld = 2ll * C;
+    const __half* s = x + ((long long)(2 * yo) * W + 2 * xo) * ld + ch * 8;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const __half* c = s + ((k >> 1) ? (long long)W * ld : 0) + ((k & 1) ? ld : 0);
+        hi[k] = *(const half8*)c;
+        lo[k] = *(const half8*)(c + C);
+    }
+}
+
+// 2x2 max pooling of a split map [H,W,2C] -> [H/2,W/2,2C]: the cells are compared as float(hi) + float(lo) and the winning PAIR
+// is copied (ties in the sum: the first cell, as the backward below and torch)
+__global__ void __launch_bounds__(256) k_maxpool2_split(const __half* __restrict__ x, int H, int W, int C, __half* __restrict__ y) {
+    const int Ho = H / 2, Wo = W / 2, C8 = C / 8;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)Ho * Wo * C8) return;
+    const int ch = (int)(i % C8);
+    const long long q = i / C8;
+    half8 hi[4], lo[4], oh, ol;
+    load_window_split(x, W, C, (int)(q / Wo), (int)(q % Wo), ch, hi, lo);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int arg = first_max4((float)hi[0][e] + (float)lo[0][e], (float)hi[1][e] + (float)lo[1][e], (float)hi[2][e] + (float)lo[2][e],
+                                   (float)hi[3][e] + (float)lo[3][e]);
+        oh[e] = arg == 0 ? hi[0][e] : (arg == 1 ? hi[1][e] : (arg == 2 ? hi[2][e] : hi[3][e]));
+        ol[e] = arg == 0 ? lo[0][e] : (arg == 1 ? lo[1][e] : (arg == 2 ? lo[2][e] : lo[3][e]));
+    }
+    *(half8*)(y + q * 2 * C + ch * 8) = oh;
+    *(half8*)(y + q * 2 * C + C + ch * 8) = ol;
+}
+
+// its backward: x the split input [H,W,2C], gy [H/2,W/2,C] and gx [H,W,C] plain fp16 gradients (k_maxpool2_bwd's rules)
+__global__ void __launch_bounds__(256) k_maxpool2_bwd_split(const __half* __restrict__ x, const __half* __restrict__ gy, int H, int W, int C,
+                                                           __half* __restrict__ gx) {
+    const int Ho = H / 2, Wo = W / 2, C8 = C / 8;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)H * W * C8) return;
+    const int ch = (int)(i % C8);
+    const long long q = i / C8;
+    const int xi = (int)(q % W), yi = (int)(q / W);
+    half8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = (_Float16)0.0f;
+    const int yo = yi >> 1, xo = xi >> 1;
+    if (yo < Ho && xo < Wo) {
+        half8 hi[4], lo[4];
+        load_window_split(x, W, C, yo, xo, ch, hi, lo);
+        const half8 g = *(const half8*)(gy + ((long long)yo * Wo + xo) * C + ch * 8);
+        const int me = (yi & 1) * 2 + (xi & 1);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int arg = first_max4((float)hi[0][e] + (float)lo[0][e], (float)hi[1][e] + (float)lo[1][e], (float)hi[2][e] + (float)lo[2][e],
+                                       (float)hi[3][e] + (float)lo[3][e]);
+            if (arg == me) o[e] = g[e];
+        }
+    }
+    *(half8*)(gx + q * C + ch * 8) = o;
+}
+
+// 8 channels of pixel p of a feature map as fp32: [P, C] fp16, or (SPLIT) the pair sum of [P, 2C]
+template <bool SPLIT>
+__device__ __forceinline__ void load_feat8(const __half* __restrict__ f, long long p, int C, int sub, float (&v)[8]) {
+    const __half* s = f + p * (SPLIT ? 2 * C : C) + sub * 8;
+    const half8 h = *(const half8*)s;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (float)h[e];
+    if constexpr (SPLIT) {
+        const half8 l = *(const half8*)(s + C);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += (float)l[e];
+    }
+}
+
+// One LPIPS layer on two feature maps a, b [P, C] fp16 (SPLIT: both [P, 2C] pairs) (C = 64 .. 512, a multiple of 64; LPR = C / 8 lanes per pixel):
 //   value_p = sum_c w_c (a_c / (|a| + eps) - b_c / (|b| + eps))^2 ;  the layer's term is mean_p value_p.
 // Forward: per-block partial sums (fixed order) -> k_lpips_finish adds them up.
-template <int LPR>
+template <int LPR, bool SPLIT>
 __global__ void __launch_bounds__(256) k_lpips_layer(const __half* __restrict__ a, const __half* __restrict__ b, const float* __restrict__ w,
                                                     long long P, float* __restrict__ partial) {
     constexpr int C = LPR * 8, PPB = 256 / LPR;       // pixels per block
@@ -112,16 +223,18 @@ __global__ void __launch_bounds__(256) k_lpips_layer(const __half* __restrict__ 
     const long long p = (long long)blockIdx.x * PPB + threadIdx.x / LPR;
     float val = 0.0f;
     if (p < P) {
-        const half8 av = *(const half8*)(a + p * C + sub * 8), bv = *(const half8*)(b + p * C + sub * 8);
+        float av[8], bv[8];
+        load_feat8<SPLIT>(a, p, C, sub, av);
+        load_feat8<SPLIT>(b, p, C, sub, bv);
         float sa = 0.0f, sb = 0.0f;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { sa += (float)av[e] * (float)av[e]; sb += (float)bv[e] * (float)bv[e]; }
+        for (int e = 0; e < 8; ++e) { sa += av[e] * av[e]; sb += bv[e] * bv[e]; }
 #pragma unroll
         for (int o = LPR / 2; o > 0; o >>= 1) { sa += __shfl_xor(sa, o, 64); sb += __shfl_xor(sb, o, 64); }
         const float ra = 1.0f / (sqrtf(sa) + 1e-10f), rb = 1.0f / (sqrtf(sb) + 1e-10f);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const float d = (float)av[e] * ra - (float)bv[e] * rb;
+            const float d = av[e] * ra - bv[e] * rb;
             val += w[sub * 8 + e] * d * d;
         }
     }
@@ -149,19 +262,21 @@ __global__ void __launch_bounds__(1024) k_lpips_finish(const float* __restrict__
 
 // Backward of one layer wrt a: with n = a / r, r = |a| + eps, e_c = 2 w_c (n_c - b_c / (|b| + eps)) / P,
 //   d value / d a_k = e_k / r - (sum_c e_c a_c) a_k / (r^2 |a|)
-// written (accumulate = 0) or added (1) to ga [P, C] fp16, multiplied by `gscale` (upstream gradient x loss scale); the sum
+// written (accumulate = 0) or added (1) to ga [P, C] fp16 (a single fp16 tensor in the SPLIT variant too), multiplied by `gscale` (upstream gradient x loss scale); the sum
 // is then masked by a > 0 (the feature map is the output of a ReLU: what leaves is the gradient wrt its pre-activation).
-template <int LPR>
+template <int LPR, bool SPLIT>
 __global__ void __launch_bounds__(256) k_lpips_layer_bwd(const __half* __restrict__ a, const __half* __restrict__ b, const float* __restrict__ w,
                                                         long long P, float gscale, int accumulate, __half* __restrict__ ga) {
     constexpr int C = LPR * 8, PPB = 256 / LPR;
     const int sub = threadIdx.x % LPR;
     const long long p = (long long)blockIdx.x * PPB + threadIdx.x / LPR;
     if (p >= P) return;                                  // (whole LPR-lane groups leave together: the shuffles below stay inside a group)
-    const half8 av = *(const half8*)(a + p * C + sub * 8), bv = *(const half8*)(b + p * C + sub * 8);
+    float av[8], bv[8];
+    load_feat8<SPLIT>(a, p, C, sub, av);
+    load_feat8<SPLIT>(b, p, C, sub, bv);
     float sa = 0.0f, sb = 0.0f;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { sa += (float)av[e] * (float)av[e]; sb += (float)bv[e] * (float)bv[e]; }
+    for (int e = 0; e < 8; ++e) { sa += av[e] * av[e]; sb += bv[e] * bv[e]; }
 #pragma unroll
     for (int o = LPR / 2; o > 0; o >>= 1) { sa += __shfl_xor(sa, o, 64); sb += __shfl_xor(sb, o, 64); }
     const float na = sqrtf(sa);
@@ -169,8 +284,8 @@ __global__ void __launch_bounds__(256) k_lpips_layer_bwd(const __half* __restric
     float ev[8], dot = 0.0f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        ev[e] = 2.0f * w[sub * 8 + e] * ((float)av[e] * ra - (float)bv[e] * rb) * gscale;
-        dot += ev[e] * (float)av[e];
+        ev[e] = 2.0f * w[sub * 8 + e] * (av[e] * ra - bv[e] * rb) * gscale;
+        dot += ev[e] * av[e];
     }
 #pragma unroll
     for (int o = LPR / 2; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
@@ -179,26 +294,62 @@ __global__ void __launch_bounds__(256) k_lpips_layer_bwd(const __half* __restric
     if (accumulate) o = *(const half8*)(ga + p * C + sub * 8);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const float g = ev[e] * ra - k2 * (float)av[e];
+        const float g = ev[e] * ra - k2 * av[e];
         // `a` is a post-ReLU activation: the total gradient passes its ReLU here (zero where the activation is zero).
         // The gradient carries the loss scale (1024 H W / P_k) and a factor 1 / |a|: a pixel whose feature norm is tiny would
         // overflow fp16 to inf and the backward convolutions would spread inf / NaN into the image gradient - saturate.
         const float t = fminf(fmaxf((accumulate ? (float)o[e] : 0.0f) + g, -65504.0f), 65504.0f);
-        o[e] = (float)av[e] > 0.0f ? (_Float16)t : (_Float16)0.0f;
+        o[e] = av[e] > 0.0f ? (_Float16)t : (_Float16)0.0f;
     }
     *(half8*)(ga + p * C + sub * 8) = o;
 }
 
-template <int LPR>
+template <int LPR, bool SPLIT>
 int launch_layer(const __half* a, const __half* b, const float* w, long long P, float* partial, hipStream_t stream) {
     const int blocks = (int)((P + 256 / LPR - 1) / (256 / LPR));
-    SYN3R_LAUNCH_NAMED("k_lpips_layer", k_lpips_layer<LPR>, dim3(blocks), dim3(256), 0, stream, a, b, w, P, partial);
+    SYN3R_LAUNCH_NAMED(SPLIT ? "k_lpips_layer_split" : "k_lpips_layer", (k_lpips_layer<LPR, SPLIT>), dim3(blocks), dim3(256), 0, stream, a, b, w, P, partial);
     return blocks;
 }
-template <int LPR>
+template <int LPR, bool SPLIT>
 void launch_layer_bwd(const __half* a, const __half* b, const float* w, long long P, float gscale, int acc, __half* ga, hipStream_t stream) {
     const int blocks = (int)((P + 256 / LPR - 1) / (256 / LPR));
-    SYN3R_LAUNCH_NAMED("k_lpips_layer_bwd", k_lpips_layer_bwd<LPR>, dim3(blocks), dim3(256), 0, stream, a, b, w, P, gscale, acc, ga);
+    SYN3R_LAUNCH_NAMED(SPLIT ? "k_lpips_layer_bwd_split" : "k_lpips_layer_bwd", (k_lpips_layer_bwd<LPR, SPLIT>), dim3(blocks), dim3(256), 0, stream, a, b, w, P,
+                       gscale, acc, ga);
+}
+
+template <bool SPLIT>
+int lpips_layer(const void* a, const void* b, const float* w, long long P, int C, int accumulate, float* value, void* ws, size_t ws_bytes,
+                void* stream_) {
+    SYN3R_REQUIRE(a && b && w && value && ws, "lpips_layer: null argument");
+    SYN3R_REQUIRE(P > 0 && P < (1ll << 31) && (C == 64 || C == 128 || C == 256 || C == 512), "lpips_layer: P=%lld, C=%d (64 / 128 / 256 / 512)", P, C);
+    SYN3R_REQUIRE(ws_bytes >= syn3r_lpips_layer_workspace_bytes(P, C), "lpips_layer: workspace too small");
+    hipStream_t stream = (hipStream_t)stream_;
+    float* partial = (float*)ws;
+    int blocks = 0;
+    const __half *ah = (const __half*)a, *bh = (const __half*)b;
+    if (C == 64) blocks = launch_layer<8, SPLIT>(ah, bh, w, P, partial, stream);
+    else if (C == 128) blocks = launch_layer<16, SPLIT>(ah, bh, w, P, partial, stream);
+    else if (C == 256) blocks = launch_layer<32, SPLIT>(ah, bh, w, P, partial, stream);
+    else blocks = launch_layer<64, SPLIT>(ah, bh, w, P, partial, stream);
+    SYN3R_LAUNCH(k_lpips_finish, dim3(1), dim3(1024), 0, stream, (const float*)partial, blocks, 1.0f / (float)P, accumulate, value);
+    SYN3R_LAUNCH_CHECK("lpips_layer launch");
+    return SYN3R_OK;
+}
+
+template <bool SPLIT>
+int lpips_layer_bwd(const void* a, const void* b, const float* w, long long P, int C, float gscale, int accumulate, void* grad_a, void* stream_) {
+    SYN3R_REQUIRE(a && b && w && grad_a, "lpips_layer_bwd: null argument");
+    SYN3R_REQUIRE(P > 0 && P < (1ll << 31) && (C == 64 || C == 128 || C == 256 || C == 512), "lpips_layer_bwd: P=%lld, C=%d", P, C);
+    hipStream_t stream = (hipStream_t)stream_;
+    const __half *ah = (const __half*)a, *bh = (const __half*)b;
+    __half* g = (__half*)grad_a;
+    const float gs = gscale / (float)P;
+    if (C == 64) launch_layer_bwd<8, SPLIT>(ah, bh, w, P, gs, accumulate, g, stream);
+    else if (C == 128) launch_layer_bwd<16, SPLIT>(ah, bh, w, P, gs, accumulate, g, stream);
+    else if (C == 256) launch_layer_bwd<32, SPLIT>(ah, bh, w, P, gs, accumulate, g, stream);
+    else launch_layer_bwd<64, SPLIT>(ah, bh, w, P, gs, accumulate, g, stream);
+    SYN3R_LAUNCH_CHECK("lpips_layer_bwd launch");
+    return SYN3R_OK;
 }
 
 }  // namespace
@@ -246,35 +397,47 @@ extern "C" size_t syn3r_lpips_layer_workspace_bytes(long long P, int C) {
 // value[0] (+)= mean_p sum_c w_c (a_c/(|a|+eps) - b_c/(|b|+eps))^2     a, b [P, C] fp16; w [C] fp32; value fp32 (device)
 extern "C" int syn3r_lpips_layer_f16(const void* a, const void* b, const float* w, long long P, int C, int accumulate, float* value,
                                      void* ws, size_t ws_bytes, void* stream_) {
-    SYN3R_REQUIRE(a && b && w && value && ws, "lpips_layer: null argument");
-    SYN3R_REQUIRE(P > 0 && P < (1ll << 31) && (C == 64 || C == 128 || C == 256 || C == 512), "lpips_layer: P=%lld, C=%d (64 / 128 / 256 / 512)", P, C);
-    SYN3R_REQUIRE(ws_bytes >= syn3r_lpips_layer_workspace_bytes(P, C), "lpips_layer: workspace too small");
-    hipStream_t stream = (hipStream_t)stream_;
-    float* partial = (float*)ws;
-    int blocks = 0;
-    const __half *ah = (const __half*)a, *bh = (const __half*)b;
-    if (C == 64) blocks = launch_layer<8>(ah, bh, w, P, partial, stream);
-    else if (C == 128) blocks = launch_layer<16>(ah, bh, w, P, partial, stream);
-    else if (C == 256) blocks = launch_layer<32>(ah, bh, w, P, partial, stream);
-    else blocks = launch_layer<64>(ah, bh, w, P, partial, stream);
-    SYN3R_LAUNCH(k_lpips_finish, dim3(1), dim3(1024), 0, stream, (const float*)partial, blocks, 1.0f / (float)P, accumulate, value);
-    SYN3R_LAUNCH_CHECK("lpips_layer launch");
-    return SYN3R_OK;
+    return lpips_layer<false>(a, b, w, P, C, accumulate, value, ws, ws_bytes, stream_);
 }
 
 // grad_a [P, C] fp16 (=, or += with accumulate) d(layer term)/d a * gscale
 extern "C" int syn3r_lpips_layer_bwd_f16(const void* a, const void* b, const float* w, long long P, int C, float gscale, int accumulate,
                                          void* grad_a, void* stream_) {
-    SYN3R_REQUIRE(a && b && w && grad_a, "lpips_layer_bwd: null argument");
-    SYN3R_REQUIRE(P > 0 && P < (1ll << 31) && (C == 64 || C == 128 || C == 256 || C == 512), "lpips_layer_bwd: P=%lld, C=%d", P, C);
-    hipStream_t stream = (hipStream_t)stream_;
-    const __half *ah = (const __half*)a, *bh = (const __half*)b;
-    __half* g = (__half*)grad_a;
-    const float gs = gscale / (float)P;
-    if (C == 64) launch_layer_bwd<8>(ah, bh, w, P, gs, accumulate, g, stream);
-    else if (C == 128) launch_layer_bwd<16>(ah, bh, w, P, gs, accumulate, g, stream);
-    else if (C == 256) launch_layer_bwd<32>(ah, bh, w, P, gs, accumulate, g, stream);
-    else launch_layer_bwd<64>(ah, bh, w, P, gs, accumulate, g, stream);
-    SYN3R_LAUNCH_CHECK("lpips_layer_bwd launch");
+    return lpips_layer_bwd<false>(a, b, w, P, C, gscale, accumulate, grad_a, stream_);
+}
+
+// ---- the split-activation entries: feature maps / activations are [.., 2C] pairs, gradients single fp16 tensors [.., C]
+extern "C" int syn3r_lpips_image_split_f16(const float* img, int H, int W, void* out, void* stream_) {
+    SYN3R_REQUIRE(img && out && SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W), "lpips_image_split: bad arguments H=%d W=%d", H, W);
+    const long long hw = (long long)H * W;
+    SYN3R_LAUNCH(k_lpips_image_split, dim3((unsigned)((hw * 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, img, hw, (__half*)out);
+    SYN3R_LAUNCH_CHECK("lpips_image_split launch");
     return SYN3R_OK;
+}
+
+extern "C" int syn3r_maxpool2_split_f16(const void* x, int H, int W, int C, void* y, void* stream_) {
+    SYN3R_REQUIRE(x && y && SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W) && H >= 2 && W >= 2 && SYN3R_DIM_OK(C) && C % 8 == 0, "maxpool2_split: bad arguments H=%d W=%d C=%d", H, W, C);
+    const long long n = (long long)(H / 2) * (W / 2) * (C / 8);
+    SYN3R_LAUNCH(k_maxpool2_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, (const __half*)x, H, W, C, (__half*)y);
+    SYN3R_LAUNCH_CHECK("maxpool2_split launch");
+    return SYN3R_OK;
+}
+
+extern "C" int syn3r_maxpool2_bwd_split_f16(const void* x, const void* gy, int H, int W, int C, void* gx, void* stream_) {
+    SYN3R_REQUIRE(x && gy && gx && SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W) && H >= 2 && W >= 2 && SYN3R_DIM_OK(C) && C % 8 == 0, "maxpool2_bwd_split: bad arguments");
+    const long long n = (long long)H * W * (C / 8);
+    SYN3R_LAUNCH(k_maxpool2_bwd_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, (const __half*)x, (const __half*)gy, H, W, C,
+                 (__half*)gx);
+    SYN3R_LAUNCH_CHECK("maxpool2_bwd_split launch");
+    return SYN3R_OK;
+}
+
+extern "C" int syn3r_lpips_layer_split_f16(const void* a, const void* b, const float* w, long long P, int C, int accumulate, float* value,
+                                           void* ws, size_t ws_bytes, void* stream_) {
+    return lpips_layer<true>(a, b, w, P, C, accumulate, value, ws, ws_bytes, stream_);
+}
+
+extern "C" int syn3r_lpips_layer_bwd_split_f16(const void* a, const void* b, const float* w, long long P, int C, float gscale, int accumulate,
+                                               void* grad_a, void* stream_) {
+    return lpips_layer_bwd<true>(a, b, w, P, C, gscale, accumulate, grad_a, stream_);
 }

@@ -13,6 +13,12 @@ Forward and backward run on the HIP operators: the 13 convolutions (and their ba
 transposed, flipped weights, with the ReLU mask of the layer below fused into its epilogue) on the implicit-GEMM kernel,
 pooling / normalised differences / image scaling in csrc/lpips.hip.  fp16 storage, fp32 accumulation; the backward carries
 a loss scale (the pixel gradients are ~1e-9, below fp16's range) that the last kernel divides out.
+
+`LPIPS(precision="fp16x2")` stores every forward activation of both branches as an fp16 PAIR hi + lo (>= 21 significant bits at
+the fp16 MFMA rate: the convolutions read the pair as 2C input channels under weights duplicated along Cin).  One fp16 per
+activation flips ReLU masks in the layers above, and the gradient is discontinuous in those: the image gradient of the default
+mode is 5-6 % away from float64, of this mode ~5e-4 (profiles/README.md, "LPIPS gradient error").  The gradient chain is fp16 in
+both modes.
 """
 from __future__ import annotations
 
@@ -36,6 +42,9 @@ _SLICES: Tuple[Tuple[Tuple[int, int, int], ...], ...] = (
 _CHNS = (64, 128, 256, 512, 512)
 
 
+PRECISIONS = ("fp16", "fp16x2")
+
+
 def _conv(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], Hh: int, Ww: int, relu: bool, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [H*W, Cin] fp16, w [Cout,3,3,Cin] -> [H*W, Cout] (syn3r_conv2d3x3_act_f16)."""
     dev = x.device
@@ -47,13 +56,32 @@ def _conv(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], Hh: int, 
     return out
 
 
+def _conv_split(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], Hh: int, Ww: int, relu: bool, split_out: bool,
+                mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """syn3r_conv2d3x3_split_f16.  Forward (`split_out`): x a split map [H*W, 2 Cin] (or the image tensor [H*W, 64]), w the
+    duplicated weights [Cout,3,3,x.shape[1]] -> the split map [H*W, 2 Cout].  Backward-data: x a gradient [H*W, Cout], w the
+    transposed, flipped weights -> the gradient [H*W, Cin], zeroed where the hi plane of the split map `mask` [H*W, 2 Cin] is <= 0."""
+    dev = x.device
+    Cin, Cout = x.shape[1], w.shape[0]
+    ld_out = 2 * Cout if split_out else Cout
+    out = torch.empty((Hh * Ww, ld_out), dtype=H16, device=dev)
+    rc = L.load().syn3r_conv2d3x3_split_f16(L.ptr(x), L.ptr(w), L.ptr(out), ld_out, L.ptr(b), 1 if relu else 0, 1 if split_out else 0, L.ptr(mask),
+                                            mask.shape[1] if mask is not None else 0, 1, Hh, Ww, Cin, Cout, L.stream_ptr(dev))
+    L.check(rc, "syn3r_conv2d3x3_split_f16")
+    return out
+
+
 class LPIPS:
     """`lpips.LPIPS(net='vgg', version='0.1')`: `loss = model(pred, target)` for [3,H,W] images in [0,1] (the package's
     `normalize=True` input convention); differentiable wrt `pred`."""
 
     LOSS_SCALE_PER_PIXEL = 1024.0       # backward loss scale = this x H x W (keeps the fp16 gradients of every layer in range)
 
-    def __init__(self):
+    def __init__(self, precision: str = "fp16"):
+        if precision not in PRECISIONS:
+            raise ValueError(f"LPIPS: precision must be one of {PRECISIONS}, got {precision!r}")
+        self.precision = precision
+        self.split = precision == "fp16x2"      # forward activations as fp16 pairs [H*W, 2C] (hi plane | lo plane)
         self.shapes: Dict[str, Tuple[int, ...]] = {}
         for s, convs in enumerate(_SLICES):
             for idx, cin, cout in convs:
@@ -62,7 +90,7 @@ class LPIPS:
         for k, c in enumerate(_CHNS):
             self.shapes[f"lin{k}.model.1.weight"] = (1, c, 1, 1)
         self.device: Optional[torch.device] = None
-        self._target_cache: Dict[int, tuple] = {}
+        self._target_cache: Dict[Tuple[int, str], tuple] = {}
 
     def parameter_shapes(self) -> Dict[str, Tuple[int, ...]]:
         return dict(self.shapes)
@@ -91,7 +119,15 @@ class LPIPS:
                 # backward-data = the forward kernel on W'[ci][ky][kx][co] = W[co][2-ky][2-kx][ci]
                 wb = torch.zeros((cin_p, 3, 3, cout), dtype=torch.float32, device=dev)
                 wb[:cin] = w.flip(2, 3).permute(1, 2, 3, 0)
-                fw.append((wf.to(H16).contiguous(), b))
+                wf = wf.to(H16)
+                if self.split:
+                    # a split input is 2 Cin channels [hi | lo]: the fp16 weights twice along Cin (the image tensor keeps its 64
+                    # channels: hi in 0..2, lo in 3..5)
+                    if cin < 64:
+                        wf[..., cin:2 * cin] = wf[..., :cin]
+                    else:
+                        wf = torch.cat([wf, wf], dim=3)
+                fw.append((wf.contiguous(), b))
                 bw.append(wb.to(H16).contiguous())
             self.fwd.append(fw)
             self.bwd.append(bw)
@@ -121,7 +157,10 @@ class LPIPS:
         lib = L.load()
         _, Hh, Ww = img.shape
         x = torch.empty((Hh * Ww, 64), dtype=H16, device=dev)
-        L.check(lib.syn3r_lpips_image_f16(L.ptr(img), Hh, Ww, L.ptr(x), L.stream_ptr(dev)), "syn3r_lpips_image_f16")
+        if self.split:
+            L.check(lib.syn3r_lpips_image_split_f16(L.ptr(img), Hh, Ww, L.ptr(x), L.stream_ptr(dev)), "syn3r_lpips_image_split_f16")
+        else:
+            L.check(lib.syn3r_lpips_image_f16(L.ptr(img), Hh, Ww, L.ptr(x), L.stream_ptr(dev)), "syn3r_lpips_image_f16")
         feats, acts, dims = [], [], []
         h, w_ = Hh, Ww
         for s, convs in enumerate(self.fwd):
@@ -129,12 +168,15 @@ class LPIPS:
                 if h < 2 or w_ < 2:
                     raise ValueError("LPIPS: image too small for the five VGG stages (needs >= 16 pixels per side)")
                 y = torch.empty(((h // 2) * (w_ // 2), x.shape[1]), dtype=H16, device=dev)
-                L.check(lib.syn3r_maxpool2_f16(L.ptr(x), h, w_, x.shape[1], L.ptr(y), L.stream_ptr(dev)), "syn3r_maxpool2_f16")
+                if self.split:
+                    L.check(lib.syn3r_maxpool2_split_f16(L.ptr(x), h, w_, x.shape[1] // 2, L.ptr(y), L.stream_ptr(dev)), "syn3r_maxpool2_split_f16")
+                else:
+                    L.check(lib.syn3r_maxpool2_f16(L.ptr(x), h, w_, x.shape[1], L.ptr(y), L.stream_ptr(dev)), "syn3r_maxpool2_f16")
                 h, w_ = h // 2, w_ // 2
                 x = y
             layer_acts = [x]                       # input of the slice (the image tensor or the pooled map)
             for wf, b in convs:
-                x = _conv(x, wf, b, h, w_, relu=True)
+                x = _conv_split(x, wf, b, h, w_, relu=True, split_out=True) if self.split else _conv(x, wf, b, h, w_, relu=True)
                 layer_acts.append(x)
             feats.append(x)
             dims.append((h, w_))
@@ -143,8 +185,9 @@ class LPIPS:
         return feats, acts, dims
 
     def _target_features(self, target: torch.Tensor):
-        """Feature maps of a ground-truth image, kept per tensor object (training compares many renders with few targets)."""
-        key = id(target)
+        """Feature maps of a ground-truth image, kept per tensor object and precision (training compares many renders with few
+        targets; the maps of the two precisions differ in layout)."""
+        key = (id(target), self.precision)
         hit = self._target_cache.get(key)
         if hit is not None and hit[0] is target and hit[1] == target._version:
             return hit[2]
@@ -173,11 +216,12 @@ class _LpipsFn(torch.autograd.Function):
         tfeats = model._target_features(target)
         value = torch.zeros(1, dtype=torch.float32, device=dev)
         for k in range(5):
-            P, C = feats[k].shape
+            P, C = feats[k].shape[0], _CHNS[k]
             ws = L.workspace(dev, lib.syn3r_lpips_layer_workspace_bytes(P, C), "lpips")
-            rc = lib.syn3r_lpips_layer_f16(L.ptr(feats[k]), L.ptr(tfeats[k]), L.ptr(model.lin[k]), P, C, 1 if k else 0, L.ptr(value),
-                                           L.ptr(ws), ws.numel(), L.stream_ptr(dev))
-            L.check(rc, "syn3r_lpips_layer_f16")
+            layer = lib.syn3r_lpips_layer_split_f16 if model.split else lib.syn3r_lpips_layer_f16
+            rc = layer(L.ptr(feats[k]), L.ptr(tfeats[k]), L.ptr(model.lin[k]), P, C, 1 if k else 0, L.ptr(value), L.ptr(ws), ws.numel(),
+                       L.stream_ptr(dev))
+            L.check(rc, "syn3r_lpips_layer_split_f16" if model.split else "syn3r_lpips_layer_f16")
         ctx.model, ctx.acts, ctx.dims, ctx.tfeats = model, acts, dims, tfeats
         ctx.shape = tuple(pred.shape)
         return value[0]
@@ -193,16 +237,16 @@ class _LpipsFn(torch.autograd.Function):
         up = 1.0                                       # the upstream scalar multiplies the result at the end, on the device (no host read)
         g = None                                       # gradient wrt the current slice's OUTPUT feature map (post-ReLU), x scale
         for k in range(4, -1, -1):
-            feat = acts[k][-1]
-            P, C = feat.shape
+            feat = acts[k][-1]                         # [P, C], or the split map [P, 2C]: the gradients are [P, C] in both modes
+            P, C = feat.shape[0], _CHNS[k]
             if g is None:
-                g = torch.empty_like(feat)
+                g = torch.empty((P, C), dtype=H16, device=dev)
                 acc = 0
             else:
                 acc = 1
-            rc = lib.syn3r_lpips_layer_bwd_f16(L.ptr(feat), L.ptr(tfeats[k]), L.ptr(model.lin[k]), P, C, up * scale, acc, L.ptr(g),
-                                               L.stream_ptr(dev))
-            L.check(rc, "syn3r_lpips_layer_bwd_f16")
+            layer_bwd = lib.syn3r_lpips_layer_bwd_split_f16 if model.split else lib.syn3r_lpips_layer_bwd_f16
+            rc = layer_bwd(L.ptr(feat), L.ptr(tfeats[k]), L.ptr(model.lin[k]), P, C, up * scale, acc, L.ptr(g), L.stream_ptr(dev))
+            L.check(rc, "syn3r_lpips_layer_bwd_split_f16" if model.split else "syn3r_lpips_layer_bwd_f16")
             h, w_ = dims[k]
             # back through the slice's convolutions: g is d/d(post-ReLU output of conv n) -> mask by (output > 0) -> backward-data
             # convolution -> d/d(input of conv n) = d/d(post-ReLU output of conv n-1), whose own mask is applied in the epilogue
@@ -211,13 +255,17 @@ class _LpipsFn(torch.autograd.Function):
             for n in range(nconv - 1, -1, -1):
                 below = acts[k][n]                     # input of conv n (post-ReLU of conv n-1, or the slice input)
                 mask = below if n > 0 else None        # the slice input is a pooled map / the image tensor: no ReLU of its own
-                g = _conv(g, model.bwd[k][n], None, h, w_, relu=False, mask=mask)
+                if model.split and mask is not None:   # the mask is the hi plane of the split map (row stride 2 Cin)
+                    g = _conv_split(g, model.bwd[k][n], None, h, w_, relu=False, split_out=False, mask=mask)
+                else:
+                    g = _conv(g, model.bwd[k][n], None, h, w_, relu=False, mask=mask)
             if k > 0:                                  # through the max-pool into the previous slice's output
                 ph, pw = dims[k - 1]
                 prev = acts[k - 1][-1]
-                gp = torch.empty_like(prev)
-                rc = lib.syn3r_maxpool2_bwd_f16(L.ptr(prev), L.ptr(g), ph, pw, prev.shape[1], L.ptr(gp), L.stream_ptr(dev))
-                L.check(rc, "syn3r_maxpool2_bwd_f16")
+                gp = torch.empty((ph * pw, _CHNS[k - 1]), dtype=H16, device=dev)
+                pool_bwd = lib.syn3r_maxpool2_bwd_split_f16 if model.split else lib.syn3r_maxpool2_bwd_f16
+                rc = pool_bwd(L.ptr(prev), L.ptr(g), ph, pw, _CHNS[k - 1], L.ptr(gp), L.stream_ptr(dev))
+                L.check(rc, "syn3r_maxpool2_bwd_split_f16" if model.split else "syn3r_maxpool2_bwd_f16")
                 g = gp                                 # the previous slice's layer term is ADDED to it at the top of the loop
         d_img = torch.empty((3, Hh, Ww), dtype=torch.float32, device=dev)
         L.check(lib.syn3r_lpips_image_bwd(L.ptr(g), Hh, Ww, float(scale), L.ptr(d_img), L.stream_ptr(dev)), "syn3r_lpips_image_bwd")

@@ -82,6 +82,10 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                     help="weight of the LPIPS term during refines (bash_scripts/batch_dl3dv_train.sh:84-87 passes 1); needs --lpips_weights")
     ap.add_argument("--lpips_weights", type=str, default=None,
                     help="local state_dict file of lpips.LPIPS(net='vgg') (torch.save format); the package's download is not reachable offline")
+    ap.add_argument("--lpips_precision", type=str, default="fp16", choices=("fp16", "fp16x2"),
+                    help="activation storage of the LPIPS model built from --lpips_weights: fp16 (default), or fp16x2 = every forward "
+                         "activation as an fp16 pair hi + lo (image gradient 5e-4 .. 9e-4 instead of 5-6 %% away from float64; the "
+                         "forward convolutions of the render double their K; gs/lpips.py)")
     ap.add_argument("--depth_weight", type=float, default=0.0,
                     help="weight of FSGS' depth-correlation term, 1 - Pearson(rendered depth, monocular prior), on every training step "
                          "(0 = off); views need a prior (Camera.depth_image or an injected GSTrainer.depth_net)")
@@ -233,7 +237,7 @@ def run_scene(name: str, args, device, factory: Callable) -> List[float]:
         trainer.lpips = sc["lpips"]
     elif getattr(args, "lpips_weights", None):
         from .gs.lpips import LPIPS
-        trainer.lpips = LPIPS().load_state_dict(torch.load(args.lpips_weights, map_location="cpu", weights_only=True), device)
+        trainer.lpips = LPIPS(precision=getattr(args, "lpips_precision", "fp16")).load_state_dict(torch.load(args.lpips_weights, map_location="cpu", weights_only=True), device)
     runner = DiffusionGS(trainer, num_input_views=sc["num_input_views"], save_dir=trainer.scene.model_path,
                          diffusion_type=args.diffusion_type, interp_type=args.interp_type, input_args=args,
                          svd_components=comps, num_inference_steps=args.num_inference_steps,

@@ -1,5 +1,6 @@
-"""Developer tool: LPIPS forward + backward at the bench resolution (1080p): ms per call and per kernel family."""
-import sys, time
+"""Developer tool: LPIPS forward + backward at the bench resolution (1080p): ms per call and per kernel family.
+python tools/lpips_bench.py [H W] [--precision fp16|fp16x2]"""
+import argparse, sys, time
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import torch
@@ -8,8 +9,14 @@ from syn3r_amd import _lib as L
 from syn3r_amd.gs.lpips import LPIPS
 
 dev = torch.device("cuda", 0)
-H, W = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (1080, 1920)
-m = LPIPS().init_random(dev)
+ap = argparse.ArgumentParser()
+ap.add_argument("size", type=int, nargs="*", default=[1080, 1920], help="H W")
+ap.add_argument("--precision", default="fp16", choices=("fp16", "fp16x2"))
+args = ap.parse_args()
+if len(args.size) != 2:
+    ap.error(f"size takes two numbers, H W (got {len(args.size)})")
+H, W = args.size
+m = LPIPS(precision=args.precision).init_random(dev)
 a = torch.rand(3, H, W, device=dev).requires_grad_(True)
 b = torch.rand(3, H, W, device=dev)
 for _ in range(2):
@@ -20,7 +27,7 @@ n = 5
 for _ in range(n):
     m(a, b).backward()
 torch.cuda.synchronize()
-print(f"LPIPS fwd+bwd at {W}x{H}: {1e3 * (time.perf_counter() - t0) / n:.2f} ms per call (target features cached)")
+print(f"LPIPS[{args.precision}] fwd+bwd at {W}x{H}: {1e3 * (time.perf_counter() - t0) / n:.2f} ms per call (target features cached)")
 with L.kernel_trace() as tr:
     m(a, b).backward()
     torch.cuda.synchronize()
