@@ -24,12 +24,33 @@ def _cloud(n, seed, strays=40):
     return pts
 
 
-@pytest.mark.parametrize("n,seed", [(30000, 0), (4097, 1), (13, 2)])
-def test_statistical_outlier_vs_oracle(gpu, n, seed):
+def _degenerate(kind, n):
+    """float64 clouds with zero extent on one or two axes, or on an integer lattice with duplicates (exact ties); the sizes
+    cross one and two box boundaries (1024 points) by a single point"""
+    g = np.random.default_rng(n)
+    if kind == "planar":
+        pts = g.random((n, 3))
+        pts[:, 2] = 0.5
+    elif kind == "lattice":
+        pts = g.integers(0, 12, (n, 3)).astype(np.float64)
+        pts[: n // 4] = pts[n // 4: 2 * (n // 4)]
+    else:                                                      # "line"
+        pts = np.zeros((n, 3))
+        pts[:, 0] = g.random(n)
+    return pts
+
+
+_P = pytest.param
+
+
+@pytest.mark.parametrize("kind,n,seed", [_P("clusters", 30000, 0, id="30000-0"), _P("clusters", 4097, 1, id="4097-1"),
+                                         _P("clusters", 13, 2, id="13-2"), ("planar", 1025, None), ("planar", 2049, None),
+                                         ("lattice", 2049, None), ("line", 1025, None)])
+def test_statistical_outlier_vs_oracle(gpu, kind, n, seed):
     """avg distance (k = 20, self included, float64) bit for bit against the k-d tree oracle; mean / std / threshold to
     float64 rounding of a different summation order; the SAME inliers."""
     from syn3r_amd import pcd as P
-    pts = _cloud(n, seed, strays=min(40, n // 4))
+    pts = _cloud(n, seed, strays=min(40, n // 4)) if kind == "clusters" else _degenerate(kind, n)
     keep, avg, stats = P.statistical_outlier(torch.from_numpy(pts).to(gpu), 20, 3.0)
     ind, oavg, (mean, std, thr) = PO.remove_statistical_outlier(pts, 20, 3.0)
     np.testing.assert_array_equal(avg.cpu().numpy(), oavg)

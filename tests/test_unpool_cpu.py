@@ -68,6 +68,12 @@ def test_graph_entry_rejects_bad_arguments(lib):
         assert call(n_=bad) == E_INVALID and f"n={bad}" in _err(lib)
     assert call(wsb=need - 1) == E_WORKSPACE and "workspace" in _err(lib)
     assert call(ws=p + 16) == E_INVALID and "workspace" in _err(lib) and "aligned" in _err(lib)
+    # the two older search entries answer a short workspace with E_INVALID (the header documents E_WORKSPACE for the graph and
+    # unpooling entries only)
+    assert lib.syn3r_knn3_mean_dist2(p, n, p, p, lib.syn3r_knn3_workspace_bytes(n) - 1, None) == E_INVALID and "workspace" in _err(lib)
+    need64 = lib.syn3r_pcd_outlier_workspace_bytes(n)
+    assert need64 > need
+    assert lib.syn3r_pcd_statistical_outlier(p, n, 20, 3.0, p, p, p, p, need64 - 1, None) == E_INVALID and "workspace" in _err(lib)
 
 
 def test_unpool_entries_reject_bad_arguments(lib):

@@ -1,5 +1,6 @@
 """Per-kernel comparison of two device assembly listings (developer tool): did a source change alter a kernel's code object?
-usage: hipcc <build flags> --cuda-device-only -S file.hip -o a.s   (both versions) ; python tools/isa_diff.py a.s b.s [name substring]
+usage: hipcc <build flags> --cuda-device-only -S file.hip -o a.s   (both versions) ; python tools/isa_diff.py a.s b.s [name substring] [OLD=NEW ...]
+OLD=NEW pairs a kernel that the change renamed: substrings of the mangled names in a.s and b.s, each matching exactly one kernel.
 Per kernel: IDENTICAL (same instruction stream), REGS (same opcode sequence, other register numbers / operands) or DIFFERENT; the
 instruction counts; vgpr / vgpr spill / sgpr spill / private segment from the metadata; for changed kernels whether the hand-written
 (inline asm) s_waitcnt immediates are the same multiset, else what each side has more of."""
@@ -27,7 +28,10 @@ def kernels(path):
 
 
 a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
-want = sys.argv[3] if len(sys.argv) > 3 else ""
+want = "".join(x for x in sys.argv[3:] if "=" not in x)
+for old, new in (x.split("=") for x in sys.argv[3:] if "=" in x):        # a renamed kernel goes by its old name on both sides
+    (o,), (n,) = [k for k in a if old in k], [k for k in b if new in k]
+    b = {(o if k == n else k): v for k, v in b.items()}
 names = [n for n in a if want in n] + [n for n in b if n not in a and want in n]
 try:
     pretty = dict(zip(names, subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")))
