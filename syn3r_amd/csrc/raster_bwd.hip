@@ -12,10 +12,10 @@
 // not after the published per-channel form: ONE running scalar per pixel stands for the colours / depth of everything behind
 // the current splat, the visit sums only RAW moments of G * dL/dalpha (the opacity, conic and pixel -> NDC factors, uniform
 // per splat, are applied once per Gaussian in k_preprocess_bwd), and a loss without a depth gradient runs an instance without
-// the depth terms (k_render_bwd's comment has the formulas; 125 -> 94 / 91 vector instructions per 128-pixel visit).
-// Per visited splat the up to 128 pixel contributions to 10 quantities are summed by
-// reduce10 (two half/row swap levels + DPP row rotates,
-// 30 VALU instructions), accumulated per (tile, splat) in LDS across the two wavefronts, and flushed with
+// the depth terms (k_render_bwd's comment has the formulas; 125 -> 94 / 91 vector instructions per 128-pixel visit in round 7,
+// 80 / 74 now).  Per visited splat the up to 128 pixel contributions to 10 quantities (9 without a depth gradient) are summed by
+// reduce_lanes (two half/row swap levels + transposing DPP row rotates, 21 / 19 VALU instructions; the x moments are formed
+// after the lane's two pixels, which share dx, are added), accumulated per (tile, splat) in LDS across the two wavefronts, and flushed with
 // ONE atomic per record slot onto a contiguous 64-byte gradient record (MI355X float atomics want
 // contiguous segments, MI355X_MICROARCH.md "Global float atomics").
 #include "common.h"
@@ -36,48 +36,68 @@ constexpr int kGradSlots = 16;
 // pixel); k_preprocess_bwd turns them into the gradients of the pixel mean and the conic.  Slot 9 (sum h) is dL/d(opacity x confidence).
 enum { G_R = 0, G_G, G_B, G_DEPTH, G_MX, G_MY, G_CXX, G_CXY, G_CYY, G_OP, G_USED = 10 };
 
-// Sum each of the 10 per-lane gradient terms over the 64 lanes.  Returns, on lane l with column c = l & 15 and 16-lane row q = l >> 4,
-// the total of value base(q) + c for c < 3 (even rows) / c < 2 (odd rows), base = 0, 3, 5, 8: row 0 owns values 0-2, row 1 values 3-4,
-// row 2 values 5-7, row 3 values 8-9 (reduce_slot below).
+// Sum the per-lane gradient terms over the 64 lanes: NV = 10 values, or 9 without a depth gradient (value 9 is the depth term).
+// Returns, on the lanes reduce_value names, a (partial) total of one value; every other lane holds a by-product.
 // Two transposing levels use gfx950's half / row swaps (v_permlane32_swap, v_permlane16_swap): one VALU instruction moves BOTH
-// directions of the exchange, so a level costs a swap and an add per surviving value and halves the number of live registers
-// (10 -> 5 -> 3; the odd one of the second level is swapped against a copy of itself).  The last four levels stay inside a 16-lane
-// row: v_add_f32 with a DPP row rotate, written as inline asm - through __builtin_amdgcn_update_dpp hipcc split the row_ror:1 step into
-// v_mov 0 + v_mov_dpp + v_add, and the 12-value form of rounds 2-5 swapped two zero pads through both levels: 38 instructions, now 29
-// (round 6; the kernel is bound by vector issue, 128 -> 119 instructions per visit).  No LDS-pipe ds_bpermute anywhere.
-__device__ __forceinline__ float row_sum16(float x) {
-    float y;
-    asm("v_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xf" : "=v"(y) : "v"(x));
-    asm("v_add_f32_dpp %0, %1, %1 row_ror:4 row_mask:0xf bank_mask:0xf" : "=v"(x) : "v"(y));
-    asm("v_add_f32_dpp %0, %1, %1 row_ror:2 row_mask:0xf bank_mask:0xf" : "=v"(y) : "v"(x));
-    asm("v_add_f32_dpp %0, %1, %1 row_ror:1 row_mask:0xf bank_mask:0xf" : "=v"(x) : "v"(y));
-    return x;
-}
-__device__ __forceinline__ float reduce10(float (&v)[10], int lane) {
+// directions of the exchange, so a level costs a swap and an add per PAIR of values and halves the number of live registers
+// (10 -> 5 -> 3).  A value without a partner is not swapped at all: its register stays with both halves (rows), each of which
+// sums its own lanes and hands in a partial total - the LDS atomic that follows adds the two.  That is value 4 at the first
+// level when value 9 is dead (NV = 9) and a[2] at the second level, always.  Who owns what after the two levels (row q = lane >> 4):
+//     b[0]: rows 0-3 own values 0, 3, 5, 8     b[1]: 1, 4, 6, 9 (NV = 9: 1, 4, 6, 4)     b[2]: 2, 2, 7, 7
+// The last four levels stay inside a 16-lane row and transpose as well: v_add_f32 with a DPP row rotate (lane c reads lane
+// c - n of its row) whose bank_mask keeps the banks of four lanes that a step must not write.
+//     row_ror:8   b[0] + its rotation into lanes 0-7, b[1] + its rotation into lanes 8-15 of ONE register t; b[2] whole (period 8)
+//     row_ror:4   t + its rotation is a complete sum over the lanes = c (mod 4) where lane c - 4 held the same value: banks 1 (b[0])
+//                 and 3 (b[1]); b[2] + its rotation goes into the free banks 0 and 2
+//     row_ror:2, row_ror:1 on t alone: lane 3 of a bank has read lanes 2, 1, 0 of the SAME bank only
+// so lane 3 of a row ends with the row's sum of b[2], lane 7 of b[0], lane 15 of b[1] (lane 11: b[2] again, not used): 7
+// instructions where three separate row sums and two selects took 14; 21 / 19 in all (rounds 6-7: 30, rounds 2-5: 38).
+// The DPP steps are ONE inline-asm block with their wait states written in it: a VALU write of a register needs two wait states
+// before a DPP read of it, and hipcc's hazard recogniser does not look into asm (the per-instruction asm of round 6 was safe only
+// where the scheduler happened to interleave three chains).  __builtin_amdgcn_update_dpp cannot say these steps: it is a MOVE whose
+// masked-off lanes take `old`, and hipcc folds move + add into v_add_f32_dpp only with the add's other operand in those lanes; a
+// step that puts one value's sum into some banks and KEEPS another value in the rest is an add with a tied destination - through
+// the builtin it would cost a select per merge (and round 6 saw the row_ror:1 step split even with full masks).  s_nop is not a
+// vector instruction: the SIMD issues another wavefront's meanwhile.  No LDS-pipe ds_bpermute anywhere.
+template <int NV>
+__device__ __forceinline__ float reduce_lanes(float (&v)[10]) {
+    static_assert(NV == 9 || NV == 10, "value 9 is the only optional one");
     float a[5];
 #pragma unroll
-    for (int k = 0; k < 5; ++k) {   // lanes 32-63 of v[k] <-> lanes 0-31 of v[k+5]: the lower half owns k, the upper k + 5
+    for (int k = 0; k < NV - 5; ++k) {   // lanes 32-63 of v[k] <-> lanes 0-31 of v[k+5]: the lower half owns k, the upper k + 5
         auto r = __builtin_amdgcn_permlane32_swap(__float_as_int(v[k]), __float_as_int(v[k + 5]), false, false);
         a[k] = __int_as_float(r[0]) + __int_as_float(r[1]);
     }
+    if (NV == 9) a[4] = v[4];            // both halves keep their own lanes' share of value 4
     float b[3];
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {   // odd 16-lane rows of a[k] <-> even rows of a[k+3]: even rows own k, odd rows k + 3
+    for (int k = 0; k < 2; ++k) {        // odd 16-lane rows of a[k] <-> even rows of a[k+3]: even rows own k, odd rows k + 3
         auto r = __builtin_amdgcn_permlane16_swap(__float_as_int(a[k]), __float_as_int(a[k + 3]), false, false);
         b[k] = __int_as_float(r[0]) + __int_as_float(r[1]);
     }
-    {                                // a[2] against itself: both rows of a pair get the pair's total (the odd rows' copy is not stored)
-        auto r = __builtin_amdgcn_permlane16_swap(__float_as_int(a[2]), __float_as_int(a[2]), false, false);
-        b[2] = __int_as_float(r[0]) + __int_as_float(r[1]);
-    }
-    b[0] = row_sum16(b[0]); b[1] = row_sum16(b[1]); b[2] = row_sum16(b[2]);
-    const int c = lane & 15;
-    return c == 0 ? b[0] : (c == 1 ? b[1] : b[2]);
+    b[2] = a[2];                         // both rows of a pair keep their own lanes' share
+    asm("s_nop 1\n\t"                                                                    // b[] are fresh VALU results
+        "v_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"             // lanes 0-7:  b0[c] + b0[c + 8]
+        "v_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"             // lanes 8-15: b1[c] + b1[c - 8]
+        "v_add_f32_dpp %2, %2, %2 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"                                                                    // (one instruction + one state since %0 was written)
+        "v_add_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"             // banks 1, 3
+        "v_add_f32_dpp %0, %2, %2 row_ror:4 row_mask:0xf bank_mask:0x5\n\t"             // banks 0, 2
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_ror:2 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_ror:1 row_mask:0xf bank_mask:0xf"
+        : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]));
+    return b[0];
 }
-// the gradient slot reduce10's return value belongs to on this lane, or -1
-__device__ __forceinline__ int reduce_slot(int lane) {
+// the VALUE (index into reduce_lanes' argument) whose partial total this lane holds afterwards, or -1
+template <int NV>
+__device__ __forceinline__ int reduce_value(int lane) {
     const int c = lane & 15, q = lane >> 4;
-    return c < ((q & 1) ? 2 : 3) ? ((5 * q + 1) >> 1) + c : -1;
+    if (c == 7) return ((5 * q + 1) >> 1);                       // b[0]: 0, 3, 5, 8
+    if (c == 15) return (NV == 9 && q == 3) ? 4 : ((5 * q + 1) >> 1) + 1;   // b[1]: 1, 4, 6, 9
+    if (c == 3) return q < 2 ? 2 : 7;                            // b[2]
+    return -1;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -89,7 +109,7 @@ __device__ __forceinline__ int reduce_slot(int lane) {
 // v_pk_mul_f32 / v_pk_add_f32: two pixels per VALU issue); only exp, rcp, min and the compares stay one per pixel.
 // The kernel is VALU-bound (rocprofv3 round 1: 78 % VALU issue): against one pixel per lane this halves the issue
 // slots of the chain-rule arithmetic and halves the number of cross-lane reductions per pixel (the two pixels of a
-// lane are added before reduce10).  The visit list is per wavefront, i.e. per 16 x 8 half: coarser than the former
+// lane are added before reduce_lanes).  The visit list is per wavefront, i.e. per 16 x 8 half: coarser than the former
 // 8 x 8 quadrant (more visits pass the reach test), but a visit now carries 128 pixels for ~0.6 of the issue cost
 // of two 64-pixel visits.  Splats are staged 128 at a time (one per thread).
 typedef float f2 __attribute__((ext_vector_type(2)));
@@ -171,7 +191,15 @@ __global__ void __launch_bounds__(kBwdThreads) k_render_bwd(
     const f2 tail = T_final * (gA - (bg0 * gr + bg1 * gg + bg2 * gb));
     f2 R = tail;                          // tail minus the weighted gradient-colour products of everything behind the current splat
 
-    const int rslot = reduce_slot(lane);
+    // reduce_lanes' argument order: the depth term last, so that it is the value the colour-only instance leaves out
+    constexpr int NV = HAS_DEPTH_GRAD ? 10 : 9;
+    const int rval = reduce_value<NV>(lane);
+    int rslot = -1;                       // the gradient slot this lane's total belongs to
+    {
+        const int order[10] = {G_R, G_G, G_B, G_MX, G_MY, G_CXX, G_CXY, G_CYY, G_OP, G_DEPTH};
+#pragma unroll
+        for (int k = 0; k < 10; ++k) rslot = rval == k ? order[k] : rslot;
+    }
     int todo = total;
     // The records of round rd + 1 are requested (list entry, then the 48-byte record: two dependent global loads)
     // BEFORE round rd is processed and land in registers meanwhile: the gather latency is off the critical path.
@@ -224,7 +252,8 @@ __global__ void __launch_bounds__(kBwdThreads) k_render_bwd(
             const f2 dy = splat2(a.y) - fy;
             const float hxx = -0.5f * a.z * dx * dx, bxy = a.w * dx;
             const f2 power = (-0.5f * b.x) * dy * dy - bxy * dy + hxx;
-            f2 G = (f2){__expf(power.x), __expf(power.y)};
+            const f2 pl = power * kLog2e;       // __expf's own multiply, as one packed instruction for the pair: the same bits
+            f2 G = (f2){__builtin_amdgcn_exp2f(pl.x), __builtin_amdgcn_exp2f(pl.y)};
             const f2 araw = b.y * G;
             const bool act0 = (contributor < lc0) && (power.x <= 0.0f) && (fminf(kAlphaMax, araw.x) >= kAlphaMin);
             const bool act1 = (contributor < lc1) && (power.y <= 0.0f) && (fminf(kAlphaMax, araw.y) >= kAlphaMin);
@@ -250,20 +279,21 @@ __global__ void __launch_bounds__(kBwdThreads) k_render_bwd(
             R = R - wgt * d;
             // raw moments of h = G dL/dalpha; opacity, conic and the pixel -> NDC factors wait for k_preprocess_bwd
             const f2 h = G * dL_da;
-            const f2 hx = h * dx, hy = h * dy;
-            f2 w[10];
-            w[G_R] = wgt * gr; w[G_G] = wgt * gg; w[G_B] = wgt * gb;
-            w[G_DEPTH] = HAS_DEPTH_GRAD ? wgt * gD : splat2(0.f);
-            w[G_MX] = hx;
-            w[G_MY] = hy;
-            w[G_CXX] = hx * dx;
-            w[G_CXY] = hx * dy;
-            w[G_CYY] = hy * dy;
-            w[G_OP] = h;
+            // the two pixels of a lane share dx: the x moments are formed from the pair's sums
+            const f2 hy = h * dy, hyy = hy * dy;
+            const f2 wr = wgt * gr, wg = wgt * gg, wb = wgt * gb;
+            const float Sh = h.x + h.y, Sy = hy.x + hy.y, Sx = Sh * dx;
             float v[10];
-#pragma unroll
-            for (int k = 0; k < 10; ++k) v[k] = w[k].x + w[k].y;
-            const float s = reduce10(v, lane);
+            v[0] = wr.x + wr.y; v[1] = wg.x + wg.y; v[2] = wb.x + wb.y;
+            v[3] = Sx;
+            v[4] = Sy;
+            v[5] = Sx * dx;
+            v[6] = Sy * dx;
+            v[7] = hyy.x + hyy.y;
+            v[8] = Sh;
+            v[9] = 0.0f;
+            if constexpr (HAS_DEPTH_GRAD) { const f2 wd = wgt * gD; v[9] = wd.x + wd.y; }
+            const float s = reduce_lanes<NV>(v);
             if (rslot >= 0) atomicAdd(&sacc[j * kGradSlots + rslot], s);   // LDS, 10 banks
           }
         }

@@ -24,6 +24,7 @@ constexpr float kLowPass = 0.3f;                // added to the 2D covariance di
 constexpr float kAlphaMin = 1.0f / 255.0f;
 constexpr float kAlphaMax = 0.99f;
 constexpr float kTransmittanceMin = 1e-4f;
+constexpr float kLog2e = 1.4426950408889634f;  // the blend kernels' exp(x) is v_exp_f32 of x * log2(e), as __expf forms it (0x3fb8aa3b)
 
 // Per-Gaussian screen-space record gathered by the blend kernels: 3 x 16-byte loads.
 struct alignas(16) Splat {
