@@ -249,7 +249,7 @@ int syn3r_raster_preprocess_raw(int N, int sh_degree, int sh_coeffs, const float
  * result of the published "duplicate (tile<<32 | depth) keys, sort, find tile
  * ranges", built here by filtering the Gaussians through super-tiles of 4x4 or
  * 8x8 tiles (whose short lists are sorted by (depth bits, index) in LDS) and then
- * per tile (csrc/raster_fwd.hip; images with more than 512 super-tiles take the
+ * per tile (csrc/raster_bin.hip; images with more than 512 super-tiles take the
  * argsort + pair sort) - then the blend.  P is the pair CAPACITY of
  * `binning` (an estimate is fine: a list that does not fit sets the overflow
  * flag in the geometry header and is truncated, never written past the buffer).

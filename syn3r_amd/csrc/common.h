@@ -142,6 +142,37 @@ __device__ __forceinline__ int wave_sum_i(int v) {
     return v;
 }
 
+// Inclusive prefix sum over the 64 lanes of a wavefront (1-D blocks: lane = threadIdx.x & 63).
+__device__ __forceinline__ unsigned wave_scan_incl(unsigned v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(v, o, 64); if (lane >= o) v += t; }
+    return v;
+}
+// Exclusive scan of one value per thread over a block of WAVES wavefronts; `total` = the block's sum on every thread.
+// Every thread of the block must call it; `smem` may be reused right after it returns.
+template <int WAVES>
+__device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned* smem /*[WAVES + 1]*/, unsigned& total) {
+    static_assert(WAVES >= 1 && WAVES <= 64, "one wavefront scans the wave totals");
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned incl = wave_scan_incl(v);
+    if (lane == 63) smem[wv] = incl;
+    __syncthreads();
+    if (wv == 0) {
+        const unsigned s = lane < WAVES ? smem[lane] : 0u;
+        unsigned si = s;
+#pragma unroll
+        for (int o = 1; o < WAVES; o <<= 1) { const unsigned t = __shfl_up(si, o, 64); if (lane >= o) si += t; }
+        if (lane < WAVES) smem[lane] = si - s;      // exclusive wave offsets
+        if (lane == WAVES - 1) smem[WAVES] = si;    // block total
+    }
+    __syncthreads();
+    const unsigned res = incl - v + smem[wv];
+    total = smem[WAVES];
+    __syncthreads();
+    return res;
+}
+
 // erf with |error| <= 1.5e-7 (Abramowitz & Stegun 7.1.26): ~14 VALU operations instead of libm's ~40.
 // Used by the GELU of the GEGLU gate, whose result is rounded to fp16 (relative step 4.9e-4).
 __device__ __forceinline__ float fast_erff(float x) {

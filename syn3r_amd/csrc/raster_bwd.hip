@@ -23,11 +23,6 @@
 
 using namespace syn3r;
 
-namespace syn3r {
-void raster_fill_camera(Camera& cam, const float* view, const float* proj, const float* campos, float tanfovx,
-                        float tanfovy, int H, int W);
-}
-
 namespace {
 
 // 64-byte per-Gaussian gradient record written by the blend backward
@@ -112,16 +107,10 @@ __device__ __forceinline__ int reduce_value(int lane) {
 // lane are added before reduce_lanes).  The visit list is per wavefront, i.e. per 16 x 8 half: coarser than the former
 // 8 x 8 quadrant (more visits pass the reach test), but a visit now carries 128 pixels for ~0.6 of the issue cost
 // of two 64-pixel visits.  Splats are staged 128 at a time (one per thread).
-typedef float f2 __attribute__((ext_vector_type(2)));
-constexpr int kBwdThreads = 128;
-#ifdef SYN3R_RASTER_STATS      // developer build: [0] lane tests, [1] wavefront visits, [2] visits with an active pixel, [3] active pixels
+constexpr int kBwdThreads = kBlendThreads;
+#ifdef SYN3R_RASTER_STATS
 __device__ unsigned long long g_bwd_stats[4];
-#define BSTAT(i, n) do { if (lane == 0) atomicAdd(&g_bwd_stats[i], (unsigned long long)(n)); } while (0)
-#else
-#define BSTAT(i, n)
 #endif
-
-__device__ __forceinline__ f2 splat2(float s) { return (f2){s, s}; }
 
 // Per visit (splat i, T_i the transmittance in front of it, a_i its alpha, w_i = a_i T_i its blend weight, g the pixel's
 // output gradients):
@@ -145,15 +134,11 @@ __global__ void __launch_bounds__(kBwdThreads) k_render_bwd(
     __shared__ unsigned sid[kBwdThreads];
     __shared__ float sacc[kBwdThreads * kGradSlots];   // per-round gradient records: the 2 wavefronts meet here first
     const unsigned tile = tile_order ? tile_order[blockIdx.x] : xcd_remap(blockIdx.x, (unsigned)(gx * gy));
-    const int tx = tile % gx, ty = tile / gx;
     const int wq = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int lx = lane & 15, ly = wq * 8 + (lane >> 4);
-    const int px = tx * kTileX + lx, py0 = ty * kTileY + ly, py1 = py0 + 4;
-    const bool in0 = px < W && py0 < H, in1 = px < W && py1 < H;
-    const float fx = (float)px;
-    const f2 fy = (f2){(float)py0, (float)py1};
+    const BlendFrame f = blend_frame(tile, wq, lane, H, W, gx);
+    const bool in0 = f.in0, in1 = f.in1;
     const uint2 range = ranges[tile];
-    const size_t hw = (size_t)H * W, pix0 = (size_t)py0 * W + px, pix1 = (size_t)py1 * W + px;
+    const size_t hw = (size_t)H * W, pix0 = (size_t)f.py0 * W + f.px, pix1 = (size_t)f.py1 * W + f.px;
 
     const f2 T_final = (f2){in0 ? final_T[pix0] : 0.0f, in1 ? final_T[pix1] : 0.0f};
     f2 T = T_final;
@@ -174,8 +159,7 @@ __global__ void __launch_bounds__(kBwdThreads) k_render_bwd(
     __syncthreads();
     const int total = min(s_live, (int)(range.y - range.x));
     const int rounds = (total + kBwdThreads - 1) / kBwdThreads;
-    const float sx0 = (float)(tx * kTileX), sx1 = sx0 + 15.0f;
-    const float sy0 = (float)(ty * kTileY + wq * 8), sy1 = sy0 + 7.0f;
+    const BlendHalf hf = blend_half(tile, wq, gx);
     f2 gr = splat2(0.f), gg = splat2(0.f), gb = splat2(0.f), gD = splat2(0.f), gA = splat2(0.f);
     if (in0) {
         gr.x = dL_dcolor[pix0]; gg.x = dL_dcolor[hw + pix0]; gb.x = dL_dcolor[2 * hw + pix0];
@@ -219,9 +203,7 @@ __global__ void __launch_bounds__(kBwdThreads) k_render_bwd(
     for (int rd = 0; rd < rounds; ++rd, todo -= kBwdThreads) {
         __syncthreads();
         if (have) {
-            sm[threadIdx.x * 3 + 0] = n0;
-            sm[threadIdx.x * 3 + 1] = n1;
-            sm[threadIdx.x * 3 + 2] = n2;
+            stage_splat(sm, threadIdx.x, n0, n1, n2);
             sid[threadIdx.x] = ngid;
         }
         fetch(rd + 1);
@@ -236,31 +218,25 @@ __global__ void __launch_bounds__(kBwdThreads) k_render_bwd(
           bool hit = false;
           if (c0 + lane < cnt) {
               const float4 ta = sm[(c0 + lane) * 3], tb = sm[(c0 + lane) * 3 + 1];
-              hit = splat_reaches_rect(ta.x, ta.y, ta.z, ta.w, tb.x, tb.y, sx0, sx1, sy0, sy1) &&
+              hit = splat_reaches_rect(ta.x, ta.y, ta.z, ta.w, tb.x, tb.y, hf.sx0, hf.sx1, hf.sy0, hf.sy1) &&
                     (total - 1 - (rd * kBwdThreads + c0 + lane)) < wave_live;
           }
           unsigned long long vm = __ballot(hit);
-          BSTAT(0, min(64, cnt - c0));
-          BSTAT(1, __popcll(vm));
+          RASTER_STAT(g_bwd_stats, 0, min(64, cnt - c0));
+          RASTER_STAT(g_bwd_stats, 1, __popcll(vm));
           while (vm) {
             const int j = c0 + (int)__builtin_ctzll(vm);
             vm &= vm - 1;
             const int contributor = total - 1 - (rd * kBwdThreads + j);
             const float4 a = sm[j * 3], b = sm[j * 3 + 1], c = sm[j * 3 + 2];
-            // a = (x, y, cxx, cxy)  b = (cyy, opacity, r, g)  c = (b, depth, -, -)
-            const float dx = a.x - fx;
-            const f2 dy = splat2(a.y) - fy;
-            const float hxx = -0.5f * a.z * dx * dx, bxy = a.w * dx;
-            const f2 power = (-0.5f * b.x) * dy * dy - bxy * dy + hxx;
-            const f2 pl = power * kLog2e;       // __expf's own multiply, as one packed instruction for the pair: the same bits
-            f2 G = (f2){__builtin_amdgcn_exp2f(pl.x), __builtin_amdgcn_exp2f(pl.y)};
-            const f2 araw = b.y * G;
+            const BlendEval e = blend_eval(a, b, f);
+            const float dx = e.dx;
+            const f2 dy = e.dy, power = e.power, araw = b.y * e.G;
+            f2 G = e.G;
             const bool act0 = (contributor < lc0) && (power.x <= 0.0f) && (fminf(kAlphaMax, araw.x) >= kAlphaMin);
             const bool act1 = (contributor < lc1) && (power.y <= 0.0f) && (fminf(kAlphaMax, araw.y) >= kAlphaMin);
             if (__ballot(act0 || act1) == 0ull) continue;   // wave-uniform
-#ifdef SYN3R_RASTER_STATS
-            BSTAT(2, 1); BSTAT(3, __popcll(__ballot(act0)) + __popcll(__ballot(act1)));
-#endif
+            RASTER_STAT(g_bwd_stats, 2, 1); RASTER_STAT(g_bwd_stats, 3, __popcll(__ballot(act0)) + __popcll(__ballot(act1)));
             // Branch-free: a pixel that does not take this splat blends it with alpha = 0 and G = 0, which is an exact
             // no-op on its running state (T * rcp(1) = T, R - 0 * d = R) and makes every gradient term an exact
             // zero - no EXEC-masked region.
@@ -310,13 +286,6 @@ __global__ void __launch_bounds__(kBwdThreads) k_render_bwd(
     }
 }
 
-constexpr float SH_C0 = 0.28209479177387814f;
-constexpr float SH_C1 = 0.4886025119029199f;
-__constant__ float B_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                              -1.0925484305920792f, 0.5462742152960396f};
-__constant__ float B_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
-                              -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
-
 struct F3 { float x, y, z; };
 __device__ __forceinline__ F3 f3(float x, float y, float z) { return {x, y, z}; }
 __device__ __forceinline__ F3 operator*(float s, F3 a) { return {s * a.x, s * a.y, s * a.z}; }
@@ -352,25 +321,25 @@ __device__ __forceinline__ F3 sh_backward(int D, int M, F3 pos, const float* cam
         dx = -SH_C1 * c(3); dy = -SH_C1 * c(1); dz = SH_C1 * c(2);
         if (D > 1) {
             float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-            put(4, B_C2[0] * xy); put(5, B_C2[1] * yz); put(6, B_C2[2] * (2.f * zz - xx - yy));
-            put(7, B_C2[3] * xz); put(8, B_C2[4] * (xx - yy));
-            dx = dx + (B_C2[0] * y) * c(4) + (B_C2[2] * 2.f * -x) * c(6) + (B_C2[3] * z) * c(7) + (B_C2[4] * 2.f * x) * c(8);
-            dy = dy + (B_C2[0] * x) * c(4) + (B_C2[1] * z) * c(5) + (B_C2[2] * 2.f * -y) * c(6) + (B_C2[4] * 2.f * -y) * c(8);
-            dz = dz + (B_C2[1] * y) * c(5) + (B_C2[2] * 2.f * 2.f * z) * c(6) + (B_C2[3] * x) * c(7);
+            put(4, SH_C2[0] * xy); put(5, SH_C2[1] * yz); put(6, SH_C2[2] * (2.f * zz - xx - yy));
+            put(7, SH_C2[3] * xz); put(8, SH_C2[4] * (xx - yy));
+            dx = dx + (SH_C2[0] * y) * c(4) + (SH_C2[2] * 2.f * -x) * c(6) + (SH_C2[3] * z) * c(7) + (SH_C2[4] * 2.f * x) * c(8);
+            dy = dy + (SH_C2[0] * x) * c(4) + (SH_C2[1] * z) * c(5) + (SH_C2[2] * 2.f * -y) * c(6) + (SH_C2[4] * 2.f * -y) * c(8);
+            dz = dz + (SH_C2[1] * y) * c(5) + (SH_C2[2] * 2.f * 2.f * z) * c(6) + (SH_C2[3] * x) * c(7);
             if (D > 2) {
-                put(9, B_C3[0] * y * (3.f * xx - yy)); put(10, B_C3[1] * xy * z);
-                put(11, B_C3[2] * y * (4.f * zz - xx - yy)); put(12, B_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy));
-                put(13, B_C3[4] * x * (4.f * zz - xx - yy)); put(14, B_C3[5] * z * (xx - yy));
-                put(15, B_C3[6] * x * (xx - 3.f * yy));
-                dx = dx + (B_C3[0] * 3.f * 2.f * xy) * c(9) + (B_C3[1] * yz) * c(10) + (B_C3[2] * -2.f * xy) * c(11) +
-                     (B_C3[3] * -3.f * 2.f * xz) * c(12) + (B_C3[4] * (-3.f * xx + 4.f * zz - yy)) * c(13) +
-                     (B_C3[5] * 2.f * xz) * c(14) + (B_C3[6] * 3.f * (xx - yy)) * c(15);
-                dy = dy + (B_C3[0] * 3.f * (xx - yy)) * c(9) + (B_C3[1] * xz) * c(10) +
-                     (B_C3[2] * (-3.f * yy + 4.f * zz - xx)) * c(11) + (B_C3[3] * -3.f * 2.f * yz) * c(12) +
-                     (B_C3[4] * -2.f * xy) * c(13) + (B_C3[5] * -2.f * yz) * c(14) + (B_C3[6] * -3.f * 2.f * xy) * c(15);
-                dz = dz + (B_C3[1] * xy) * c(10) + (B_C3[2] * 4.f * 2.f * yz) * c(11) +
-                     (B_C3[3] * 3.f * (2.f * zz - xx - yy)) * c(12) + (B_C3[4] * 4.f * 2.f * xz) * c(13) +
-                     (B_C3[5] * (xx - yy)) * c(14);
+                put(9, SH_C3[0] * y * (3.f * xx - yy)); put(10, SH_C3[1] * xy * z);
+                put(11, SH_C3[2] * y * (4.f * zz - xx - yy)); put(12, SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy));
+                put(13, SH_C3[4] * x * (4.f * zz - xx - yy)); put(14, SH_C3[5] * z * (xx - yy));
+                put(15, SH_C3[6] * x * (xx - 3.f * yy));
+                dx = dx + (SH_C3[0] * 3.f * 2.f * xy) * c(9) + (SH_C3[1] * yz) * c(10) + (SH_C3[2] * -2.f * xy) * c(11) +
+                     (SH_C3[3] * -3.f * 2.f * xz) * c(12) + (SH_C3[4] * (-3.f * xx + 4.f * zz - yy)) * c(13) +
+                     (SH_C3[5] * 2.f * xz) * c(14) + (SH_C3[6] * 3.f * (xx - yy)) * c(15);
+                dy = dy + (SH_C3[0] * 3.f * (xx - yy)) * c(9) + (SH_C3[1] * xz) * c(10) +
+                     (SH_C3[2] * (-3.f * yy + 4.f * zz - xx)) * c(11) + (SH_C3[3] * -3.f * 2.f * yz) * c(12) +
+                     (SH_C3[4] * -2.f * xy) * c(13) + (SH_C3[5] * -2.f * yz) * c(14) + (SH_C3[6] * -3.f * 2.f * xy) * c(15);
+                dz = dz + (SH_C3[1] * xy) * c(10) + (SH_C3[2] * 4.f * 2.f * yz) * c(11) +
+                     (SH_C3[3] * 3.f * (2.f * zz - xx - yy)) * c(12) + (SH_C3[4] * 4.f * 2.f * xz) * c(13) +
+                     (SH_C3[5] * (xx - yy)) * c(14);
             }
         }
     }
@@ -445,15 +414,11 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(
     float c0 = cv[0], c1 = cv[1], c2 = cv[2], c3 = cv[3], c4 = cv[4], c5 = cv[5];
     float limx = kFovGuard * cam.tanfovx, limy = kFovGuard * cam.tanfovy;
     float txtz = t.x / t.z, tytz = t.y / t.z;
-    float tx = fminf(limx, fmaxf(-limx, txtz)) * t.z;
-    float ty = fminf(limy, fmaxf(-limy, tytz)) * t.z;
     float x_mul = (txtz < -limx || txtz > limx) ? 0.0f : 1.0f;
     float y_mul = (tytz < -limy || tytz > limy) ? 0.0f : 1.0f;
-    float J00 = cam.focal_x / t.z, J02 = -(cam.focal_x * tx) / (t.z * t.z);
-    float J11 = cam.focal_y / t.z, J12 = -(cam.focal_y * ty) / (t.z * t.z);
+    const EwaRows w = ewa_rows(cam, t.x, t.y, t.z);
+    const float tx = w.tx, ty = w.ty, T00 = w.T00, T01 = w.T01, T02 = w.T02, T10 = w.T10, T11 = w.T11, T12 = w.T12;
     float W00 = v[0], W01 = v[4], W02 = v[8], W10 = v[1], W11 = v[5], W12 = v[9], W20 = v[2], W21 = v[6], W22 = v[10];
-    float T00 = J00 * W00 + J02 * W20, T01 = J00 * W01 + J02 * W21, T02 = J00 * W02 + J02 * W22;
-    float T10 = J11 * W10 + J12 * W20, T11 = J11 * W11 + J12 * W21, T12 = J11 * W12 + J12 * W22;
     float a0 = c0 * T00 + c1 * T01 + c2 * T02, a1 = c1 * T00 + c3 * T01 + c4 * T02, a2 = c2 * T00 + c4 * T01 + c5 * T02;
     float b0 = c0 * T10 + c1 * T11 + c2 * T12, b1 = c1 * T10 + c3 * T11 + c4 * T12, b2 = c2 * T10 + c4 * T11 + c5 * T12;
     float A = T00 * a0 + T01 * a1 + T02 * a2 + kLowPass;
@@ -535,9 +500,7 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(
     }
     float sx = scale_mod * s0, sy = scale_mod * s1, sz = scale_mod * s2;
     float qr = q4.x, qx = q4.y, qy = q4.z, qz = q4.w;
-    float R00 = 1.f - 2.f * (qy * qy + qz * qz), R01 = 2.f * (qx * qy - qr * qz), R02 = 2.f * (qx * qz + qr * qy);
-    float R10 = 2.f * (qx * qy + qr * qz), R11 = 1.f - 2.f * (qx * qx + qz * qz), R12 = 2.f * (qy * qz - qr * qx);
-    float R20 = 2.f * (qx * qz - qr * qy), R21 = 2.f * (qy * qz + qr * qx), R22 = 1.f - 2.f * (qx * qx + qy * qy);
+    const auto [R00, R01, R02, R10, R11, R12, R20, R21, R22] = quat_rotation(q4);
     float m00 = R00 * sx, m01 = R01 * sy, m02 = R02 * sz;
     float m10 = R10 * sx, m11 = R11 * sy, m12 = R12 * sz;
     float m20 = R20 * sx, m21 = R21 * sy, m22 = R22 * sz;
@@ -638,7 +601,7 @@ static int raster_backward(int raw, int N, int sh_degree, int sh_coeffs, long lo
                        scales, rotations, opacities, shs, confidence, scale_modifier, cam, radii, g, grad_rec,
                        dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacities, dL_dshs, dL_dmeans2D, dL_dconfidence, raw);
     else
-    SYN3R_LAUNCH(k_preprocess_bwd<false>, dim3(ceil_div(N, 256)), dim3(256), 0, stream, N, sh_degree, sh_coeffs, means3D,
+        SYN3R_LAUNCH(k_preprocess_bwd<false>, dim3(ceil_div(N, 256)), dim3(256), 0, stream, N, sh_degree, sh_coeffs, means3D,
                        scales, rotations, opacities, shs, confidence, scale_modifier, cam, radii, g, grad_rec,
                        dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacities, dL_dshs, dL_dmeans2D, dL_dconfidence, raw);
     SYN3R_LAUNCH_CHECK("raster_backward launch");

@@ -96,13 +96,30 @@ int radix_sort_pairs(unsigned long long* keys_a, unsigned* vals_a, unsigned long
                      size_t n, int nbits, void* scratch, hipStream_t stream, int* result_in_b,
                      const unsigned* n_dev = nullptr);
 
+// camera passed by value to kernels
+struct Camera {
+    float view[16];     // world->view, column-major (x' = v[0]x + v[4]y + v[8]z + v[12])
+    float proj[16];     // world->clip, column-major
+    float campos[3];
+    float tanfovx, tanfovy, focal_x, focal_y;
+    int H, W, grid_x, grid_y;
+};
+
 size_t geom_bytes(int N);
 bool raster_tiles_ordered(int N, int gx, int gy);   // did syn3r_raster_render leave ImageState::tile_order for this shape?
 size_t image_bytes(int H, int W);
 size_t binning_bytes(long long P);
 GeomState carve_geom(void* buf, int N);
+void raster_fill_camera(Camera& cam, const float* view, const float* proj, const float* campos, float tanfovx, float tanfovy, int H, int W);
 ImageState carve_image(void* buf, int H, int W);
 BinningState carve_binning(void* buf, long long P);
+
+// Tile binning (raster_bin.hip).  After k_preprocess: the depth argsort and the tile counts scanned in that order (pair-sort
+// shapes), or the plain scan if the caller wants the exact pair count (header[0]) now (hierarchical binning: else nothing).
+int raster_bin_prepare(const GeomState& g, int N, int gx, int gy, bool want_count, hipStream_t stream);
+// Before k_render: ImageState::ranges and the list they index (pair capacity P); *tile_order: longest list first, or null.
+int raster_bin_lists(const GeomState& g, const ImageState& im, const BinningState& bn, const int* radii, int N, int gx, int gy,
+                     long long P, hipStream_t stream, unsigned** point_list, const unsigned** tile_order);
 
 #ifdef __HIPCC__
 // Conservative reach test used by the blend kernels to build per-wavefront visit lists: can the splat
@@ -134,15 +151,105 @@ __device__ __forceinline__ bool splat_reaches_rect(float mx, float my, float A, 
     }
     return qmin <= thr + (1.0e-3f + 1.0e-4f * thr);
 }
-#endif
 
-// camera passed by value to kernels
-struct Camera {
-    float view[16];     // world->view, column-major (x' = v[0]x + v[4]y + v[8]z + v[12])
-    float proj[16];     // world->clip, column-major
-    float campos[3];
-    float tanfovx, tanfovy, focal_x, focal_y;
-    int H, W, grid_x, grid_y;
+// the tiles [x0, x1) x [y0, y1) a splat of this pixel mean and radius touches
+__device__ __forceinline__ void tile_rect(float px, float py, int radius, int gx, int gy, int& x0, int& y0, int& x1,
+                                          int& y1) {
+    x0 = min(gx, max(0, (int)((px - radius) / kTileX)));
+    y0 = min(gy, max(0, (int)((py - radius) / kTileY)));
+    x1 = min(gx, max(0, (int)((px + radius + kTileX - 1) / kTileX)));
+    y1 = min(gy, max(0, (int)((py + radius + kTileY - 1) / kTileY)));
+}
+
+// ---- The blend frame: what k_render and k_render_bwd must agree on bit for bit (the backward re-derives the forward's decisions).
+// A 16 x 16 tile is a block of TWO wavefronts; wavefront w owns the 16 x 8 half (rows 8w .. 8w+7) and lane l the pixels
+// (l & 15, 8w + (l >> 4)) and (.., + 4): per-pixel quantities are float2, for gfx950's packed fp32 arithmetic.
+typedef float f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f2 splat2(float s) { return (f2){s, s}; }
+constexpr int kBlendThreads = 128;
+struct BlendFrame {
+    int px, py0, py1;              // the lane's pixels (px, py0), (px, py1)
+    bool in0, in1;                 // ... inside the image?
+    float fx;
+    f2 fy;
 };
+struct BlendHalf { float sx0, sx1, sy0, sy1; };   // pixel centres of the wavefront's 16 x 8 half (splat_reaches_rect)
+// (wq, lane) = (threadIdx.x >> 6, threadIdx.x & 63), formed IN the kernel, where the compiler knows the block size: the same code
+__device__ __forceinline__ BlendFrame blend_frame(unsigned tile, int wq, int lane, int H, int W, int gx) {
+    const int tx = tile % gx, ty = tile / gx;
+    const int lx = lane & 15, ly = wq * 8 + (lane >> 4);
+    BlendFrame f;
+    f.px = tx * kTileX + lx; f.py0 = ty * kTileY + ly; f.py1 = f.py0 + 4;
+    f.in0 = f.px < W && f.py0 < H; f.in1 = f.px < W && f.py1 < H;
+    f.fx = (float)f.px;
+    f.fy = (f2){(float)f.py0, (float)f.py1};
+    return f;
+}
+// (on its own, called where the blend loop starts: formed with the frame it would reorder the kernels' prologues)
+__device__ __forceinline__ BlendHalf blend_half(unsigned tile, int wq, int gx) {
+    const int tx = tile % gx, ty = tile / gx;
+    BlendHalf h;
+    h.sx0 = (float)(tx * kTileX); h.sx1 = h.sx0 + 15.0f;
+    h.sy0 = (float)(ty * kTileY + wq * 8); h.sy1 = h.sy0 + 7.0f;
+    return h;
+}
+// a fetched 48-byte record into its 3 x float4 LDS slot: a = (x, y, cxx, cxy)  b = (cyy, opacity, r, g)  c = (b, depth, -, -)
+__device__ __forceinline__ void stage_splat(float4* sm, int slot, const float4& n0, const float4& n1, const float4& n2) {
+    sm[slot * 3 + 0] = n0;
+    sm[slot * 3 + 1] = n1;
+    sm[slot * 3 + 2] = n2;
+}
+// the (splat, pixel pair) evaluation: offsets mean - pixel, the exponent and G = exp(power); alpha = min(kAlphaMax, opacity * G)
+struct BlendEval { float dx; f2 dy, power, G; };
+__device__ __forceinline__ BlendEval blend_eval(const float4& a, const float4& b, const BlendFrame& f) {
+    BlendEval e;
+    e.dx = a.x - f.fx;
+    e.dy = splat2(a.y) - f.fy;
+    const float hxx = -0.5f * a.z * e.dx * e.dx, bxy = a.w * e.dx;
+    e.power = (-0.5f * b.x) * e.dy * e.dy - bxy * e.dy + hxx;
+    const f2 pl = e.power * kLog2e;   // __expf's own multiply, as one packed instruction for the pair: the same bits
+    e.G = (f2){__builtin_amdgcn_exp2f(pl.x), __builtin_amdgcn_exp2f(pl.y)};
+    return e;
+}
+
+// ---- Projection pieces k_preprocess and k_preprocess_bwd share.
+constexpr float SH_C0 = 0.28209479177387814f;
+constexpr float SH_C1 = 0.4886025119029199f;
+static __constant__ float SH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
+                                      -1.0925484305920792f, 0.5462742152960396f};
+static __constant__ float SH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
+                                      -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
+// rotation of the quaternion q = (r, x, y, z) (not renormalised here); the kernels form M = R S themselves (Sigma = M M^T)
+struct Rot3 { float R00, R01, R02, R10, R11, R12, R20, R21, R22; };
+__device__ __forceinline__ Rot3 quat_rotation(float4 q) {
+    const float qr = q.x, qx = q.y, qy = q.z, qz = q.w;
+    Rot3 o;
+    o.R00 = 1.f - 2.f * (qy * qy + qz * qz); o.R01 = 2.f * (qx * qy - qr * qz); o.R02 = 2.f * (qx * qz + qr * qy);
+    o.R10 = 2.f * (qx * qy + qr * qz); o.R11 = 1.f - 2.f * (qx * qx + qz * qz); o.R12 = 2.f * (qy * qz - qr * qx);
+    o.R20 = 2.f * (qx * qz - qr * qy); o.R21 = 2.f * (qy * qz + qr * qx); o.R22 = 1.f - 2.f * (qx * qx + qy * qy);
+    return o;
+}
+// EWA: the Jacobian J of the projection at the view-space mean t, with t.x / t.z and t.y / t.z clamped to the guarded field of
+// view ((tx, ty) = the clamped values times t.z), and the rows of T = J W, W = rotation part of the view matrix (W[r][c] = v[c*4+r])
+struct EwaRows { float tx, ty, T00, T01, T02, T10, T11, T12; };
+__device__ __forceinline__ EwaRows ewa_rows(const Camera& cam, float t_x, float t_y, float t_z) {
+    const float limx = kFovGuard * cam.tanfovx, limy = kFovGuard * cam.tanfovy;
+    EwaRows o;
+    o.tx = fminf(limx, fmaxf(-limx, t_x / t_z)) * t_z;
+    o.ty = fminf(limy, fmaxf(-limy, t_y / t_z)) * t_z;
+    const float J00 = cam.focal_x / t_z, J02 = -(cam.focal_x * o.tx) / (t_z * t_z);
+    const float J11 = cam.focal_y / t_z, J12 = -(cam.focal_y * o.ty) / (t_z * t_z);
+    const float* v = cam.view;
+    o.T00 = J00 * v[0] + J02 * v[2]; o.T01 = J00 * v[4] + J02 * v[6]; o.T02 = J00 * v[8] + J02 * v[10];
+    o.T10 = J11 * v[1] + J12 * v[2]; o.T11 = J11 * v[5] + J12 * v[6]; o.T12 = J11 * v[9] + J12 * v[10];
+    return o;
+}
+
+#ifdef SYN3R_RASTER_STATS      // developer build, per blend kernel: [0] lane tests, [1] wavefront visits, [2] visits with an active pixel, [3] active pixels
+#define RASTER_STAT(arr, i, n) do { if (lane == 0) atomicAdd(&arr[i], (unsigned long long)(n)); } while (0)
+#else
+#define RASTER_STAT(arr, i, n)
+#endif
+#endif
 
 }  // namespace syn3r

@@ -126,12 +126,7 @@ __global__ void __launch_bounds__(kSel) k_select(StepParams p, const void* __res
             const int lane = threadIdx.x;
             unsigned c0 = hist[4 * lane], c1 = hist[4 * lane + 1], c2 = hist[4 * lane + 2], c3 = hist[4 * lane + 3];
             unsigned tot = c0 + c1 + c2 + c3;
-            unsigned incl = tot;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                unsigned t = __shfl_up(incl, o, 64);
-                if (lane >= o) incl += t;
-            }
+            unsigned incl = wave_scan_incl(tot);
             unsigned excl = incl - tot;
             unsigned rank = s_rank;
             if (rank >= excl && rank < incl) {

@@ -15,7 +15,7 @@
 //             its stable rank; scatter to base + rank.
 // HBM-bound: (key+4) B read + (key+4) B written per pair per pass, + one key read in k_hist.
 //
-// The rasteriser uses two instantiations (raster_fwd.hip): Gaussians by depth bits (u32 keys, 8-bit digits,
+// The rasteriser's pair-sort path uses two instantiations (raster_bin.hip): Gaussians by depth bits (u32 keys, 8-bit digits,
 // 4 passes over N elements) and (tile, Gaussian) pairs by tile id (u32 keys, 7-bit digits, 2 passes over P
 // pairs, emitted in depth order) - together the same order as one 45-bit sort of (tile << 32 | depth) keys.
 #include "common.h"
@@ -30,34 +30,6 @@ constexpr int kScanThreads = 1024;
 constexpr int kScanItems = 4;                      // per thread
 constexpr int kScanChunk = kScanThreads * kScanItems;  // 4096 per block
 
-__device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned* smem /*[16+1]*/, unsigned& total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    unsigned incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        unsigned t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) smem[wv] = incl;
-    __syncthreads();
-    if (wv == 0) {
-        unsigned s = lane < (int)(blockDim.x >> 6) ? smem[lane] : 0;
-        unsigned si = s;
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) {
-            unsigned t = __shfl_up(si, o, 64);
-            if (lane >= o) si += t;
-        }
-        if (lane < 16) smem[lane] = si - s;   // exclusive wave offsets
-        if (lane == 15) smem[16] = si;        // block total
-    }
-    __syncthreads();
-    unsigned res = incl - v + smem[wv];
-    total = smem[16];
-    __syncthreads();
-    return res;
-}
-
 // phase 1: per-chunk sums
 __global__ void __launch_bounds__(kScanThreads) k_scan_sums(const unsigned* __restrict__ in,
                                                            const unsigned* __restrict__ perm, size_t n,
@@ -68,7 +40,7 @@ __global__ void __launch_bounds__(kScanThreads) k_scan_sums(const unsigned* __re
 #pragma unroll
     for (int k = 0; k < kScanItems; ++k) s += (base + k < n) ? (perm ? in[perm[base + k]] : in[base + k]) : 0;
     unsigned total;
-    block_exclusive_scan(s, smem, total);
+    block_exclusive_scan<kScanThreads / 64>(s, smem, total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
@@ -81,7 +53,7 @@ __global__ void __launch_bounds__(kScanThreads) k_scan_top(unsigned* __restrict_
         int i = start + threadIdx.x;
         unsigned v = i < nchunks ? sums[i] : 0;
         unsigned total;
-        unsigned ex = block_exclusive_scan(v, smem, total);
+        unsigned ex = block_exclusive_scan<kScanThreads / 64>(v, smem, total);
         if (i < nchunks) sums[i] = ex + carry;
         carry += total;
     }
@@ -103,7 +75,7 @@ __global__ void __launch_bounds__(kScanThreads) k_scan_final(const unsigned* __r
         s += v[k];
     }
     unsigned total;
-    unsigned ex = block_exclusive_scan(s, smem, total) + sums[blockIdx.x];
+    unsigned ex = block_exclusive_scan<kScanThreads / 64>(s, smem, total) + sums[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < kScanItems; ++k) {
         if (base + k < n) out[base + k] = ex;
@@ -138,7 +110,7 @@ __global__ void __launch_bounds__(kScanThreads) k_scan_small(const unsigned* __r
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) s += v[k];
     unsigned total;
-    unsigned ex = block_exclusive_scan(s, smem, total);
+    unsigned ex = block_exclusive_scan<kScanThreads / 64>(s, smem, total);
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) {
         unsigned t = v[k];
@@ -240,7 +212,7 @@ __global__ void __launch_bounds__(kSortThreads) k_scatter(const K* __restrict__ 
     const size_t n = live_count(n_cap, n_dev);
     __shared__ unsigned fbase[FUSED ? BINS : 1];   // FUSED: what the scanned table would hold for (digit, this block)
     if constexpr (FUSED) {
-        __shared__ unsigned ssm[17];
+        __shared__ unsigned ssm[kSortWaves + 1];
         const unsigned* col = bases + threadIdx.x;        // block-major table: entry (block b, digit d) at b * BINS + d
         unsigned tot = 0, pre = 0;
         constexpr int UN = 16;                             // loads in flight per thread: the loop is L2 latency, not bandwidth
@@ -255,7 +227,7 @@ __global__ void __launch_bounds__(kSortThreads) k_scatter(const K* __restrict__ 
             }
         }
         unsigned total;
-        fbase[threadIdx.x] = block_exclusive_scan(tot, ssm, total) + pre;
+        fbase[threadIdx.x] = block_exclusive_scan<kSortWaves>(tot, ssm, total) + pre;
     }
     __shared__ unsigned wh[kSortWaves][BINS];   // per-wave digit counts, then running block-local offsets
     __shared__ unsigned gbase[BINS];            // global position of local position 0 of the digit's run (may wrap: unsigned arithmetic)
@@ -295,13 +267,7 @@ __global__ void __launch_bounds__(kSortThreads) k_scatter(const K* __restrict__ 
             tot[k] = t;
             sum += t;
         }
-        unsigned incl = sum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            unsigned t = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += t;
-        }
-        unsigned run = incl - sum;
+        unsigned run = wave_scan_incl(sum) - sum;
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
             const int d = lane * PER + k;

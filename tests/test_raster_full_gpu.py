@@ -92,7 +92,7 @@ def _check_tile_lists(gpu, N, H, W, bg=(0.1, 0.2, 0.3), scale_mult=1.0):
     """The oracle's float32 preprocess + stable sort of the published (tile << 32 | depth bits) keys, run live, against the
     HIP binning.  A Gaussian whose 3-sigma radius lands on an integer boundary may get a different ceil() from the two fp32
     evaluation orders: those (a handful in 200 000) are removed from both lists, everything else must agree index for
-    index."""
+    index.  Returns the oracle's ranges."""
     from syn3r_amd.raster import _Rasterize
     m, s, q, o, sh = RO.synthetic_gaussians(N, seed=1234, dtype=torch.float32)
     s = s * scale_mult
@@ -125,6 +125,7 @@ def _check_tile_lists(gpu, N, H, W, bg=(0.1, 0.2, 0.3), scale_mult=1.0):
         np.testing.assert_array_equal(a_ids, b_ids)          # same Gaussians in the same order ...
         np.testing.assert_array_equal(a_tiles, b_tiles)      # ... in the same tiles
     print(f"tile lists {N} @ {W}x{H}: P = {dbg['num_rendered']}, {len(odd)} Gaussians with a ceil() tie excluded")
+    return ranges
 
 
 def test_tile_lists_index_for_index_at_benchmark_size(golden, gpu):
@@ -137,12 +138,19 @@ def test_tile_lists_index_for_index_at_benchmark_size(golden, gpu):
     (60_000, 2160, 3840, 1.0, "510 super-tiles: eight mask words per wavefront, one column part per thread"),
     (20_000, 1152, 8192, 1.0, "576 super-tiles: beyond the hierarchical binning, the pair sort takes it"),
     (5_000, 100, 260, 1.0, "ragged image: partial tiles and partial super-tiles on both edges"),
-    (4_000, 1080, 1920, 10.0, "large footprints: more list entries per block round than the LDS staging holds, written from the ranking loop"),
+    (4_000, 1080, 1920, 10.0, "large footprints: more list entries per block round than the LDS staging holds"),
+    (20_000, 48, 40, 1.0, "nine single-tile super-tiles, lists of 155 .. 15 487: k_super_sort in LDS, in 3 pieces and in 4 (the last partial)"),
 ])
 def test_tile_lists_other_binning_shapes(N, H, W, scale, what, gpu):
-    """The hierarchical binning (csrc/raster_fwd.hip: super-tile lists, then a filter per tile) and its fallback at the shapes
+    """The hierarchical binning (csrc/raster_bin.hip: super-tile lists, then a filter per tile) and its fallback at the shapes
     that take its other branches; same oracle, same index-for-index bar."""
-    _check_tile_lists(gpu, N, H, W, scale_mult=scale)
+    ranges = _check_tile_lists(gpu, N, H, W, scale_mult=scale)
+    if (H, W) == (48, 40):
+        # k_super_sort orders up to kSortLds = 4096 keys in LDS and longer lists in LDS-sized pieces merged through global memory
+        # (the 8 192 merge, and the 16 384 merge with its distance-4096 global step): the scene must stay on both sides of that
+        lens = ranges[:, 1] - ranges[:, 0]
+        assert int(lens.max()) > 8192, lens
+        assert bool(((lens > 0) & (lens <= 4096)).any()), lens
 
 
 def _edge_scene(kind, N, H, W):
