@@ -634,6 +634,17 @@ int syn3r_adam_step(float* param, const float* grad, float* exp_avg, float* exp_
 int syn3r_adam_step_multi(int count, float* const* params, const float* const* grads, float* const* exp_avgs,
                           float* const* exp_avg_sqs, const long long* numels, const float* lrs, float beta1, float beta2,
                           const float* epss, const int* steps, void* stream);
+/* syn3r_adam_step_multi with TWO learning rates inside a row of a tensor: the published 3DGS optimiser behind
+ * gsTrainer.training() / finetune() (model/diffusionGS.py:139,1640) holds the SH coefficients as two torch.optim.Adam groups,
+ * f_dc at feature_lr and f_rest at feature_lr / 20; here they are ONE contiguous [N, M, 3] tensor (the rasteriser takes one `shs`
+ * pointer), so the kernel picks the rate by position: element i of tensor k uses lrs[k] when i % row_lens[k] < head_lens[k], else
+ * lrs_tail[k] (the features: row_len = 3 M, head_len = 3).  row_lens[k] == 0: no split, lrs[k] everywhere, lrs_tail[k] unread
+ * (lrs_tail may be NULL when no tensor is split).  Everything else as syn3r_adam_step_multi, bit for bit.  Refused besides that
+ * entry's cases: row_len < 0, head_len outside 0..row_len, numel % row_len != 0, a split tensor of 2^31 elements or more. */
+int syn3r_adam_step_multi_rows(int count, float* const* params, const float* const* grads, float* const* exp_avgs,
+                               float* const* exp_avg_sqs, const long long* numels, const float* lrs, const float* lrs_tail,
+                               const int* row_lens, const int* head_lens, float beta1, float beta2,
+                               const float* epss, const int* steps, void* stream);
 
 /* The parameter activations of the published 3DGS model that FSGS' trainer applies before every render inside
  * gsTrainer.training() / finetune() (model/diffusionGS.py:139,1640; GaussianModel.get_scaling / get_rotation / get_opacity):

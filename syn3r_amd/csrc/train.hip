@@ -124,6 +124,50 @@ __global__ void __launch_bounds__(kThreads) k_adam_multi(AdamTable t) {
     v[i] = vi;
 }
 
+// k_adam_multi with TWO learning rates inside a row of a tensor (the published 3DGS optimiser: f_dc at feature_lr, f_rest at
+// feature_lr / 20, here ONE contiguous [N, M, 3] tensor because the rasteriser takes one `shs` pointer): element i of tensor k takes
+// neg_step[k] when i % row_len[k] < head_len[k], neg_step_tail[k] otherwise; row_len[k] == 0 is a plain tensor (no column arithmetic:
+// the branch is on a table entry, uniform per block).  Otherwise element for element k_adam_multi (bit-identical with equal rates).
+// The split costs no bytes.  256 threads do not divide a 48-float row, so the column of a block's first element differs per block:
+//   col0 = (block's first element) % row_len   scalar unit only: Lemire / Kaser / Kurz 2019 ("Faster remainder by direct
+//          computation"), a % d = mulhi64(M * a mod 2^64, d) with M = floor((2^64 - 1) / d) + 1, exact for every 32-bit a and d >= 1
+//          (the entry refuses a split tensor of 2^31 elements or more);
+//   tcol = thread % row_len = thread - ((thread * ceil(2^16 / row_len)) >> 16) * row_len: exact for thread < 256 and row_len <= 255
+//          (the error of the quotient is thread * (magic * row_len - 2^16) / 2^16 < 255 * 255 / 2^16 < 1); row_len >= 256 has magic 0;
+//   col  = min(x, x - row_len) in unsigned arithmetic with x = col0 + tcol < 2 row_len (x - row_len wraps above x when x < row_len).
+struct AdamRowsTable {
+    AdamTable t;
+    float neg_step_tail[kAdamMulti];
+    unsigned row_len[kAdamMulti], head_len[kAdamMulti], tid_magic[kAdamMulti];
+    unsigned long long row_magic[kAdamMulti];
+};
+__global__ void __launch_bounds__(kThreads) k_adam_multi_rows(AdamRowsTable r) {
+    const AdamTable& t = r.t;
+    int k = 0;
+#pragma unroll
+    for (int q = 1; q < kAdamMulti; ++q) k += (q < t.count && blockIdx.x >= t.blk0[q]) ? 1 : 0;
+    const unsigned blk = blockIdx.x - t.blk0[k];
+    const long long i = (long long)blk * kThreads + threadIdx.x;
+    if (i >= t.n[k]) return;
+    float neg_step = t.neg_step[k];
+    const unsigned row = r.row_len[k];
+    if (row != 0) {
+        const unsigned col0 = (unsigned)__umul64hi(r.row_magic[k] * (unsigned long long)(blk * (unsigned)kThreads), (unsigned long long)row);
+        const unsigned x = col0 + threadIdx.x - __umul24(__umul24(threadIdx.x, r.tid_magic[k]) >> 16, row);
+        const float tail = r.neg_step_tail[k];             // read before the select: a load in one arm of ?: is a divergent branch
+        neg_step = min(x, x - row) < r.head_len[k] ? neg_step : tail;
+    }
+    float* __restrict__ p = t.p[k]; const float* __restrict__ g = t.g[k]; float* __restrict__ m = t.m[k]; float* __restrict__ v = t.v[k];
+    const float gi = g[i];
+    float mi = m[i], vi = v[i];
+    mi = mi + t.w1 * (gi - mi);
+    vi = vi * t.beta2 + (t.w2 * gi) * gi;
+    const float denom = sqrtf(vi) / t.bc2_sqrt[k] + t.eps[k];
+    p[i] = p[i] + neg_step * (mi / denom);
+    m[i] = mi;
+    v[i] = vi;
+}
+
 // ---------------------------------------------------------------------------------------------
 // The published 3DGS parameter activations (GaussianModel.get_scaling / get_rotation / get_opacity: exp, normalize, sigmoid;
 // FSGS' trainer behind gsTrainer.training() / finetune(), model/diffusionGS.py:139,1640) as ONE launch forward and ONE launch
@@ -556,6 +600,50 @@ extern "C" int syn3r_adam_step_multi(int count, float* const* params, const floa
     for (int k = count; k <= kAdamMulti; ++k) t.blk0[k] = (unsigned)blocks;
     SYN3R_LAUNCH(k_adam_multi, dim3((unsigned)blocks), dim3(kThreads), 0, stream, t);
     SYN3R_LAUNCH_CHECK("adam_step_multi launch");
+    return SYN3R_OK;
+}
+
+extern "C" int syn3r_adam_step_multi_rows(int count, float* const* params, const float* const* grads, float* const* exp_avgs,
+                                          float* const* exp_avg_sqs, const long long* numels, const float* lrs, const float* lrs_tail,
+                                          const int* row_lens, const int* head_lens, float beta1, float beta2, const float* epss,
+                                          const int* steps, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    SYN3R_REQUIRE(count >= 1 && count <= kAdamMulti, "adam_step_multi_rows: count=%d must be 1..%d", count, kAdamMulti);
+    SYN3R_REQUIRE(params && grads && exp_avgs && exp_avg_sqs && numels && lrs && row_lens && head_lens && epss && steps,
+                  "adam_step_multi_rows: null table");
+    SYN3R_REQUIRE(beta1 >= 0.5f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f, "adam_step_multi_rows: betas out of range");
+    AdamRowsTable r{};
+    AdamTable& t = r.t;
+    t.count = count;
+    t.w1 = (float)(1.0 - (double)beta1); t.beta2 = beta2; t.w2 = (float)(1.0 - (double)beta2);
+    long long blocks = 0;
+    for (int k = 0; k < count; ++k) {
+        SYN3R_REQUIRE(params[k] && grads[k] && exp_avgs[k] && exp_avg_sqs[k], "adam_step_multi_rows: null pointer in tensor %d", k);
+        SYN3R_REQUIRE(numels[k] > 0 && steps[k] >= 1, "adam_step_multi_rows: tensor %d: n must be positive, step 1-based", k);
+        const int row = row_lens[k], head = head_lens[k];
+        SYN3R_REQUIRE(row >= 0, "adam_step_multi_rows: tensor %d: row_len=%d is negative", k, row);
+        // the scalar factors are computed as torch does, in double on the host (syn3r_adam_step)
+        const double bc1 = 1.0 - pow((double)beta1, (double)steps[k]);
+        const double bc2 = 1.0 - pow((double)beta2, (double)steps[k]);
+        if (row > 0) {
+            SYN3R_REQUIRE(lrs_tail, "adam_step_multi_rows: tensor %d has a row split and lrs_tail is null", k);
+            SYN3R_REQUIRE(head >= 0 && head <= row, "adam_step_multi_rows: tensor %d: head_len=%d must be 0..row_len=%d", k, head, row);
+            SYN3R_REQUIRE(numels[k] % row == 0, "adam_step_multi_rows: tensor %d: n=%lld is no multiple of row_len=%d", k, numels[k], row);
+            SYN3R_REQUIRE(numels[k] < (1ll << 31), "adam_step_multi_rows: tensor %d: a split tensor must have fewer than 2^31 elements", k);
+            r.neg_step_tail[k] = (float)(-((double)lrs_tail[k] / bc1));
+            r.row_len[k] = (unsigned)row; r.head_len[k] = (unsigned)head;
+            r.tid_magic[k] = row < kThreads ? (65536u + (unsigned)row - 1u) / (unsigned)row : 0u;
+            r.row_magic[k] = ~0ull / (unsigned long long)row + 1ull;
+        }
+        t.p[k] = params[k]; t.g[k] = grads[k]; t.m[k] = exp_avgs[k]; t.v[k] = exp_avg_sqs[k]; t.n[k] = numels[k];
+        t.neg_step[k] = (float)(-((double)lrs[k] / bc1)); t.bc2_sqrt[k] = (float)sqrt(bc2); t.eps[k] = epss[k];
+        t.blk0[k] = (unsigned)blocks;
+        blocks += (numels[k] + kThreads - 1) / kThreads;
+        SYN3R_REQUIRE(blocks < (1ll << 31), "adam_step_multi_rows: tensors too large");
+    }
+    for (int k = count; k <= kAdamMulti; ++k) t.blk0[k] = (unsigned)blocks;
+    SYN3R_LAUNCH(k_adam_multi_rows, dim3((unsigned)blocks), dim3(kThreads), 0, stream, r);
+    SYN3R_LAUNCH_CHECK("adam_step_multi_rows launch");
     return SYN3R_OK;
 }
 

@@ -295,7 +295,10 @@ def proximity_unpool(xyz: torch.Tensor, log_scales: torch.Tensor, opacity_logits
 class FusedAdam:
     """`torch.optim.Adam(param_groups, eps=...)` (no weight decay / amsgrad) with one kernel per parameter tensor.
     Keeps torch's `param_groups` / `state` layout so checkpoints and lr schedules written for the torch optimiser
-    keep working."""
+    keep working.
+    A group may carry `lr_tail`, `row_len` and `head_len`: its tensors are rows of `row_len` floats whose first `head_len` take
+    `lr` and the rest `lr_tail` (`syn3r_adam_step_multi_rows`: the published 3DGS f_dc / f_rest groups as ONE [N, M, 3] tensor
+    with row_len = 3 M, head_len = 3).  `row_len` 0 or absent: a plain group."""
 
     def __init__(self, param_groups: Iterable[dict], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8):
         self.param_groups: List[dict] = []
@@ -319,12 +322,16 @@ class FusedAdam:
     @torch.no_grad()
     def step(self):
         """One update of every parameter that has a gradient: ONE launch per (beta1, beta2) and up to 8 tensors
-        (`syn3r_adam_step_multi`; the trainer's five / six groups share their betas), element for element `torch.optim.Adam`."""
+        (`syn3r_adam_step_multi`; the trainer's five / six groups share their betas), element for element `torch.optim.Adam`.
+        A chunk with a tensor of a row-split group goes through `syn3r_adam_step_multi_rows` (the plain tensors ride along with
+        row_len = 0); a chunk without one takes `syn3r_adam_step_multi` as before."""
         import ctypes as C
         lib = L.load()
         batches: dict = {}
         for g in self.param_groups:
             b1, b2 = g["betas"]
+            row_len = int(g.get("row_len") or 0)
+            split = (float(g["lr_tail"]), row_len, int(g["head_len"])) if row_len else (0.0, 0, 0)
             for p in g["params"]:
                 if p.grad is None:
                     continue
@@ -336,15 +343,22 @@ class FusedAdam:
                     st = self.state[p] = {"step": 0, "exp_avg": torch.zeros_like(p), "exp_avg_sq": torch.zeros_like(p)}
                 st["step"] += 1
                 grad = p.grad.contiguous()
-                batches.setdefault((float(b1), float(b2), p.device), []).append((p, grad, st, float(g["lr"]), float(g["eps"])))
+                batches.setdefault((float(b1), float(b2), p.device), []).append((p, grad, st, float(g["lr"]), float(g["eps"]), split))
         for (b1, b2, dev), items in batches.items():
             for k0 in range(0, len(items), 8):
                 chunk = items[k0:k0 + 8]
                 n = len(chunk)
                 ptrs = lambda sel: (C.c_void_p * n)(*[sel(it) for it in chunk])
-                rc = lib.syn3r_adam_step_multi(
-                    n, ptrs(lambda it: it[0].data_ptr()), ptrs(lambda it: it[1].data_ptr()), ptrs(lambda it: it[2]["exp_avg"].data_ptr()),
-                    ptrs(lambda it: it[2]["exp_avg_sq"].data_ptr()), (C.c_longlong * n)(*[it[0].numel() for it in chunk]),
-                    (C.c_float * n)(*[it[3] for it in chunk]), b1, b2, (C.c_float * n)(*[it[4] for it in chunk]),
-                    (C.c_int * n)(*[int(it[2]["step"]) for it in chunk]), L.stream_ptr(dev))
-                L.check(rc, "adam_step_multi")
+                tables = (n, ptrs(lambda it: it[0].data_ptr()), ptrs(lambda it: it[1].data_ptr()), ptrs(lambda it: it[2]["exp_avg"].data_ptr()),
+                          ptrs(lambda it: it[2]["exp_avg_sq"].data_ptr()), (C.c_longlong * n)(*[it[0].numel() for it in chunk]),
+                          (C.c_float * n)(*[it[3] for it in chunk]))
+                tail = (b1, b2, (C.c_float * n)(*[it[4] for it in chunk]), (C.c_int * n)(*[int(it[2]["step"]) for it in chunk]),
+                        L.stream_ptr(dev))
+                if any(it[5][1] for it in chunk):
+                    rc = lib.syn3r_adam_step_multi_rows(*tables, (C.c_float * n)(*[it[5][0] for it in chunk]),
+                                                        (C.c_int * n)(*[it[5][1] for it in chunk]),
+                                                        (C.c_int * n)(*[it[5][2] for it in chunk]), *tail)
+                    L.check(rc, "adam_step_multi_rows")
+                else:
+                    rc = lib.syn3r_adam_step_multi(*tables, *tail)
+                    L.check(rc, "adam_step_multi")

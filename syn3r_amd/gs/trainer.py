@@ -108,18 +108,30 @@ def build_rotation(q: torch.Tensor) -> torch.Tensor:
 
 
 class GaussianModel:
-    """Trainable Gaussian parameters with the published activations (exp scale, sigmoid opacity, unit quaternion)."""
+    """Trainable Gaussian parameters with the published activations (exp scale, sigmoid opacity, unit quaternion).
+    `active_sh_degree` (None: `sh_degree`): the degree the rasteriser evaluates; the published training starts at 0 and raises
+    it with `oneupSHdegree` (`OptimizationParams.sh_degree_interval`)."""
 
-    def __init__(self, xyz, log_scales, rotations, opacity_logits, shs, sh_degree: int = 3, device="cuda"):
+    def __init__(self, xyz, log_scales, rotations, opacity_logits, shs, sh_degree: int = 3, device="cuda",
+                 active_sh_degree: Optional[int] = None):
         dev = torch.device(device)
         p = lambda t: torch.nn.Parameter(torch.as_tensor(t, dtype=torch.float32).to(dev).contiguous())
         self._xyz, self._scaling, self._rotation = p(xyz), p(log_scales), p(rotations)
         self._opacity, self._features = p(opacity_logits), p(shs)
         self.confidence = torch.ones(self._xyz.shape[0], device=dev)
-        self.max_sh_degree = self.active_sh_degree = sh_degree
+        self.max_sh_degree = sh_degree
+        self.active_sh_degree = sh_degree if active_sh_degree is None else int(active_sh_degree)
+        if not 0 <= self.active_sh_degree <= self.max_sh_degree:
+            raise ValueError(f"GaussianModel: active_sh_degree={active_sh_degree} must be in 0..sh_degree={sh_degree}")
 
     def parameters(self):
         return [self._xyz, self._features, self._opacity, self._scaling, self._rotation]
+
+    def oneupSHdegree(self):
+        """Published `GaussianModel.oneupSHdegree`: one more active SH band, up to `max_sh_degree`.  The kernels take any
+        sh_degree <= sqrt(coefficients) - 1 and write exact zeros to the gradient of the inactive rows."""
+        if self.active_sh_degree < self.max_sh_degree:
+            self.active_sh_degree += 1
 
     @property
     def get_xyz(self): return self._xyz
@@ -178,7 +190,9 @@ class GaussianModel:
     def set_from_pcd(self, points: np.ndarray, colors: np.ndarray, append: bool):
         """Published 3DGS `create_from_pcd`: DC colour = (rgb - 0.5) / C0, higher SH zero, isotropic scale =
         sqrt(mean squared distance to the 3 nearest neighbours), identity rotation, opacity 0.1.  The reference does this
-        inside FSGS (`simple-knn` CUDA extension, absent); the exact 3-NN search is `csrc/knn.hip` (`train_ops.knn3_mean_dist2`)."""
+        inside FSGS (`simple-knn` CUDA extension, absent); the exact 3-NN search is `csrc/knn.hip` (`train_ops.knn3_mean_dist2`).
+        `active_sh_degree` is left alone (the published `create_from_pcd` runs on a fresh model at degree 0; whether FSGS' fork
+        restarts the degree when the orchestrator re-initialises from a point cloud is not visible - UNPINNED)."""
         dev = self._xyz.device
         to_dev = lambda a: (a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))).to(dev, torch.float32)
         pts, rgb = to_dev(points), to_dev(colors)
@@ -249,6 +263,38 @@ class OptimizationParams:
     proximity_until_iter: int = 2000
     proximity_dist_factor: float = 5.0
     proximity_scale_factor: float = 1.0
+    # Three rules of the published 3DGS optimiser (Kerbl et al. 2023 and its released training loop), all OFF by default: the
+    # log-linear position learning-rate decay (`expon_lr`, `GSTrainer.update_learning_rate`), f_rest at feature_lr / div
+    # (`GSTrainer.reset_optimizers`) and the progressive SH degree (`GaussianModel.oneupSHdegree`).  The released values - decay
+    # 1.6e-4 -> 1.6e-6 over 30 000 steps, div 20, one degree every 1000 iterations - are RECALLED from the released 3DGS arguments,
+    # which are not available to check against, and FSGS' fork may differ: UNPINNED, hence options (launch.py --gs_schedule published).
+    position_lr_final: Optional[float] = None   # None: position_lr stays constant
+    position_lr_delay_mult: float = 0.01
+    position_lr_delay_steps: int = 0
+    position_lr_max_steps: int = 30_000
+    spatial_lr_scale: Optional[float] = 1.0     # multiplier of the position rate; None: cameras_extent() when the optimiser is (re)built
+    feature_rest_lr_div: float = 1.0            # 1: one rate for all SH coefficients; else rows 1.. of a Gaussian at feature_lr / div
+    sh_degree_interval: int = 0                 # 0: active_sh_degree stays; else oneupSHdegree() every that many iterations
+
+
+def expon_lr(step, lr_init: float, lr_final: float, lr_delay_steps: int = 0, lr_delay_mult: float = 1.0,
+             max_steps: int = 1_000_000) -> float:
+    """The published 3DGS `get_expon_lr_func` helper (general_utils; from Plenoxels / JaxNeRF) at one step, in float64:
+    log-linear interpolation lr_init -> lr_final over `max_steps` (clamped beyond), times the delay factor
+    lr_delay_mult + (1 - lr_delay_mult) sin(pi/2 clip(step / lr_delay_steps, 0, 1)) when lr_delay_steps > 0.
+    0.0 for a negative step or when both rates are zero.  At the two ends (t = 0, t = 1) the rate is lr_init / lr_final itself, not
+    exp(log(.)) of it (which may be an ulp or two away)."""
+    if step < 0 or (lr_init == 0.0 and lr_final == 0.0):
+        return 0.0
+    if lr_init <= 0.0 or lr_final <= 0.0:
+        raise ValueError(f"expon_lr: rates must be positive (or both zero), got {lr_init} -> {lr_final}")
+    delay = 1.0
+    if lr_delay_steps > 0:
+        delay = lr_delay_mult + (1.0 - lr_delay_mult) * math.sin(0.5 * math.pi * min(max(step / lr_delay_steps, 0.0), 1.0))
+    t = min(max(step / max_steps, 0.0), 1.0)
+    if t == 0.0 or t == 1.0:
+        return delay * float(lr_init if t == 0.0 else lr_final)
+    return delay * math.exp(math.log(lr_init) * (1.0 - t) + math.log(lr_final) * t)
 
 
 class _Scene:
@@ -289,11 +335,32 @@ class GSTrainer:
 
     # ------------------------------------------------------------------ surface used by DiffusionGS
     def reset_optimizers(self):
+        """A fresh optimiser over the five parameter tensors (the published `training_setup`).  With `opt.feature_rest_lr_div`
+        != 1 the features group carries the row split of `FusedAdam` (`lr_tail = feature_lr / div`, `row_len = 3 M`, `head_len
+        = 3`): the published f_dc / f_rest groups on ONE tensor.  `opt.spatial_lr_scale` None is resolved here, to
+        `cameras_extent()` of the cameras registered now."""
         g, o = self.gaussians, self.opt
+        features = {"params": [g._features], "lr": o.feature_lr}
+        if o.feature_rest_lr_div != 1.0:
+            features.update(lr_tail=o.feature_lr / o.feature_rest_lr_div, row_len=3 * int(g._features.shape[1]), head_len=3)
+        self.spatial_lr_scale = self.cameras_extent() if o.spatial_lr_scale is None else float(o.spatial_lr_scale)
         self.optimizer = FusedAdam([
-            {"params": [g._xyz], "lr": o.position_lr}, {"params": [g._features], "lr": o.feature_lr},
+            {"params": [g._xyz], "lr": o.position_lr}, features,
             {"params": [g._opacity], "lr": o.opacity_lr}, {"params": [g._scaling], "lr": o.scaling_lr},
             {"params": [g._rotation], "lr": o.rotation_lr}], eps=1e-15)
+
+    def update_learning_rate(self, iteration: int) -> float:
+        """Published `GaussianModel.update_learning_rate`: with `opt.position_lr_final` set, the xyz group's rate becomes
+        spatial_lr_scale x expon_lr(iteration, position_lr, position_lr_final, ...) (host arithmetic into the `lr` the next launch
+        carries; no launch, no synchronisation).  `iteration` is the loop's own 1-based counter (`train_step` passes
+        `self.iteration + 1`), so the schedule restarts with every `training(0, ...)` / `finetune(0, ...)` - refine_GS resets the
+        optimisers before each finetune anyway (diffusionGS.py:1634).  Whether FSGS' fork keeps one global step across refines is
+        not visible: UNPINNED.  Returns the xyz group's rate."""
+        o, grp = self.opt, self.optimizer.param_groups[0]
+        if o.position_lr_final is not None:
+            grp["lr"] = self.spatial_lr_scale * expon_lr(iteration, o.position_lr, o.position_lr_final, o.position_lr_delay_steps,
+                                                         o.position_lr_delay_mult, o.position_lr_max_steps)
+        return grp["lr"]
 
     def reset_gs(self):
         return None
@@ -657,7 +724,10 @@ class GSTrainer:
         its two prior transforms, `train_ops.depth_correlation_loss`) for a camera with a prior (`depth_prior`: `cam.depth_image` or
         the injected `depth_net`); a camera without one skips it.  As FSGS' `loss += depth_weight * depth_loss` the term is weighted
         by `depth_weight` alone, not by the camera confidence - UNPINNED for SYN3R's FSGS fork (not vendored).
-        `explicit` (default: whenever the LPIPS term is off): the step without autograd (`_explicit_step`)."""
+        `explicit` (default: whenever the LPIPS term is off): the step without autograd (`_explicit_step`).
+        The published schedule, when switched on (`OptimizationParams`): `update_learning_rate(iteration + 1)` before the optimiser
+        step, `oneupSHdegree()` after every `sh_degree_interval`-th step (the published loop raises it at the top of the next
+        iteration); the step both count is the loop's own counter `self.iteration` - UNPINNED, see `update_learning_rate`."""
         cam = cam or self._pick_camera()
         lpips_on = self.opt.use_lpips_loss and self.opt.lpips_weight > 0.0 and self.lpips is not None
         if explicit is None:
@@ -687,9 +757,12 @@ class GSTrainer:
             n0 = self.gaussians._xyz.shape[0]
             self._density_control(out)
             changed = self.gaussians._xyz.shape[0] != n0
+        self.update_learning_rate(self.iteration + 1)
         if not changed:                       # (the gradients of this step belong to the old set of Gaussians)
             self.optimizer.step()
         self.iteration += 1
+        if self.opt.sh_degree_interval > 0 and self.iteration % self.opt.sh_degree_interval == 0:
+            self.gaussians.oneupSHdegree()
         return loss.detach()
 
     def _capacity_keys(self):

@@ -34,7 +34,10 @@ from . import dist as D
 
 
 def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0], epilog=(
+        "Accepted and ignored (flags of the absent FSGS parameter groups that the reference's batch scripts pass): "
+        + " ".join(sorted(FSGS_FLAGS)) + ".  --svd_l1_weight (batch_dl3dv_train.sh:87) belongs to the absent fork too: its meaning is "
+        "not visible, so it has none here."))
     ap.add_argument("--scenes", type=str, required=True, help="comma-separated scene names")
     ap.add_argument("--scene-factory", type=str, default="syn3r_amd.launch:synthetic_scene",
                     help="module:function building one scene (see the module docstring)")
@@ -92,11 +95,29 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--use_proximity_densify", type=int, default=0,
                     help="1: FSGS' proximity-guided Gaussian unpooling inside the density control (bash_scripts/batch_llff_train.sh:37 and "
                          "batch_dl3dv_train.sh:85 pass 0); thresholds: OptimizationParams.proximity_*")
+    # FSGS' OptimizationParams / ModelParams flags that this trainer has a field for (bash_scripts/batch_llff_train.sh:37 and
+    # batch_dl3dv_train.sh:85 pass --densify_grad_threshold 0.0002 --percent_dense 0.001).  None = leave OptimizationParams alone.
+    for flag, typ in TRAINER_FLAGS:
+        ap.add_argument("--" + flag, type=typ, default=None,
+                        help=f"OptimizationParams.{TRAINER_FLAG_FIELDS.get(flag, flag)} (default: the trainer's own)" if flag != "sh_degree"
+                        else "largest SH degree of the model the scene factory builds (default: the factory's own)")
+    ap.add_argument("--gs_schedule", type=str, default="constant", choices=("constant", "published"),
+                    help="published: the three rules of the published 3DGS optimiser - position rate decaying log-linearly to "
+                         "--position_lr_final (default 1.6e-6) over --position_lr_max_steps, times the camera extent; SH rows 1.. at "
+                         "feature_lr / 20; SH degree from 0, one up every 1000 iterations (values recalled, UNPINNED: "
+                         "gs/trainer.py OptimizationParams).  constant (default): none of them")
     ap.add_argument("--num_inference_steps", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     # FSGS' parameter groups (scripts/train.py:44-46: -s, --eval, --n_views, --resolution, --use_dust3r ... of the batch scripts)
     # belong to the absent submodule: a command line that carries them is accepted, they are kept in `ignored_flags`
-    args, rest = ap.parse_known_args(argv)
+    given = list(sys.argv[1:] if argv is None else argv)
+    args, rest = ap.parse_known_args(given)
+    # argparse takes `--percent_dens` for an abbreviation of `--percent_dense`: while that flag sat in FSGS_FLAGS the token was an
+    # unknown argument, and a misspelling stays one
+    declared = ["--" + f for f, _ in TRAINER_FLAGS] + ["--gs_schedule"]
+    cut = [t for t in given if t.startswith("--") and any(d != t.split("=")[0] and d.startswith(t.split("=")[0]) for d in declared)]
+    if cut:
+        ap.error(f"unknown argument(s): {' '.join(cut)} (the trainer's flags are not abbreviated)")
     # Only the flags of FSGS' ModelParams / OptimizationParams / PipelineParams groups that the reference's batch scripts pass
     # (bash_scripts/*.sh) are tolerated; anything else is a misspelling of one of ours and an error - a dropped
     # `--iteratons 500` must not start a multi-hour job on the defaults.
@@ -108,15 +129,42 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     return args
 
 
+# FSGS' optimiser / model flags with a counterpart in this trainer (published 3DGS OptimizationParams / ModelParams names), and the
+# OptimizationParams field of those whose name differs
+TRAINER_FLAGS = (
+    ("percent_dense", float), ("densify_grad_threshold", float), ("densify_from_iter", int), ("densify_until_iter", int),
+    ("densification_interval", int), ("opacity_reset_interval", int), ("position_lr_init", float), ("position_lr_final", float),
+    ("position_lr_max_steps", int), ("feature_lr", float), ("opacity_lr", float), ("scaling_lr", float), ("rotation_lr", float),
+    ("sh_degree", int))
+TRAINER_FLAG_FIELDS = {"position_lr_init": "position_lr"}
+
+
+def apply_trainer_flags(opt, args):
+    """-> a copy of `opt` (gs.OptimizationParams) with the TRAINER_FLAGS that were given (not None) in their fields, and with
+    `--gs_schedule published` the switches of the three published optimiser rules: decay to --position_lr_final or 1.6e-6,
+    spatial_lr_scale = None (the camera extent), feature_rest_lr_div = 20, sh_degree_interval = 1000.  Pure: no GPU, `opt`
+    untouched.  (--sh_degree describes the model, not the optimiser: the scene factory reads it.)"""
+    import dataclasses
+    new = {}
+    for flag, _ in TRAINER_FLAGS:
+        v = getattr(args, flag, None)
+        if v is not None and flag != "sh_degree":
+            new[TRAINER_FLAG_FIELDS.get(flag, flag)] = v
+    if getattr(args, "gs_schedule", "constant") == "published":
+        if new.get("position_lr_final", opt.position_lr_final) is None:
+            new["position_lr_final"] = 1.6e-6
+        new.update(spatial_lr_scale=None, feature_rest_lr_div=20.0, sh_degree_interval=1000)
+    return dataclasses.replace(opt, **new)
+
+
 # scripts/train.py:44-46 builds FSGS' three parameter groups on the parser; these are the flags of theirs that the reference's
-# bash_scripts/batch_{llff,dtu,dl3dv}_train.sh pass on the command line
+# bash_scripts/batch_{llff,dtu,dl3dv}_train.sh pass on the command line and that nothing here reads.  --svd_l1_weight
+# (batch_dl3dv_train.sh:87) belongs to the absent fork as well: its meaning is not visible, so it is accepted and ignored.
 FSGS_FLAGS = frozenset([
     "-s", "--source_path", "-m", "-r", "--resolution", "--images", "-i", "--eval", "--n_views", "--use_dust3r", "--rand_pcd",
     "--num_train_samples", "--sample_pseudo_interval", "--sample_svd_pseudo_interval", "--start_sample_svd_frame",
-    "--start_sample_pseudo", "--end_sample_pseudo", "--svd_depth_warmup", "--svd_lpips_weight",
-    "--percent_dense", "--densify_grad_threshold", "--densify_from_iter", "--densify_until_iter", "--densification_interval",
-    "--opacity_reset_interval", "--position_lr_init", "--position_lr_final", "--position_lr_max_steps", "--feature_lr",
-    "--opacity_lr", "--scaling_lr", "--rotation_lr", "--depth_pseudo_weight", "--white_background", "--sh_degree",
+    "--start_sample_pseudo", "--end_sample_pseudo", "--svd_depth_warmup", "--svd_lpips_weight", "--svd_l1_weight",
+    "--depth_pseudo_weight", "--white_background",
     "--data_device", "--convert_SHs_python", "--compute_cov3D_python", "--debug", "--checkpoint", "--video", "-a", "-p", "-f", "-d",
 ])
 # the types the orchestrator accepts (model/diffusionGS.py:115-124, :244-255; syn3r_amd/diffusionGS.py raises on the rest)
@@ -148,7 +196,8 @@ def synthetic_scene(name: str, args, device) -> dict:
     """`synthetic:<seed>[:<N>]` — a seeded Gaussian cloud rendered from three cameras on a baseline (the views to fit),
     a perturbed copy of it as the initial model, and two held-out cameras between the inputs for PSNR / SSIM.  Each training
     camera carries the truth cloud's disparity as its depth prior (`depth_image`: alpha / depth where alpha >= 0.5, else 0;
-    read only when `--depth_weight` > 0)."""
+    read only when `--depth_weight` > 0).  `--sh_degree` d (0..3): the model's largest SH degree; the 16 coefficient rows stay,
+    those above (d + 1)^2 are never read."""
     from .gs import Camera, GaussianModel, GSTrainer, OptimizationParams
     from .synthetic import synthetic_gaussians
     parts = name.split(":")
@@ -173,7 +222,8 @@ def synthetic_scene(name: str, args, device) -> dict:
              for dx in (-0.15, 0.0, 0.15)]
     test = [Camera.from_w2c(pose(dx), K, H, W, image=shot(dx), data_device=device) for dx in (-0.075, 0.075)]
     g = torch.Generator().manual_seed(seed + 1)
-    model = GaussianModel(m + 0.01 * torch.randn(m.shape, generator=g), torch.log(s), q, logit, sh, device=device)
+    sh_degree = 3 if getattr(args, "sh_degree", None) is None else int(args.sh_degree)
+    model = GaussianModel(m + 0.01 * torch.randn(m.shape, generator=g), torch.log(s), q, logit, sh, sh_degree=sh_degree, device=device)
     opt = OptimizationParams(iterations=args.iterations, lambda_dssim=args.lambda_dssim, seed=args.seed)
     out_dir = os.path.join(args.model_path, name.replace(":", "_"))
     trainer = GSTrainer(model, train, opt, model_path=out_dir, checkpoint_iterations=args.checkpoint_iterations)
@@ -233,6 +283,10 @@ def run_scene(name: str, args, device, factory: Callable) -> List[float]:
     trainer.opt.lpips_weight = float(getattr(args, "lpips_weight", 0.0))
     trainer.opt.depth_weight = float(getattr(args, "depth_weight", 0.0))
     trainer.opt.use_proximity_densify = bool(getattr(args, "use_proximity_densify", 0))
+    trainer.opt = apply_trainer_flags(trainer.opt, args)
+    if getattr(args, "gs_schedule", "constant") == "published" and trainer.iteration == 0:
+        trainer.gaussians.active_sh_degree = 0      # a fresh model (a factory that loaded a checkpoint has iteration > 0)
+    trainer.reset_optimizers()                      # the groups' rates and the features' row split follow the flags
     if sc.get("lpips") is not None:
         trainer.lpips = sc["lpips"]
     elif getattr(args, "lpips_weights", None):
