@@ -597,6 +597,39 @@ int syn3r_photo_loss_backward(const float* image, const float* target, int C, in
 int syn3r_photo_loss_step(const float* image, const float* target, int C, int H, int W, float lambda_dssim, float weight,
                           const float* grad_loss, float* loss3, float* grad_image, void* ws, size_t ws_bytes, void* stream);
 
+/* EXTENSION (not in the reference, which weights a whole pseudo-view by the scalar cam_confidence, model/diffusionGS.py:1631):
+ * the photometric loss with a per-pixel weight map m [H,W] fp32 shared by all channels (meant to lie in [0,1] and be finite;
+ * not validated on the device; it is data - no gradient with respect to it).  With ssim(c,p) the published SSIM map exactly
+ * as syn3r_photo_loss forms it - the map weights the per-pixel SSIM VALUE, it does not enter the window moments - and all
+ * means over the C*H*W elements (NOT divided by sum(m): a constant map m = k is the scalar weight k * weight, a map of ones
+ * is syn3r_photo_loss):
+ *   loss4[1] = mean(m |I - G|), loss4[2] = mean(m ssim), loss4[3] = mean(m),
+ *   loss4[0] = weight * ((1 - lambda_dssim) * loss4[1] + lambda_dssim * (loss4[3] - loss4[2]))
+ *   grad_image(c,q) = grad_loss[0] * weight / (C*H*W) * [ (1 - lambda_dssim) m(q) sign(I - G)(c,q)
+ *                     - lambda_dssim (win*(m d_mu1) + 2 I(c,q) win*(m d_sg1) + G(c,q) win*(m d_sg12))(c,q) ]
+ * d_mu1, d_sg1, d_sg12: the derivative maps of the SSIM value the forward stores, win*: the 11x11 separable window.
+ * Arguments as the three entries above plus map (H*W floats, device); loss4: 4 floats; ws:
+ * syn3r_photo_loss_map_workspace_bytes (3 sums per tile instead of 2), shared by forward and backward.  A null map, a null
+ * image or non-positive sizes are rejected (syn3r_last_error).  syn3r_photo_loss_map_step: same bits as
+ * syn3r_photo_loss_map + syn3r_photo_loss_map_backward. */
+size_t syn3r_photo_loss_map_workspace_bytes(int C, int H, int W);
+int syn3r_photo_loss_map(const float* image, const float* target, const float* map, int C, int H, int W, float lambda_dssim,
+                         float weight, float* loss4, void* ws, size_t ws_bytes, void* stream);
+int syn3r_photo_loss_map_backward(const float* image, const float* target, const float* map, int C, int H, int W,
+                                  float lambda_dssim, float weight, const float* grad_loss, const void* ws, float* grad_image,
+                                  void* stream);
+int syn3r_photo_loss_map_step(const float* image, const float* target, const float* map, int C, int H, int W, float lambda_dssim,
+                              float weight, const float* grad_loss, float* loss4, float* grad_image, void* ws, size_t ws_bytes,
+                              void* stream);
+/* The L1 pair with the same map: element i of the n = C * plane floats belongs to pixel i % plane (plane = H*W, so the flat index
+ * finds its pixel; n must be a multiple of plane):
+ *   loss[0] = weight * mean(m |image - target|) over n;  grad_image[i] = grad_loss[0] * weight / n * m[i % plane] * sign(image[i] - target[i])
+ * ws: syn3r_l1_loss_workspace_bytes(n).  Same rejections. */
+int syn3r_l1_loss_map(const float* image, const float* target, const float* map, long long n, long long plane, float weight,
+                      float* loss, void* ws, size_t ws_bytes, void* stream);
+int syn3r_l1_loss_map_backward(const float* image, const float* target, const float* map, long long n, long long plane,
+                               float weight, const float* grad_loss, float* grad_image, void* stream);
+
 /* FSGS' depth-correlation regulariser (Zhu et al., ECCV 2024, "geometry guidance"; the reference's batch scripts switch FSGS'
  * depth terms on, bash_scripts/batch_{llff,dl3dv}_train.sh --svd_depth_warmup 1; FSGS' trainer is not vendored) on one rendered
  * depth map d and one monocular prior p, n = H*W fp32 values each:

@@ -108,6 +108,12 @@ SIGNATURES = {
     "syn3r_photo_loss": (c_i, [c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_sz, c_p]),
     "syn3r_photo_loss_backward": (c_i, [c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_p]),
     "syn3r_photo_loss_step": (c_i, [c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "syn3r_photo_loss_map_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
+    "syn3r_photo_loss_map": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_sz, c_p]),
+    "syn3r_photo_loss_map_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_p]),
+    "syn3r_photo_loss_map_step": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "syn3r_l1_loss_map": (c_i, [c_p, c_p, c_p, c_ll, c_ll, c_f, c_p, c_p, c_sz, c_p]),
+    "syn3r_l1_loss_map_backward": (c_i, [c_p, c_p, c_p, c_ll, c_ll, c_f, c_p, c_p, c_p]),
     "syn3r_depth_corr_loss_workspace_bytes": (c_sz, [c_ll]),
     "syn3r_depth_corr_loss": (c_i, [c_p, c_p, c_ll, c_f, c_f, c_i, c_p, c_p, c_sz, c_p]),
     "syn3r_depth_corr_loss_backward": (c_i, [c_p, c_p, c_ll, c_f, c_f, c_i, c_p, c_p, c_sz, c_p, c_p]),

@@ -75,6 +75,88 @@ __global__ void __launch_bounds__(kThreads) k_l1_grad(const float* __restrict__ 
     }
 }
 
+// The L1 pair with a per-pixel weight map m [plane] shared by the n / plane channels (syn3r_l1_loss_map: an extension, see the
+// header): element i belongs to pixel i % plane.  A thread's group of four starts at pixel `pix`, found with ONE 64-bit
+// remainder before the grid-stride loop and advanced by the stride's remainder afterwards.  VEC: plane % 4 == 0 and m 16-byte
+// aligned, so the four weights are one aligned 16-byte load; else four loads whose pixel wraps at the plane's end.
+// i % plane for 0 <= i < 2^52, plane > 0: the quotient from one fp64 division (off by one at most, corrected) - a 64-bit integer
+// remainder is ~150 instructions, three of them were most of these kernels
+__device__ __forceinline__ long long l1_map_rem(long long i, long long plane) {
+    long long r = i - (long long)((double)i / (double)plane) * plane;
+    if (r < 0) r += plane;
+    if (r >= plane) r -= plane;
+    return r;
+}
+struct L1MapWalk { long long pix, step; };
+__device__ __forceinline__ L1MapWalk l1_map_walk(long long plane) {
+    L1MapWalk w;
+    w.pix = l1_map_rem(((long long)blockIdx.x * kThreads + threadIdx.x) * 4, plane);
+    w.step = l1_map_rem((long long)gridDim.x * kThreads * 4, plane);
+    return w;
+}
+template <bool VEC>
+__device__ __forceinline__ float4 l1_map_load4(const float* __restrict__ m, long long pix, long long plane) {
+    if constexpr (VEC) {
+        return *(const float4*)(m + pix);
+    } else {
+        long long p[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { p[e] = pix + e; if (p[e] >= plane) p[e] = l1_map_rem(p[e], plane); }
+        return make_float4(m[p[0]], m[p[1]], m[p[2]], m[p[3]]);
+    }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(kThreads) k_l1_partial_map(const float* __restrict__ a, const float* __restrict__ b,
+                                                            const float* __restrict__ m, long long n, long long plane,
+                                                            float* __restrict__ partial) {
+    float s = 0.0f;
+    const long long n4 = n >> 2;
+    const float4* a4 = (const float4*)a;
+    const float4* b4 = (const float4*)b;
+    L1MapWalk wk = l1_map_walk(plane);
+    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (long long)gridDim.x * kThreads) {
+        float4 x = a4[i], y = b4[i];
+        const float4 w = l1_map_load4<VEC>(m, wk.pix, plane);
+        s += (w.x * fabsf(x.x - y.x) + w.y * fabsf(x.y - y.y)) + (w.z * fabsf(x.z - y.z) + w.w * fabsf(x.w - y.w));
+        wk.pix += wk.step;
+        if (wk.pix >= plane) wk.pix -= plane;
+    }
+    if (blockIdx.x == 0) {
+        long long i = (n4 << 2) + threadIdx.x;
+        if (i < n) s += m[l1_map_rem(i, plane)] * fabsf(a[i] - b[i]);
+    }
+    s = wave_sum(s);
+    __shared__ float ws[kThreads / 64];
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(kThreads) k_l1_grad_map(const float* __restrict__ a, const float* __restrict__ b,
+                                                         const float* __restrict__ m, long long n, long long plane, float scale,
+                                                         const float* __restrict__ go, float* __restrict__ grad) {
+    const float g = scale * (go ? *go : 1.0f);
+    auto sgn = [g](float d) { return d > 0.0f ? g : (d < 0.0f ? -g : 0.0f); };   // torch.sign: 0 at 0
+    const long long n4 = n >> 2;
+    const float4* a4 = (const float4*)a;
+    const float4* b4 = (const float4*)b;
+    float4* g4 = (float4*)grad;
+    L1MapWalk wk = l1_map_walk(plane);
+    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (long long)gridDim.x * kThreads) {
+        float4 x = a4[i], y = b4[i];
+        const float4 w = l1_map_load4<VEC>(m, wk.pix, plane);
+        g4[i] = make_float4(w.x * sgn(x.x - y.x), w.y * sgn(x.y - y.y), w.z * sgn(x.z - y.z), w.w * sgn(x.w - y.w));
+        wk.pix += wk.step;
+        if (wk.pix >= plane) wk.pix -= plane;
+    }
+    if (blockIdx.x == 0) {
+        long long i = (n4 << 2) + threadIdx.x;
+        if (i < n) grad[i] = m[l1_map_rem(i, plane)] * sgn(a[i] - b[i]);
+    }
+}
+
 // torch.optim.Adam (_single_tensor_adam / _multi_tensor_adam, no weight decay, no amsgrad, not maximize):
 //   exp_avg.lerp_(grad, 1 - beta1);  exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
 //   denom = exp_avg_sq.sqrt() / sqrt(1 - beta2^t) + eps;  param.addcdiv_(exp_avg, denom, value = -lr / (1 - beta1^t))
@@ -287,10 +369,33 @@ __device__ __forceinline__ void photo_load20(float (&v)[20], const float* __rest
     }
 }
 
+// The weights of an item's own four pixels (row y, columns x .. x + 3; x % 4 == 0): photo_load20's rule - an unconditional load
+// from a clamped address, zero outside the image by a select afterwards.
 template <bool VEC>
+__device__ __forceinline__ void photo_load4(float (&v)[kRun], const float* __restrict__ plane, int y, int x, int H, int W) {
+    const bool row = y >= 0 && y < H;
+    const float* src = plane + (size_t)min(max(y, 0), H - 1) * W;
+    if constexpr (VEC) {
+        const float4 t = *(const float4*)(src + min(x, W - 4));
+        const bool in = row && x < W;
+        v[0] = in ? t.x : 0.0f; v[1] = in ? t.y : 0.0f; v[2] = in ? t.z : 0.0f; v[3] = in ? t.w : 0.0f;
+    } else {
+        float t[kRun];
+#pragma unroll
+        for (int e = 0; e < kRun; ++e) t[e] = src[min(x + e, W - 1)];
+#pragma unroll
+        for (int e = 0; e < kRun; ++e) v[e] = (row && x + e < W) ? t[e] : 0.0f;
+    }
+}
+
+// MAP: the per-pixel weight map `wmap` [H,W] of syn3r_photo_loss_map (one map for all channels) multiplies the L1 term and the SSIM
+// map VALUE at the output pixel - so the three stored derivative maps carry it and the backward's window needs nothing new -; it
+// does not enter the window moments.  The tile's sums become (sum m|d|, sum m ssim, sum m): 3 floats per tile instead of 2.
+// MAP = false is the kernel without a map: `wmap` is never read, no branch is added.
+template <bool VEC, bool MAP>
 __global__ void __launch_bounds__(kPhotoThreads) k_photo_fwd(const float* __restrict__ img, const float* __restrict__ gt, int H,
                                                    int W, int C, SsimWindow win, float* __restrict__ maps,
-                                                   float* __restrict__ partial) {
+                                                   float* __restrict__ partial, const float* __restrict__ wmap) {
     __shared__ __attribute__((aligned(16))) f2 hA[kReg][kTile], hB[kReg][kTile];   // (mu1, mu2), (E[p^2], E[q^2]) after the horizontal pass
     __shared__ __attribute__((aligned(16))) float hC[kReg][kTile];                 // E[pq]
     __shared__ float red[kPhotoThreads / 64];
@@ -300,6 +405,13 @@ __global__ void __launch_bounds__(kPhotoThreads) k_photo_fwd(const float* __rest
     const float* a = img + c * plane;
     const float* b = gt + c * plane;
     float l1_sum = 0.f;
+    // MAP: the weights of the vertical pass' own pixels (column tx, rows ty .. ty + 3), requested before the horizontal pass
+    float mv[kRun];
+    if constexpr (MAP) {
+#pragma unroll
+        for (int j = 0; j < kRun; ++j)
+            mv[j] = wmap[(size_t)min(y0 + (int)(threadIdx.x >> 5) * kRun + j, H - 1) * W + min(x0 + (int)(threadIdx.x & (kTile - 1)), W - 1)];     // (clamped: rows / columns past the image are not summed)
+    }
     // horizontal pass: item = (halo row, run of 4 columns)
     for (int i = threadIdx.x; i < kPhotoItems; i += kPhotoThreads) {
         const int ry = i / (kTile / kRun), tx = (i - ry * (kTile / kRun)) * kRun;
@@ -307,6 +419,8 @@ __global__ void __launch_bounds__(kPhotoThreads) k_photo_fwd(const float* __rest
         float p[20], q[20];
         photo_load20<VEC>(p, a, y, x0 + tx - 8, H, W);
         photo_load20<VEC>(q, b, y, x0 + tx - 8, H, W);
+        float mh[kRun];
+        if constexpr (MAP) photo_load4<VEC>(mh, wmap, y, x0 + tx, H, W);
         f2 pq[kSpan], sq[kSpan];
         float pr[kSpan];
 #pragma unroll
@@ -337,7 +451,10 @@ __global__ void __launch_bounds__(kPhotoThreads) k_photo_fwd(const float* __rest
         if (ry >= kHalo && ry < kHalo + kTile && y < H) {      // an output row: its L1 terms (the run's own pixels are inputs kHalo .. kHalo + 3)
 #pragma unroll
             for (int j = 0; j < kRun; ++j)
-                if (x0 + tx + j < W) l1_sum += fabsf(pq[kHalo + j].x - pq[kHalo + j].y);
+                if (x0 + tx + j < W) {
+                    if constexpr (MAP) l1_sum += mh[j] * fabsf(pq[kHalo + j].x - pq[kHalo + j].y);
+                    else l1_sum += fabsf(pq[kHalo + j].x - pq[kHalo + j].y);
+                }
         }
     }
     __syncthreads();
@@ -364,7 +481,7 @@ __global__ void __launch_bounds__(kPhotoThreads) k_photo_fwd(const float* __rest
             }
         }
     }
-    float ssim_sum = 0.f;
+    float ssim_sum = 0.f, m_sum = 0.f;
     const size_t n = (size_t)C * plane;
 #pragma unroll
     for (int j = 0; j < kRun; ++j) {
@@ -386,13 +503,28 @@ __global__ void __launch_bounds__(kPhotoThreads) k_photo_fwd(const float* __rest
             const float d_mu1 = (2.f * mu2 * B * Cc - 2.f * mu1 * A * B) * inv * invC    // explicit
                                 - 2.f * mu1 * d_sg1 - mu2 * d_sg12;                      // through sigma1^2, sigma12
             const size_t o = (size_t)c * plane + (size_t)y * W + x;
-            maps[o] = d_mu1; maps[n + o] = d_sg1; maps[2 * n + o] = d_sg12;
-            ssim_sum += ssim;
+            if constexpr (MAP) {
+                const float m = mv[j];
+                maps[o] = m * d_mu1; maps[n + o] = m * d_sg1; maps[2 * n + o] = m * d_sg12;
+                ssim_sum += m * ssim;
+                m_sum += m;
+            } else {
+                maps[o] = d_mu1; maps[n + o] = d_sg1; maps[2 * n + o] = d_sg12;
+                ssim_sum += ssim;
+            }
         }
     }
     const float ts = block_sum_photo(ssim_sum, red);
     const float tl = block_sum_photo(l1_sum, red);
-    if (threadIdx.x == 0) {
+    if constexpr (MAP) {
+        const float tm = block_sum_photo(m_sum, red);
+        if (threadIdx.x == 0) {
+            const size_t bid = tl_.id;
+            partial[3 * bid] = tl;
+            partial[3 * bid + 1] = ts;
+            partial[3 * bid + 2] = tm;
+        }
+    } else if (threadIdx.x == 0) {
         const size_t bid = tl_.id;
         partial[2 * bid] = tl;
         partial[2 * bid + 1] = ts;
@@ -400,33 +532,54 @@ __global__ void __launch_bounds__(kPhotoThreads) k_photo_fwd(const float* __rest
 }
 
 // loss[0] = w*((1-lam)*L1 + lam*(1-SSIM)), loss[1] = L1, loss[2] = SSIM  (fixed-order double sums; a block of 256 threads)
+// MAP (3 floats per tile, 4 outputs): loss[1] = mean(m|d|), loss[2] = mean(m ssim), loss[3] = mean(m),
+// loss[0] = w*((1-lam)*loss[1] + lam*(loss[3] - loss[2])) - all means over the C*H*W elements
 struct PhotoFinal { const float* partial; long long nblocks; double inv_n; float lam, weight; float* loss; };
+template <bool MAP>
 __device__ __forceinline__ void photo_final(const PhotoFinal f) {
     static_assert(kPhotoThreads == 256, "photo_final: one sum per thread of a 256-thread block");
-    double sl = 0.0, ss = 0.0;
-    for (long long i = threadIdx.x; i < f.nblocks; i += 256) { sl += (double)f.partial[2 * i]; ss += (double)f.partial[2 * i + 1]; }
+    constexpr int kPer = MAP ? 3 : 2;
+    double sl = 0.0, ss = 0.0, sm = 0.0;
+    for (long long i = threadIdx.x; i < f.nblocks; i += 256) {
+        sl += (double)f.partial[kPer * i]; ss += (double)f.partial[kPer * i + 1];
+        if constexpr (MAP) sm += (double)f.partial[kPer * i + 2];
+    }
     sl = wave_sum_d(sl); ss = wave_sum_d(ss);
+    if constexpr (MAP) sm = wave_sum_d(sm);
     __shared__ double w1[4], w2[4];
-    if ((threadIdx.x & 63) == 0) { w1[threadIdx.x >> 6] = sl; w2[threadIdx.x >> 6] = ss; }
+    double* w3 = nullptr;
+    if constexpr (MAP) { __shared__ double w3s[4]; w3 = w3s; }
+    if ((threadIdx.x & 63) == 0) {
+        w1[threadIdx.x >> 6] = sl; w2[threadIdx.x >> 6] = ss;
+        if constexpr (MAP) w3[threadIdx.x >> 6] = sm;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         const double l1 = ((w1[0] + w1[1]) + (w1[2] + w1[3])) * f.inv_n, ssim = ((w2[0] + w2[1]) + (w2[2] + w2[3])) * f.inv_n;
-        f.loss[0] = (float)((double)f.weight * ((1.0 - (double)f.lam) * l1 + (double)f.lam * (1.0 - ssim)));
+        if constexpr (MAP) {
+            const double mm = ((w3[0] + w3[1]) + (w3[2] + w3[3])) * f.inv_n;
+            f.loss[0] = (float)((double)f.weight * ((1.0 - (double)f.lam) * l1 + (double)f.lam * (mm - ssim)));
+            f.loss[3] = (float)mm;
+        } else {
+            f.loss[0] = (float)((double)f.weight * ((1.0 - (double)f.lam) * l1 + (double)f.lam * (1.0 - ssim)));
+        }
         f.loss[1] = (float)l1;
         f.loss[2] = (float)ssim;
     }
 }
-__global__ void __launch_bounds__(256) k_photo_final(PhotoFinal f) { photo_final(f); }
+__global__ void __launch_bounds__(256) k_photo_final(PhotoFinal f) { photo_final<false>(f); }
+__global__ void __launch_bounds__(256) k_photo_final_map(PhotoFinal f) { photo_final<true>(f); }
 
-template <bool VEC>
+// MAP: the L1 sign term takes the weight m(q) of its own pixel; the windowed part reads derivative maps that already carry it
+template <bool VEC, bool MAP>
 __global__ void __launch_bounds__(kPhotoThreads) k_photo_bwd(const float* __restrict__ img, const float* __restrict__ gt, int H,
                                                    int W, int C, SsimWindow win, const float* __restrict__ maps, float c_l1,
                                                    float c_ssim, const float* __restrict__ go,
-                                                   float* __restrict__ grad, PhotoFinal fin) {
+                                                   float* __restrict__ grad, PhotoFinal fin, const float* __restrict__ wmap) {
     __shared__ __attribute__((aligned(16))) f2 hA[kReg][kTile];      // windowed (d_mu1, d_sigma1^2) after the horizontal pass
     // syn3r_photo_loss_step: the forward's per-tile sums become loss3 HERE (k_photo_final's fixed-order double sums, by the block
     // that is dispatched first) instead of in a single-block launch between the two passes: the gradient does not read the loss
-    if (fin.partial && blockIdx.x == 0) photo_final(fin);
+    if (fin.partial && blockIdx.x == 0) photo_final<MAP>(fin);
     __shared__ __attribute__((aligned(16))) float hC[kReg][kTile];   // windowed d_sigma12
     const PhotoTile tl_ = photo_tile((W + kTile - 1) / kTile, (H + kTile - 1) / kTile);
     const int c = tl_.c, x0 = tl_.x0, y0 = tl_.y0;
@@ -434,12 +587,13 @@ __global__ void __launch_bounds__(kPhotoThreads) k_photo_bwd(const float* __rest
     const float* m0 = maps + c * plane;
     // the vertical pass' own pixels (column tx, rows ty .. ty + 3), requested before the horizontal pass
     const int vtx = threadIdx.x & (kTile - 1), vty = (threadIdx.x >> 5) * kRun;
-    float pv[kRun], qv[kRun];
+    float pv[kRun], qv[kRun], mv[kRun];
 #pragma unroll
     for (int j = 0; j < kRun; ++j) {
         const size_t o = (size_t)c * plane + (size_t)min(y0 + vty + j, H - 1) * W + min(x0 + vtx, W - 1);     // (clamped: rows / columns past the image are not written)
         pv[j] = img[o];
         qv[j] = gt[o];
+        if constexpr (MAP) mv[j] = wmap[o - (size_t)c * plane];
     }
     for (int i = threadIdx.x; i < kPhotoItems; i += kPhotoThreads) {
         const int ry = i / (kTile / kRun), tx = (i - ry * (kTile / kRun)) * kRun;
@@ -495,7 +649,8 @@ __global__ void __launch_bounds__(kPhotoThreads) k_photo_bwd(const float* __rest
         const size_t o = (size_t)c * plane + (size_t)y * W + x;
         const float p = pv[j], q = qv[j], d = p - q;
         const float sgn = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
-        grad[o] = up * (c_l1 * sgn - c_ssim * (gA[j].x + 2.0f * p * gA[j].y + q * gC[j]));
+        if constexpr (MAP) grad[o] = up * (c_l1 * (mv[j] * sgn) - c_ssim * (gA[j].x + 2.0f * p * gA[j].y + q * gC[j]));
+        else grad[o] = up * (c_l1 * sgn - c_ssim * (gA[j].x + 2.0f * p * gA[j].y + q * gC[j]));
     }
 }
 
@@ -551,6 +706,44 @@ extern "C" int syn3r_l1_loss_backward(const float* image, const float* target, l
     SYN3R_LAUNCH(k_l1_grad, dim3((unsigned)b), dim3(kThreads), 0, stream, image, target, n, weight / (float)n,
                  grad_loss, grad_image);
     SYN3R_LAUNCH_CHECK("l1_loss_backward launch");
+    return SYN3R_OK;
+}
+
+// one 16-byte load of four weights: the plane is whole groups of four and the map is aligned
+static bool l1_map_vec(const float* map, long long plane) { return plane % 4 == 0 && ((uintptr_t)map & 15) == 0; }
+
+extern "C" int syn3r_l1_loss_map(const float* image, const float* target, const float* map, long long n, long long plane,
+                                 float weight, float* loss, void* ws, size_t ws_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    SYN3R_REQUIRE(n > 0 && plane > 0 && n % plane == 0, "l1_loss_map: n and plane must be positive, n a multiple of plane");
+    SYN3R_REQUIRE(map, "l1_loss_map: null map");
+    SYN3R_REQUIRE(image && target && loss && ws, "l1_loss_map: null pointer");
+    SYN3R_REQUIRE(ws_bytes >= syn3r_l1_loss_workspace_bytes(n), "l1_loss_map: workspace too small");
+    SYN3R_REQUIRE((((uintptr_t)image | (uintptr_t)target) & 15) == 0, "l1_loss_map: image/target must be 16-byte aligned");
+    const int nb = l1_blocks(n);
+    if (l1_map_vec(map, plane)) SYN3R_LAUNCH(k_l1_partial_map<true>, dim3(nb), dim3(kThreads), 0, stream, image, target, map, n, plane, (float*)ws);
+    else SYN3R_LAUNCH(k_l1_partial_map<false>, dim3(nb), dim3(kThreads), 0, stream, image, target, map, n, plane, (float*)ws);
+    SYN3R_LAUNCH(k_l1_final, dim3(1), dim3(kThreads), 0, stream, (const float*)ws, nb, weight / (float)n, loss);
+    SYN3R_LAUNCH_CHECK("l1_loss_map launch");
+    return SYN3R_OK;
+}
+
+extern "C" int syn3r_l1_loss_map_backward(const float* image, const float* target, const float* map, long long n, long long plane,
+                                          float weight, const float* grad_loss, float* grad_image, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    SYN3R_REQUIRE(n > 0 && plane > 0 && n % plane == 0, "l1_loss_map_backward: n and plane must be positive, n a multiple of plane");
+    SYN3R_REQUIRE(map, "l1_loss_map_backward: null map");
+    SYN3R_REQUIRE(image && target && grad_image, "l1_loss_map_backward: null pointer");
+    SYN3R_REQUIRE((((uintptr_t)image | (uintptr_t)target | (uintptr_t)grad_image) & 15) == 0,
+                  "l1_loss_map_backward: buffers must be 16-byte aligned");
+    long long b = (n / 4 + kThreads * 4 - 1) / (kThreads * 4);
+    if (b < 1) b = 1;
+    if (b > 4 * kMaxBlocks) b = 4 * kMaxBlocks;
+    if (l1_map_vec(map, plane)) SYN3R_LAUNCH(k_l1_grad_map<true>, dim3((unsigned)b), dim3(kThreads), 0, stream, image, target, map, n, plane,
+                                             weight / (float)n, grad_loss, grad_image);
+    else SYN3R_LAUNCH(k_l1_grad_map<false>, dim3((unsigned)b), dim3(kThreads), 0, stream, image, target, map, n, plane,
+                      weight / (float)n, grad_loss, grad_image);
+    SYN3R_LAUNCH_CHECK("l1_loss_map_backward launch");
     return SYN3R_OK;
 }
 
@@ -691,36 +884,47 @@ static SsimWindow make_window() {
     return w;
 }
 
-extern "C" size_t syn3r_photo_loss_workspace_bytes(int C, int H, int W) {
+// the three derivative maps, then `per_tile` floats of sums per tile
+static size_t photo_workspace_bytes(int C, int H, int W, size_t per_tile) {
     if (C <= 0 || C > 65535 || !SYN3R_SIDE_OK(H) || !SYN3R_SIDE_OK(W)) return 0;
     const size_t n = (size_t)C * H * W;
     const size_t blocks = (size_t)C * ((H + kTile - 1) / kTile) * ((W + kTile - 1) / kTile);
-    return 3 * n * sizeof(float) + ((2 * blocks * sizeof(float) + 255) / 256) * 256;
+    return 3 * n * sizeof(float) + ((per_tile * blocks * sizeof(float) + 255) / 256) * 256;
 }
+extern "C" size_t syn3r_photo_loss_workspace_bytes(int C, int H, int W) { return photo_workspace_bytes(C, H, W, 2); }
+extern "C" size_t syn3r_photo_loss_map_workspace_bytes(int C, int H, int W) { return photo_workspace_bytes(C, H, W, 3); }
 
-// forward pass (k_photo_fwd) of both entries; `final_launch`: loss3 by k_photo_final (syn3r_photo_loss) or left to the backward
-static int photo_forward(const char* who, const float* image, const float* target, int C, int H, int W, float lambda_dssim,
+// forward pass (k_photo_fwd) of both entries; `final_launch`: loss3 by k_photo_final (syn3r_photo_loss) or left to the backward.
+// `map` (the syn3r_photo_loss_map entries; null: none): the k_photo_*_map kernels, 3 sums per tile and 4 floats in loss3.
+static int photo_forward(const char* who, const float* image, const float* target, const float* map, int C, int H, int W, float lambda_dssim,
                          float weight, float* loss3, void* ws, size_t ws_bytes, hipStream_t stream, bool final_launch, PhotoFinal* fin) {
     SYN3R_REQUIRE(C > 0 && C <= 65535 && SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W), "%s: bad sizes C=%d H=%d W=%d", who, C, H, W);
     SYN3R_REQUIRE(image && target && loss3 && ws, "%s: null pointer", who);
     SYN3R_REQUIRE(lambda_dssim >= 0.0f && lambda_dssim <= 1.0f, "%s: lambda_dssim must be in [0, 1]", who);
-    SYN3R_REQUIRE(ws_bytes >= syn3r_photo_loss_workspace_bytes(C, H, W), "%s: workspace too small", who);
+    SYN3R_REQUIRE(ws_bytes >= photo_workspace_bytes(C, H, W, map ? 3 : 2), "%s: workspace too small", who);
     const size_t n = (size_t)C * H * W;
     float* maps = (float*)ws;
     float* partial = maps + 3 * n;
     const long long tiles = (long long)((W + kTile - 1) / kTile) * ((H + kTile - 1) / kTile) * C;
     SYN3R_REQUIRE(tiles < (1ll << 31), "%s: %lld tiles exceed the grid limit", who, tiles);
     const dim3 grid((unsigned)tiles);
-    const bool vec = W % 4 == 0 && (((uintptr_t)image | (uintptr_t)target) & 15) == 0;      // aligned 16-byte row runs
-    if (vec) SYN3R_LAUNCH(k_photo_fwd<true>, grid, dim3(kPhotoThreads), 0, stream, image, target, H, W, C, make_window(), maps, partial);
-    else SYN3R_LAUNCH(k_photo_fwd<false>, grid, dim3(kPhotoThreads), 0, stream, image, target, H, W, C, make_window(), maps, partial);
+    const bool vec = W % 4 == 0 && (((uintptr_t)image | (uintptr_t)target | (uintptr_t)map) & 15) == 0;      // aligned 16-byte row runs
     const PhotoFinal f{partial, (long long)grid.x, 1.0 / (double)n, lambda_dssim, weight, loss3};
+    if (map) {
+        if (vec) SYN3R_LAUNCH_NAMED("k_photo_fwd_map<true>", (k_photo_fwd<true, true>), grid, dim3(kPhotoThreads), 0, stream, image, target, H, W, C, make_window(), maps, partial, map);
+        else SYN3R_LAUNCH_NAMED("k_photo_fwd_map<false>", (k_photo_fwd<false, true>), grid, dim3(kPhotoThreads), 0, stream, image, target, H, W, C, make_window(), maps, partial, map);
+        if (final_launch) SYN3R_LAUNCH(k_photo_final_map, dim3(1), dim3(256), 0, stream, f);
+        if (fin) *fin = f;
+        return SYN3R_OK;
+    }
+    if (vec) SYN3R_LAUNCH_NAMED("k_photo_fwd<true>", (k_photo_fwd<true, false>), grid, dim3(kPhotoThreads), 0, stream, image, target, H, W, C, make_window(), maps, partial, map);
+    else SYN3R_LAUNCH_NAMED("k_photo_fwd<false>", (k_photo_fwd<false, false>), grid, dim3(kPhotoThreads), 0, stream, image, target, H, W, C, make_window(), maps, partial, map);
     if (final_launch) SYN3R_LAUNCH(k_photo_final, dim3(1), dim3(256), 0, stream, f);
     if (fin) *fin = f;
     return SYN3R_OK;
 }
 
-static int photo_backward(const char* who, const float* image, const float* target, int C, int H, int W, float lambda_dssim,
+static int photo_backward(const char* who, const float* image, const float* target, const float* map, int C, int H, int W, float lambda_dssim,
                           float weight, const float* grad_loss, const void* ws, float* grad_image, hipStream_t stream, PhotoFinal fin) {
     SYN3R_REQUIRE(C > 0 && C <= 65535 && SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W), "%s: bad sizes", who);
     SYN3R_REQUIRE(image && target && ws && grad_image, "%s: null pointer", who);
@@ -730,16 +934,23 @@ static int photo_backward(const char* who, const float* image, const float* targ
     const dim3 grid((unsigned)tiles);
     const bool vec = W % 4 == 0 && ((uintptr_t)ws & 15) == 0;
     const float c_l1 = (float)((double)weight * (1.0 - (double)lambda_dssim) / n), c_ssim = (float)((double)weight * (double)lambda_dssim / n);
-    if (vec) SYN3R_LAUNCH(k_photo_bwd<true>, grid, dim3(kPhotoThreads), 0, stream, image, target, H, W, C, make_window(), (const float*)ws,
-                          c_l1, c_ssim, grad_loss, grad_image, fin);
-    else SYN3R_LAUNCH(k_photo_bwd<false>, grid, dim3(kPhotoThreads), 0, stream, image, target, H, W, C, make_window(), (const float*)ws,
-                      c_l1, c_ssim, grad_loss, grad_image, fin);
+    if (map) {
+        if (vec) SYN3R_LAUNCH_NAMED("k_photo_bwd_map<true>", (k_photo_bwd<true, true>), grid, dim3(kPhotoThreads), 0, stream, image, target, H, W, C, make_window(),
+                                    (const float*)ws, c_l1, c_ssim, grad_loss, grad_image, fin, map);
+        else SYN3R_LAUNCH_NAMED("k_photo_bwd_map<false>", (k_photo_bwd<false, true>), grid, dim3(kPhotoThreads), 0, stream, image, target, H, W, C, make_window(),
+                                (const float*)ws, c_l1, c_ssim, grad_loss, grad_image, fin, map);
+        return SYN3R_OK;
+    }
+    if (vec) SYN3R_LAUNCH_NAMED("k_photo_bwd<true>", (k_photo_bwd<true, false>), grid, dim3(kPhotoThreads), 0, stream, image, target, H, W, C, make_window(),
+                                (const float*)ws, c_l1, c_ssim, grad_loss, grad_image, fin, map);
+    else SYN3R_LAUNCH_NAMED("k_photo_bwd<false>", (k_photo_bwd<false, false>), grid, dim3(kPhotoThreads), 0, stream, image, target, H, W, C, make_window(),
+                            (const float*)ws, c_l1, c_ssim, grad_loss, grad_image, fin, map);
     return SYN3R_OK;
 }
 
 extern "C" int syn3r_photo_loss(const float* image, const float* target, int C, int H, int W, float lambda_dssim,
                                 float weight, float* loss3, void* ws, size_t ws_bytes, void* stream_) {
-    const int rc = photo_forward("photo_loss", image, target, C, H, W, lambda_dssim, weight, loss3, ws, ws_bytes, (hipStream_t)stream_,
+    const int rc = photo_forward("photo_loss", image, target, nullptr, C, H, W, lambda_dssim, weight, loss3, ws, ws_bytes, (hipStream_t)stream_,
                                  true, nullptr);
     if (rc) return rc;
     SYN3R_LAUNCH_CHECK("photo_loss launch");
@@ -749,7 +960,7 @@ extern "C" int syn3r_photo_loss(const float* image, const float* target, int C, 
 extern "C" int syn3r_photo_loss_backward(const float* image, const float* target, int C, int H, int W,
                                          float lambda_dssim, float weight, const float* grad_loss, const void* ws,
                                          float* grad_image, void* stream_) {
-    const int rc = photo_backward("photo_loss_backward", image, target, C, H, W, lambda_dssim, weight, grad_loss, ws, grad_image,
+    const int rc = photo_backward("photo_loss_backward", image, target, nullptr, C, H, W, lambda_dssim, weight, grad_loss, ws, grad_image,
                                   (hipStream_t)stream_, PhotoFinal{});
     if (rc) return rc;
     SYN3R_LAUNCH_CHECK("photo_loss_backward launch");
@@ -760,12 +971,49 @@ extern "C" int syn3r_photo_loss_step(const float* image, const float* target, in
                                      float weight, const float* grad_loss, float* loss3, float* grad_image, void* ws,
                                      size_t ws_bytes, void* stream_) {
     PhotoFinal fin{};
-    int rc = photo_forward("photo_loss_step", image, target, C, H, W, lambda_dssim, weight, loss3, ws, ws_bytes, (hipStream_t)stream_,
+    int rc = photo_forward("photo_loss_step", image, target, nullptr, C, H, W, lambda_dssim, weight, loss3, ws, ws_bytes, (hipStream_t)stream_,
                            false, &fin);
     if (rc) return rc;
-    rc = photo_backward("photo_loss_step", image, target, C, H, W, lambda_dssim, weight, grad_loss, ws, grad_image,
+    rc = photo_backward("photo_loss_step", image, target, nullptr, C, H, W, lambda_dssim, weight, grad_loss, ws, grad_image,
                         (hipStream_t)stream_, fin);
     if (rc) return rc;
     SYN3R_LAUNCH_CHECK("photo_loss_step launch");
+    return SYN3R_OK;
+}
+
+// ---- the same three entries with a per-pixel weight map (an extension: include/syn3r_hip.h)
+extern "C" int syn3r_photo_loss_map(const float* image, const float* target, const float* map, int C, int H, int W, float lambda_dssim,
+                                    float weight, float* loss4, void* ws, size_t ws_bytes, void* stream_) {
+    SYN3R_REQUIRE(map, "photo_loss_map: null map");
+    const int rc = photo_forward("photo_loss_map", image, target, map, C, H, W, lambda_dssim, weight, loss4, ws, ws_bytes,
+                                 (hipStream_t)stream_, true, nullptr);
+    if (rc) return rc;
+    SYN3R_LAUNCH_CHECK("photo_loss_map launch");
+    return SYN3R_OK;
+}
+
+extern "C" int syn3r_photo_loss_map_backward(const float* image, const float* target, const float* map, int C, int H, int W,
+                                             float lambda_dssim, float weight, const float* grad_loss, const void* ws,
+                                             float* grad_image, void* stream_) {
+    SYN3R_REQUIRE(map, "photo_loss_map_backward: null map");
+    const int rc = photo_backward("photo_loss_map_backward", image, target, map, C, H, W, lambda_dssim, weight, grad_loss, ws, grad_image,
+                                  (hipStream_t)stream_, PhotoFinal{});
+    if (rc) return rc;
+    SYN3R_LAUNCH_CHECK("photo_loss_map_backward launch");
+    return SYN3R_OK;
+}
+
+extern "C" int syn3r_photo_loss_map_step(const float* image, const float* target, const float* map, int C, int H, int W,
+                                         float lambda_dssim, float weight, const float* grad_loss, float* loss4, float* grad_image,
+                                         void* ws, size_t ws_bytes, void* stream_) {
+    SYN3R_REQUIRE(map, "photo_loss_map_step: null map");
+    PhotoFinal fin{};
+    int rc = photo_forward("photo_loss_map_step", image, target, map, C, H, W, lambda_dssim, weight, loss4, ws, ws_bytes,
+                           (hipStream_t)stream_, false, &fin);
+    if (rc) return rc;
+    rc = photo_backward("photo_loss_map_step", image, target, map, C, H, W, lambda_dssim, weight, grad_loss, ws, grad_image,
+                        (hipStream_t)stream_, fin);
+    if (rc) return rc;
+    SYN3R_LAUNCH_CHECK("photo_loss_map_step launch");
     return SYN3R_OK;
 }

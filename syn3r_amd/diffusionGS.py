@@ -2,7 +2,7 @@
 
 `DiffusionGS(GSTrainer, num_input_views, save_dir, diffusion_type, interp_type, debug, input_args).run(refine_cycles)`
 keeps the reference's constructor, method names, artefact names (`dense_views…cyc{c}_view{i}.pt` with keys `views`,
-`poses`) and control flow:
+`poses`; a third key `confidence_maps` only with the `args.pixel_confidence` extension) and control flow:
 
     init_GS -> for each cycle: densify_views (per view pair: _interpolate_between_gs_v3 -> svd_render) -> refine_GS
 
@@ -59,6 +59,11 @@ def _resize_nearest_t(x: torch.Tensor, height: int, width: int) -> torch.Tensor:
     return x.index_select(0, ys).index_select(1, xs)
 
 
+def _pixel_confidence(runner) -> bool:
+    """`args.pixel_confidence` (EXTENSION, default 0): keep the interpolation's fused uncertainty as per-pixel confidence maps."""
+    return bool(getattr(getattr(runner, "args", None), "pixel_confidence", 0))
+
+
 class DiffusionGS:
     def __init__(self, GSTrainer, num_input_views=12, save_dir=None, diffusion_type="2Pass", interp_type="forward_warp",
                  debug=False, input_args=None, svd_components: Optional[dict] = None, num_inference_steps: int = 100,
@@ -67,6 +72,9 @@ class DiffusionGS:
         self.cam_confidence = self.args.cam_confidence
         self.pseudo_cam_sampling_rate = self.args.pseudo_cam_sampling_rate
         self.fps_keyframe_sampling = getattr(self.args, "fps_keyframe_sampling", 0)
+        # EXTENSION (off by default, not in the reference): per-pixel confidence maps of the pseudo-views, see densify_views
+        self._pair_confidence_maps = None            # of the pair _interpolate_between_gs_v3 handled last (one entry per frame)
+        self.dense_confidence_maps = None            # parallel to densify_views' dense_views
         self.debug = debug
         self.gsTrainer = GSTrainer
         self.dust3r = getattr(GSTrainer, "dust3r", None)
@@ -167,7 +175,11 @@ class DiffusionGS:
         return [frames[i] for i in range(frames.shape[0])]          # [H,W,3] float in [0,1] per frame
 
     def _interpolate_between_gs_v3(self, idx1, idx2, replace=True, perturb_interp_poses=True):
-        """diffusionGS.py:774-923."""
+        """diffusionGS.py:774-923.  With `args.pixel_confidence` (EXTENSION) the fused uncertainty of the inner frames is kept
+        instead of discarded: `self._pair_confidence_maps` = `O.confidence_maps_from_uncertainty` of it, one entry per returned
+        frame (None for the two end frames; all None on the forward_warp branch, which has no soft uncertainty).  The return
+        value is the same either way."""
+        self._pair_confidence_maps = None
         pose1, image1, depth1 = self.render_GS(idx1)
         pose2, image2, depth2 = self.render_GS(idx2)
         interpolated_poses = list(O.pose_interpolation(pose1, pose2))
@@ -186,6 +198,8 @@ class DiffusionGS:
             depth_dev[id(p)] = dp
         rs = lambda x: _resize_nearest(x, Hd, Wd)
         if self.interp_type == "forward_warp":
+            if _pixel_confidence(self):
+                self._pair_confidence_maps = [None] * len(interpolated_poses)
             return self._finish_forward_warp(interpolated_poses, image1, image2, depth1, depth2, pseudo_images, replace)
         # warps, mask post-processing and the uncertainty fusion stay on the device: one
         # batched warp per end view + two post-processing launches; the condition images go to the pipeline as
@@ -196,8 +210,10 @@ class DiffusionGS:
             h=Hd // 8, w=Wd // 8)
         image_o, image_o2 = rs(image1) / 255.0, rs(image2) / 255.0
         gs_images = torch.stack(pseudo_images[1:-1])
-        masks, cond_dev, _ = O.fuse_uncertainty_device(wd["cond_images_ori"], gs_images, wd["soft_masks_reproj_ori"],
-                                                       h=Hd // 8, w=Wd // 8)
+        masks, cond_dev, unc = O.fuse_uncertainty_device(wd["cond_images_ori"], gs_images, wd["soft_masks_reproj_ori"],
+                                                         h=Hd // 8, w=Wd // 8)
+        if _pixel_confidence(self):
+            self._pair_confidence_maps = O.confidence_maps_from_uncertainty(unc, self.gs_height, self.gs_width)
         masks = masks.cpu()
         cond_image = list(cond_dev.permute(0, 3, 1, 2))               # CHW in [0,1], as preprocess_images accepts
         lambda_ts = O.search_hypers_v2(masks, None, type="double_end", diffusion_steps=self.num_inference_steps)
@@ -247,14 +263,20 @@ class DiffusionGS:
         """diffusionGS.py:179-343.  View densification per input-view pair (HOT LOOP B), the key-frame / input-frame
         bookkeeping (:221-224,268-294) and, for `num_views_for_pcd_densification > 1`, the point-cloud densification:
         `densify_pcds` on the key frames, then the cloud filter (`syn3r_amd.pcd`: stride `n // 100000`, statistical outlier
-        removal k = 20 / 3 sigma on the device) and `dense_views/dense_views_cyc{c}.ply` (:302-336)."""
+        removal k = 20 / 3 sigma on the device) and `dense_views/dense_views_cyc{c}.ply` (:302-336).
+        With `args.pixel_confidence` (EXTENSION, off by default) `self.dense_confidence_maps` becomes a list parallel to the
+        returned `dense_views` - a [H,W] confidence map for a diffused inner frame, None for an input view - that follows the same
+        bookkeeping (`down_sample_rate` picks, `frames[:-1]`, the open chain's last view), and the pair's `.pt` cache gets a third
+        key `confidence_maps` (a cache without it loads as all None).  Without the flag nothing is kept and no key is added."""
         dense_views, dense_poses, key_frame_mask, input_flags = [], [], [], []
+        dense_maps = [] if _pixel_confidence(self) else None
         os.makedirs(os.path.join(self.save_dir, "dense_views"), exist_ok=True)
         for i in range(self.num_input_views):
             saving_path = os.path.join(self.save_dir, "dense_views" f"interpolated_dense_views_cyc{cycle_num}_view{i}.pt")
             if os.path.exists(saving_path):
                 data = torch.load(saving_path, weights_only=False)
                 frames, poses = data["views"], data["poses"]
+                cmaps = data.get("confidence_maps") or [None] * len(frames)
             else:
                 if densify_type == "interpolate_loop0_gs":
                     if i == self.num_input_views - 1:
@@ -265,12 +287,16 @@ class DiffusionGS:
                     frames, poses, _ = self._interpolate_between_gs_v3(i, (i + 1) % self.num_input_views, replace=True)
                 else:
                     raise NotImplementedError(f"{densify_type} not supported")
+                cmaps = getattr(self, "_pair_confidence_maps", None) or [None] * len(frames)
                 if down_sample_rate < 1:
                     idx = np.linspace(0, len(frames) - 1, int(len(frames) * down_sample_rate), dtype=int)
-                    frames, poses = [frames[k] for k in idx], [poses[k] for k in idx]
+                    frames, poses, cmaps = [frames[k] for k in idx], [poses[k] for k in idx], [cmaps[k] for k in idx]
             input_flags.extend([True] + [False] * (len(frames) - 2))           # a pair's first frame is an input view
             dense_views.extend(frames[:-1])
             dense_poses.extend(poses[:-1])
+            if dense_maps is not None:
+                assert len(cmaps) == len(frames)
+                dense_maps.extend(cmaps[:-1])
             key_frame_mask.extend(list(O.key_frame_template(poses, len(frames), num_views_for_pcd_densification,
                                                             bool(self.fps_keyframe_sampling))))
             if densify_type == "interpolate_loop0_gs" and i == self.num_input_views - 2:
@@ -278,8 +304,16 @@ class DiffusionGS:
                 dense_views.append(frames[-1])
                 dense_poses.append(poses[-1])
                 key_frame_mask.append(True)
+                if dense_maps is not None:
+                    dense_maps.append(cmaps[-1])
             assert len(dense_views) == len(dense_poses) == len(key_frame_mask) == len(input_flags)
-            torch.save({"views": frames, "poses": poses}, saving_path)
+            assert dense_maps is None or len(dense_maps) == len(dense_views)
+            if _pixel_confidence(self):
+                torch.save({"views": frames, "poses": poses,
+                            "confidence_maps": [None if m is None else m.detach().cpu() for m in cmaps]}, saving_path)
+            else:
+                torch.save({"views": frames, "poses": poses}, saving_path)
+        self.dense_confidence_maps = dense_maps
         dense_pcds = None
         if num_views_for_pcd_densification > 1:
             key = np.nonzero(key_frame_mask)[0]
@@ -337,9 +371,11 @@ class DiffusionGS:
         return trimesh_scene
 
     def refine_GS(self, dense_views, dense_poses, intrinsics, cam_confidence=0.01, gs_start_iter=0,
-                  disable_densification=False, load_iteration=None, pseudo_cam_sampling_rate=1, load_ckpt=True):
+                  disable_densification=False, load_iteration=None, pseudo_cam_sampling_rate=1, load_ckpt=True, confidence_maps=None):
         """diffusionGS.py:1608-1643: reload the latest refined (else the initial) checkpoint, append the dense views to
-        the training cameras, finetune, restore the original cameras."""
+        the training cameras, finetune, restore the original cameras.  `confidence_maps` (EXTENSION; `run` passes
+        `self.dense_confidence_maps` when `args.pixel_confidence` is set): per-pixel maps parallel to `dense_views`, handed to
+        `update_cameras`."""
         import glob
         tr = self.gsTrainer
         model_path = getattr(tr.scene, "model_path", None)
@@ -358,8 +394,12 @@ class DiffusionGS:
         # the reference deep-copies scene.train_cameras (:1627); the camera objects are not mutated by a finetune, so
         # copying the lists is enough to restore them (:1641)
         self.original_GS_train_cameras_bak = {k: list(v) for k, v in tr.scene.train_cameras.items()}
-        tr.update_cameras(dense_views, dense_poses, intrinsics, cam_confidences=cam_confidence, append=True,
-                          load_iteration=load_iteration)
+        if confidence_maps is not None:
+            tr.update_cameras(dense_views, dense_poses, intrinsics, cam_confidences=cam_confidence, append=True,
+                              load_iteration=load_iteration, confidence_maps=confidence_maps)
+        else:
+            tr.update_cameras(dense_views, dense_poses, intrinsics, cam_confidences=cam_confidence, append=True,
+                              load_iteration=load_iteration)
         tr.reset_optimizers()
         tr.reset_gs()
         tr.finetune(0, self.refine_epoch, disable_densification=disable_densification,
@@ -379,5 +419,6 @@ class DiffusionGS:
             self.gsTrainer.opt.use_lpips_loss = True                                  # :1690
             self.refine_GS(dense_views=dense_views, dense_poses=dense_poses, intrinsics=self.gs_intrinsics,
                            cam_confidence=self.cam_confidence, load_iteration=None,
-                           pseudo_cam_sampling_rate=self.pseudo_cam_sampling_rate, load_ckpt=(i > 0))
+                           pseudo_cam_sampling_rate=self.pseudo_cam_sampling_rate, load_ckpt=(i > 0),
+                           **({"confidence_maps": self.dense_confidence_maps} if _pixel_confidence(self) else {}))
             self.gsTrainer.opt.use_lpips_loss = False                                 # :1697

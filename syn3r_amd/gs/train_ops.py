@@ -10,71 +10,118 @@ import torch
 from .. import _lib as L
 
 
-def _l1_forward(image: torch.Tensor, target: torch.Tensor, weight: float):
+def _map_arg(who: str, weight_map: Optional[torch.Tensor], image: torch.Tensor) -> Optional[torch.Tensor]:
+    """The per-pixel weight map of the `*_map` entries as a contiguous fp32 [H,W] tensor (None stays None): [H,W] or [1,H,W] of
+    the image's H, W, float32, on the image's device, without a gradient - anything else is a ValueError."""
+    if weight_map is None:
+        return None
+    if not isinstance(weight_map, torch.Tensor):
+        raise ValueError(f"{who}: weight_map must be a tensor, got {type(weight_map).__name__}")
+    hw = tuple(image.shape[-2:]) if image.dim() >= 2 else None
+    m = weight_map[0] if weight_map.dim() == 3 and weight_map.shape[0] == 1 else weight_map
+    if hw is None or m.dim() != 2 or tuple(m.shape) != hw:
+        raise ValueError(f"{who}: weight_map must be [H,W] or [1,H,W] for the image's H, W = {hw}; got {tuple(weight_map.shape)}")
+    if m.dtype != torch.float32:
+        raise ValueError(f"{who}: weight_map must be float32, got {m.dtype}")
+    if m.device != image.device:
+        raise ValueError(f"{who}: weight_map is on {m.device}, the image on {image.device}")
+    if m.requires_grad:
+        raise ValueError(f"{who}: weight_map is data - a map that requires grad is not supported")
+    return m.contiguous()
+
+
+def _l1_forward(image: torch.Tensor, target: torch.Tensor, weight: float, weight_map: Optional[torch.Tensor] = None):
     L.require_gpu(image, target)
     if image.shape != target.shape or image.dtype != torch.float32 or target.dtype != torch.float32:
         raise ValueError("l1_loss: image and target must be float32 tensors of the same shape")
+    wm = _map_arg("l1_loss", weight_map, image)
     image, target = image.contiguous(), target.contiguous()
     lib = L.load()
     n = image.numel()
     loss = torch.empty((), dtype=torch.float32, device=image.device)
     ws = L.workspace(image.device, lib.syn3r_l1_loss_workspace_bytes(n), "l1")
-    L.check(lib.syn3r_l1_loss(L.ptr(image), L.ptr(target), n, float(weight), L.ptr(loss), L.ptr(ws), ws.numel(),
-                              L.stream_ptr(image.device)), "l1_loss")
-    return loss, image, target
+    if wm is None:
+        L.check(lib.syn3r_l1_loss(L.ptr(image), L.ptr(target), n, float(weight), L.ptr(loss), L.ptr(ws), ws.numel(),
+                                  L.stream_ptr(image.device)), "l1_loss")
+    else:
+        L.check(lib.syn3r_l1_loss_map(L.ptr(image), L.ptr(target), L.ptr(wm), n, wm.numel(), float(weight), L.ptr(loss), L.ptr(ws),
+                                      ws.numel(), L.stream_ptr(image.device)), "l1_loss_map")
+    return loss, image, target, wm
 
 
-def _l1_backward(image: torch.Tensor, target: torch.Tensor, weight: float, grad_loss):
+def _l1_backward(image: torch.Tensor, target: torch.Tensor, weight: float, grad_loss, wm: Optional[torch.Tensor] = None):
     go = grad_loss.to(torch.float32).contiguous() if grad_loss is not None else None      # device scalar; None = 1
     grad = torch.empty_like(image)
-    L.check(L.load().syn3r_l1_loss_backward(L.ptr(image), L.ptr(target), image.numel(), float(weight), L.ptr(go),
-                                            L.ptr(grad), L.stream_ptr(image.device)), "l1_loss_backward")
+    if wm is None:
+        L.check(L.load().syn3r_l1_loss_backward(L.ptr(image), L.ptr(target), image.numel(), float(weight), L.ptr(go),
+                                                L.ptr(grad), L.stream_ptr(image.device)), "l1_loss_backward")
+    else:
+        L.check(L.load().syn3r_l1_loss_map_backward(L.ptr(image), L.ptr(target), L.ptr(wm), image.numel(), wm.numel(), float(weight),
+                                                    L.ptr(go), L.ptr(grad), L.stream_ptr(image.device)), "l1_loss_map_backward")
     return grad
 
 
 class _L1Loss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, image: torch.Tensor, target: torch.Tensor, weight: float):
-        loss, image, target = _l1_forward(image, target, weight)
+    def forward(ctx, image: torch.Tensor, target: torch.Tensor, weight: float, weight_map: Optional[torch.Tensor] = None):
+        loss, image, target, wm = _l1_forward(image, target, weight, weight_map)
         ctx.save_for_backward(image, target)
         ctx.weight = float(weight)
+        ctx.wm = wm                                   # data without a gradient: kept beside the saved tensors
         return loss
 
     @staticmethod
     def backward(ctx, grad_loss: torch.Tensor):
         L.join_active_trace()
         image, target = ctx.saved_tensors
-        return _l1_backward(image, target, ctx.weight, grad_loss), None, None
+        return _l1_backward(image, target, ctx.weight, grad_loss, ctx.wm), None, None, None
 
 
-def l1_loss_step(image: torch.Tensor, target: torch.Tensor, weight: float = 1.0, grad_loss: torch.Tensor = None):
+def l1_loss_step(image: torch.Tensor, target: torch.Tensor, weight: float = 1.0, grad_loss: torch.Tensor = None,
+                 weight_map: Optional[torch.Tensor] = None):
     """Value and image gradient of `l1_loss` without autograd (the two launches `_L1Loss` makes): (loss, grad_image)."""
-    loss, image, target = _l1_forward(image.detach(), target.detach(), weight)
-    return loss, _l1_backward(image, target, weight, grad_loss)
+    loss, image, target, wm = _l1_forward(image.detach(), target.detach(), weight, weight_map)
+    return loss, _l1_backward(image, target, weight, grad_loss, wm)
 
 
-def l1_loss(image: torch.Tensor, target: torch.Tensor, weight: float = 1.0) -> torch.Tensor:
+def l1_loss(image: torch.Tensor, target: torch.Tensor, weight: float = 1.0, weight_map: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`weight * (image - target).abs().mean()` as one read of both images (forward) and one read + one write
-    (backward); the upstream gradient stays on the device."""
-    return _L1Loss.apply(image, target, weight)
+    (backward); the upstream gradient stays on the device.
+    `weight_map` (EXTENSION, not in the reference; default None = the loss above): a per-pixel weight m, [H,W] or [1,H,W] fp32 on
+    the image's device, shared by the channels of a [...,H,W] image: `weight * (m * (image - target).abs()).mean()` - the mean still
+    over all elements, so a constant map k is the weight k * weight.  The map is data: no gradient, `requires_grad` is a ValueError."""
+    return _L1Loss.apply(image, target, weight, weight_map)
+
+
+def _photo_args(who: str, image: torch.Tensor, target: torch.Tensor, weight_map: Optional[torch.Tensor]):
+    dev = L.require_gpu(image, target)
+    if image.shape != target.shape or image.dim() != 3 or image.dtype != torch.float32 or target.dtype != torch.float32:
+        raise ValueError(f"{who}: image and target must be float32 [C,H,W] tensors of the same shape")
+    return dev, _map_arg(who, weight_map, image)
 
 
 class _PhotoLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, image: torch.Tensor, target: torch.Tensor, lambda_dssim: float, weight: float):
-        L.require_gpu(image, target)
-        if image.shape != target.shape or image.dim() != 3 or image.dtype != torch.float32 or target.dtype != torch.float32:
-            raise ValueError("photometric_loss: image and target must be float32 [C,H,W] tensors of the same shape")
+    def forward(ctx, image: torch.Tensor, target: torch.Tensor, lambda_dssim: float, weight: float,
+                weight_map: Optional[torch.Tensor] = None):
+        _, wm = _photo_args("photometric_loss", image, target, weight_map)
         image, target = image.contiguous(), target.contiguous()
         lib = L.load()
         C_, H_, W_ = image.shape
         # own buffer, not the shared workspace cache: the derivative maps must survive until backward
-        ws = torch.empty(lib.syn3r_photo_loss_workspace_bytes(C_, H_, W_), dtype=torch.uint8, device=image.device)
-        out = torch.empty(3, dtype=torch.float32, device=image.device)
-        L.check(lib.syn3r_photo_loss(L.ptr(image), L.ptr(target), C_, H_, W_, float(lambda_dssim), float(weight),
-                                     L.ptr(out), L.ptr(ws), ws.numel(), L.stream_ptr(image.device)), "photo_loss")
+        if wm is None:
+            ws = torch.empty(lib.syn3r_photo_loss_workspace_bytes(C_, H_, W_), dtype=torch.uint8, device=image.device)
+            out = torch.empty(3, dtype=torch.float32, device=image.device)
+            L.check(lib.syn3r_photo_loss(L.ptr(image), L.ptr(target), C_, H_, W_, float(lambda_dssim), float(weight),
+                                         L.ptr(out), L.ptr(ws), ws.numel(), L.stream_ptr(image.device)), "photo_loss")
+        else:
+            ws = torch.empty(lib.syn3r_photo_loss_map_workspace_bytes(C_, H_, W_), dtype=torch.uint8, device=image.device)
+            out = torch.empty(4, dtype=torch.float32, device=image.device)
+            L.check(lib.syn3r_photo_loss_map(L.ptr(image), L.ptr(target), L.ptr(wm), C_, H_, W_, float(lambda_dssim), float(weight),
+                                             L.ptr(out), L.ptr(ws), ws.numel(), L.stream_ptr(image.device)), "photo_loss_map")
         ctx.save_for_backward(image, target, ws)
         ctx.args = (float(lambda_dssim), float(weight))
+        ctx.wm = wm                                   # data without a gradient: kept beside the saved tensors
         ctx.mark_non_differentiable(out)
         ctx.parts = out
         return out[0].clone(), out
@@ -87,39 +134,55 @@ class _PhotoLoss(torch.autograd.Function):
         C_, H_, W_ = image.shape
         go = grad_loss.to(torch.float32).contiguous()
         grad = torch.empty_like(image)
-        L.check(L.load().syn3r_photo_loss_backward(L.ptr(image), L.ptr(target), C_, H_, W_, lam, weight, L.ptr(go),
-                                                   L.ptr(ws), L.ptr(grad), L.stream_ptr(image.device)),
-                "photo_loss_backward")
-        return grad, None, None, None
+        if ctx.wm is None:
+            L.check(L.load().syn3r_photo_loss_backward(L.ptr(image), L.ptr(target), C_, H_, W_, lam, weight, L.ptr(go),
+                                                       L.ptr(ws), L.ptr(grad), L.stream_ptr(image.device)),
+                    "photo_loss_backward")
+        else:
+            L.check(L.load().syn3r_photo_loss_map_backward(L.ptr(image), L.ptr(target), L.ptr(ctx.wm), C_, H_, W_, lam, weight,
+                                                           L.ptr(go), L.ptr(ws), L.ptr(grad), L.stream_ptr(image.device)),
+                    "photo_loss_map_backward")
+        return grad, None, None, None, None
 
 
 def photometric_loss(image: torch.Tensor, target: torch.Tensor, lambda_dssim: float = 0.2, weight: float = 1.0,
-                     return_parts: bool = False):
+                     return_parts: bool = False, weight_map: Optional[torch.Tensor] = None):
     """The published 3DGS loss `weight * ((1 - lambda) * L1 + lambda * (1 - SSIM))` on [C,H,W] images, fused: one
     tile pass forward (also storing the SSIM derivative maps), one tile pass backward.  `return_parts`: also the
-    device tensor [loss, L1, SSIM]."""
-    loss, parts = _PhotoLoss.apply(image, target, lambda_dssim, weight)
+    device tensor [loss, L1, SSIM].
+    `weight_map` (EXTENSION, not in the reference, which weights a whole view by the scalar; default None = the loss above): a
+    per-pixel weight m, [H,W] or [1,H,W] fp32 on the image's device, one map for all channels, meant to lie in [0,1]:
+    `weight * ((1 - lambda) * mean(m |I - G|) + lambda * mean(m (1 - ssim)))` with the published SSIM map - m weights the map's
+    VALUE per pixel, it does not enter the window moments - and both means over all C*H*W elements (not divided by sum(m): a
+    constant map k is the weight k * weight, a map of ones is the loss without a map).  parts then has FOUR entries
+    [loss, mean(m |I - G|), mean(m ssim), mean(m)].  The map is data: no gradient, `requires_grad` is a ValueError."""
+    loss, parts = _PhotoLoss.apply(image, target, lambda_dssim, weight, weight_map)
     return (loss, parts) if return_parts else loss
 
 
 def photometric_loss_step(image: torch.Tensor, target: torch.Tensor, lambda_dssim: float = 0.2, weight: float = 1.0,
-                          grad_loss: torch.Tensor = None):
+                          grad_loss: torch.Tensor = None, weight_map: Optional[torch.Tensor] = None):
     """Value AND image gradient of `photometric_loss` without autograd (`syn3r_photo_loss_step`: the two tile passes, the
     scalar sums formed by the gradient pass' first block instead of a launch of their own).  Returns (loss - a view of
     parts[0] -, parts [loss, L1, SSIM], grad_image); `grad_loss`: device scalar, default 1.  Same bits as
-    `_PhotoLoss.forward` + `.backward`."""
-    dev = L.require_gpu(image, target)
-    if image.shape != target.shape or image.dim() != 3 or image.dtype != torch.float32 or target.dtype != torch.float32:
-        raise ValueError("photometric_loss_step: image and target must be float32 [C,H,W] tensors of the same shape")
+    `_PhotoLoss.forward` + `.backward`.  `weight_map`: as `photometric_loss` (`syn3r_photo_loss_map_step`; parts has 4 entries)."""
+    dev, wm = _photo_args("photometric_loss_step", image, target, weight_map)
     image, target = image.detach().contiguous(), target.detach().contiguous()
     lib = L.load()
     C_, H_, W_ = image.shape
-    ws = L.workspace(dev, lib.syn3r_photo_loss_workspace_bytes(C_, H_, W_), "photo_step")     # the maps die with the call
-    parts = torch.empty(3, dtype=torch.float32, device=dev)
     grad = torch.empty_like(image)
     go = grad_loss.to(torch.float32).contiguous() if grad_loss is not None else None
-    L.check(lib.syn3r_photo_loss_step(L.ptr(image), L.ptr(target), C_, H_, W_, float(lambda_dssim), float(weight), L.ptr(go),
-                                      L.ptr(parts), L.ptr(grad), L.ptr(ws), ws.numel(), L.stream_ptr(dev)), "photo_loss_step")
+    if wm is None:
+        ws = L.workspace(dev, lib.syn3r_photo_loss_workspace_bytes(C_, H_, W_), "photo_step")     # the maps die with the call
+        parts = torch.empty(3, dtype=torch.float32, device=dev)
+        L.check(lib.syn3r_photo_loss_step(L.ptr(image), L.ptr(target), C_, H_, W_, float(lambda_dssim), float(weight), L.ptr(go),
+                                          L.ptr(parts), L.ptr(grad), L.ptr(ws), ws.numel(), L.stream_ptr(dev)), "photo_loss_step")
+    else:
+        ws = L.workspace(dev, lib.syn3r_photo_loss_map_workspace_bytes(C_, H_, W_), "photo_step")
+        parts = torch.empty(4, dtype=torch.float32, device=dev)
+        L.check(lib.syn3r_photo_loss_map_step(L.ptr(image), L.ptr(target), L.ptr(wm), C_, H_, W_, float(lambda_dssim), float(weight),
+                                              L.ptr(go), L.ptr(parts), L.ptr(grad), L.ptr(ws), ws.numel(), L.stream_ptr(dev)),
+                "photo_loss_map_step")
     return parts[0], parts, grad
 
 
@@ -212,7 +275,7 @@ def image_metrics(image: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     ws = L.workspace(image.device, lib.syn3r_l1_loss_workspace_bytes(n), "l1")
     L.check(lib.syn3r_image_mse(L.ptr(image), L.ptr(target), n, L.ptr(mse), L.ptr(ws), ws.numel(),
                                 L.stream_ptr(image.device)), "image_mse")
-    _, parts = _PhotoLoss.apply(image, target, 1.0, 1.0)
+    _, parts = _PhotoLoss.apply(image, target, 1.0, 1.0, None)
     psnr = -10.0 * torch.log10(mse.clamp_min(1e-12))
     return torch.stack([psnr, parts[2]])
 

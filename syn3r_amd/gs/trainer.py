@@ -51,10 +51,15 @@ class Camera:
     data_device, cam_confidence)` as constructed at diffusionGS.py:161-163.  R is camera-to-world rotation and T the
     world-to-camera translation (COLMAP/3DGS convention).  `depth_image`: the monocular depth prior [H,W] (or [1,H,W]) of the
     view, named as in FSGS' camera; the trainer's depth-correlation term reads it (None: `GSTrainer.depth_net` fills it in, or
-    the view has no prior)."""
+    the view has no prior).
+    `confidence_map` (EXTENSION, not in the reference's camera; default None): a per-pixel weight [H,W] (or [1,H,W]) in [0,1] for
+    the photometric loss of this view (`train_ops.photometric_loss(weight_map=)`), on top of the scalar `cam_confidence`; stored as
+    fp32 [H,W] on `data_device`, its shape checked against the image's.  Also settable as an attribute.  `gt_alpha_mask` stays
+    ignored: in published 3DGS it multiplies the image, which is a different thing."""
 
     def __init__(self, colmap_id, R, T, FoVx, FoVy, image, gt_alpha_mask=None, image_name="", uid=0,
-                 trans=np.array([0.0, 0.0, 0.0]), scale=1.0, data_device="cuda", cam_confidence: float = 1.0, depth_image=None):
+                 trans=np.array([0.0, 0.0, 0.0]), scale=1.0, data_device="cuda", cam_confidence: float = 1.0, depth_image=None,
+                 confidence_map=None):
         self.uid, self.colmap_id, self.image_name = uid, colmap_id, image_name
         self.R, self.T, self.FoVx, self.FoVy = np.asarray(R, np.float32), np.asarray(T, np.float32), FoVx, FoVy
         self.cam_confidence = float(cam_confidence)
@@ -74,15 +79,38 @@ class Camera:
         if depth_image is not None:
             d = torch.as_tensor(depth_image, dtype=torch.float32).to(self.data_device)
             self.depth_image = (d[0] if d.dim() == 3 and d.shape[0] == 1 else d).contiguous()
+        self._confidence_map = None
+        self.confidence_map = confidence_map
+
+    @property
+    def confidence_map(self) -> Optional[torch.Tensor]:
+        return self._confidence_map
+
+    @confidence_map.setter
+    def confidence_map(self, m):
+        if m is None:
+            self._confidence_map = None
+            return
+        m = torch.as_tensor(m).detach().to(dtype=torch.float32, device=self.data_device)
+        m = m[0] if m.dim() == 3 and m.shape[0] == 1 else m
+        hw = (getattr(self, "image_height", None), getattr(self, "image_width", None))
+        if hw[0] is None:
+            raise ValueError("Camera: a confidence_map needs a camera with an image size")
+        if m.dim() != 2 or tuple(m.shape) != (int(hw[0]), int(hw[1])):
+            raise ValueError(f"Camera: confidence_map must be [H,W] or [1,H,W] for the image's H, W = ({int(hw[0])}, {int(hw[1])}); "
+                             f"got {tuple(m.shape)}")
+        self._confidence_map = m.contiguous()
 
     @classmethod
     def from_w2c(cls, w2c: np.ndarray, K: np.ndarray, H: int, W: int, image=None, **kw):
         """Build from a 4x4 world-to-camera matrix and intrinsics (the orchestrator's pose format)."""
         fovx = 2 * math.atan(W / (2 * K[0, 0]))
         fovy = 2 * math.atan(H / (2 * K[1, 1]))
+        cmap = kw.pop("confidence_map", None)
         cam = cls(0, np.asarray(w2c[:3, :3]).T, np.asarray(w2c[:3, 3]), fovx, fovy, image, **kw)
         if image is None:
             cam.image_height, cam.image_width = H, W
+        cam.confidence_map = cmap                      # (after the size is known)
         return cam
 
     def get_image(self):
@@ -369,13 +397,20 @@ class GSTrainer:
     def pseudo_cameras(self) -> List[Camera]:
         return self.scene.getPseudoCameras()
 
-    def update_cameras(self, views, poses, K, cam_confidences, append: bool = True, load_iteration=None):
+    def update_cameras(self, views, poses, K, cam_confidences, append: bool = True, load_iteration=None, confidence_maps=None):
         """diffusionGS.py:1631 — register SVD pseudo-views ([3,H,W] tensors + w2c poses) with their confidence in
-        `scene.train_cameras` (appended, as the reference; the orchestrator restores the list after the finetune)."""
+        `scene.train_cameras` (appended, as the reference; the orchestrator restores the list after the finetune).
+        `confidence_maps` (EXTENSION; default None): one per-pixel map ([H,W], see `Camera.confidence_map`) or None per view, a
+        list of the length of `views`."""
         if np.isscalar(cam_confidences):
             cam_confidences = [float(cam_confidences)] * len(views)
-        cams = [Camera.from_w2c(np.asarray(p), np.asarray(K), v.shape[1], v.shape[2], image=v, cam_confidence=c,
-                                data_device=self.gaussians._xyz.device) for v, p, c in zip(views, poses, cam_confidences)]
+        if confidence_maps is None:
+            confidence_maps = [None] * len(views)
+        elif len(confidence_maps) != len(views):
+            raise ValueError(f"update_cameras: {len(confidence_maps)} confidence_maps for {len(views)} views")
+        cams = [Camera.from_w2c(np.asarray(p), np.asarray(K), v.shape[1], v.shape[2], image=v, cam_confidence=c, confidence_map=m,
+                                data_device=self.gaussians._xyz.device)
+                for v, p, c, m in zip(views, poses, cam_confidences, confidence_maps)]
         for c in cams:
             c.is_pseudo = True
         for scale, lst in self.scene.train_cameras.items():
@@ -693,11 +728,11 @@ class GSTrainer:
             # log-scales / raw quaternions / logits in, THEIR gradients out (syn3r_raster_*_raw)
             color, radii, depth, alpha, rstate = rasterize_forward(g._xyz, g._features, g._opacity, g._scaling, g._rotation,
                                                                    g.confidence, st, raw_params=True)
-            w = float(cam.cam_confidence)
+            w, wmap = float(cam.cam_confidence), getattr(cam, "confidence_map", None)
             if self.opt.lambda_dssim > 0.0:
-                loss, _, d_color = photometric_loss_step(color, cam.original_image, self.opt.lambda_dssim, w)
+                loss, _, d_color = photometric_loss_step(color, cam.original_image, self.opt.lambda_dssim, w, weight_map=wmap)
             else:
-                loss, d_color = l1_loss_step(color, cam.original_image, w)
+                loss, d_color = l1_loss_step(color, cam.original_image, w, weight_map=wmap)
             d_depth = None
             if prior is not None:
                 d_loss, d_depth = depth_correlation_loss_step(depth, prior, self.opt.depth_weight, self.opt.depth_offset)
@@ -724,6 +759,9 @@ class GSTrainer:
         its two prior transforms, `train_ops.depth_correlation_loss`) for a camera with a prior (`depth_prior`: `cam.depth_image` or
         the injected `depth_net`); a camera without one skips it.  As FSGS' `loss += depth_weight * depth_loss` the term is weighted
         by `depth_weight` alone, not by the camera confidence - UNPINNED for SYN3R's FSGS fork (not vendored).
+        `cam.confidence_map` (EXTENSION, default None: the scalar-only, reference-shaped loss): a per-pixel weight on the photometric
+        term (L1 and D-SSIM, `train_ops.photometric_loss(weight_map=)`) on top of the scalar `cam.cam_confidence`, on both the
+        explicit and the autograd path.  The depth-correlation and LPIPS terms are NOT touched by the map.
         `explicit` (default: whenever the LPIPS term is off): the step without autograd (`_explicit_step`).
         The published schedule, when switched on (`OptimizationParams`): `update_learning_rate(iteration + 1)` before the optimiser
         step, `oneupSHdegree()` after every `sh_degree_interval`-th step (the published loop raises it at the top of the next
@@ -738,10 +776,12 @@ class GSTrainer:
             loss, out = self._explicit_step(cam)
         else:
             out = self.render_view(cam)
+            wmap = getattr(cam, "confidence_map", None)
             if self.opt.lambda_dssim > 0.0:
-                loss = photometric_loss(out["render"], cam.original_image, self.opt.lambda_dssim, float(cam.cam_confidence))
+                loss = photometric_loss(out["render"], cam.original_image, self.opt.lambda_dssim, float(cam.cam_confidence),
+                                        weight_map=wmap)
             else:
-                loss = l1_loss(out["render"], cam.original_image, weight=float(cam.cam_confidence))
+                loss = l1_loss(out["render"], cam.original_image, weight=float(cam.cam_confidence), weight_map=wmap)
             if lpips_on:
                 # the perceptual term of the refine stage (diffusionGS.py:1690,1697; `--lpips_weight`): published LPIPS-VGG on the
                 # whole render, weighted like the photometric term by the camera confidence.  How FSGS applies it is not visible

@@ -92,6 +92,10 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--depth_weight", type=float, default=0.0,
                     help="weight of FSGS' depth-correlation term, 1 - Pearson(rendered depth, monocular prior), on every training step "
                          "(0 = off); views need a prior (Camera.depth_image or an injected GSTrainer.depth_net)")
+    ap.add_argument("--pixel_confidence", type=int, default=0, choices=(0, 1),
+                    help="1: EXTENSION (not in the reference) - every diffusion pseudo-view is weighted per pixel in the photometric loss by "
+                         "1 - the fused uncertainty of its interpolation (backward_warp only), on top of --cam_confidence; the pairs' .pt "
+                         "caches gain a `confidence_maps` key.  0 (default): the reference's scalar weight alone")
     ap.add_argument("--use_proximity_densify", type=int, default=0,
                     help="1: FSGS' proximity-guided Gaussian unpooling inside the density control (bash_scripts/batch_llff_train.sh:37 and "
                          "batch_dl3dv_train.sh:85 pass 0); thresholds: OptimizationParams.proximity_*")
@@ -114,7 +118,7 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     args, rest = ap.parse_known_args(given)
     # argparse takes `--percent_dens` for an abbreviation of `--percent_dense`: while that flag sat in FSGS_FLAGS the token was an
     # unknown argument, and a misspelling stays one
-    declared = ["--" + f for f, _ in TRAINER_FLAGS] + ["--gs_schedule"]
+    declared = ["--" + f for f, _ in TRAINER_FLAGS] + ["--gs_schedule", "--pixel_confidence"]
     cut = [t for t in given if t.startswith("--") and any(d != t.split("=")[0] and d.startswith(t.split("=")[0]) for d in declared)]
     if cut:
         ap.error(f"unknown argument(s): {' '.join(cut)} (the trainer's flags are not abbreviated)")

@@ -219,6 +219,26 @@ def fuse_uncertainty_device(cond_images_ori: torch.Tensor, gs_images, soft_masks
     return masks, cond, unc
 
 
+def confidence_maps_from_uncertainty(unc: torch.Tensor, gs_height: int, gs_width: int) -> list:
+    """EXTENSION (not in the reference, which weights a whole pseudo-view by one scalar, model/diffusionGS.py:1631): the per-pixel
+    confidence maps of one interpolated view pair from the fused uncertainty `unc` [n,H,W] of its n INNER frames
+    (`fuse_uncertainty_device`'s third result, at the diffusion resolution): `[None] + [clamp(1 - bilinear(unc_k), 0, 1)] * n +
+    [None]`, one entry per frame of the pair.  The resize to the GS resolution is pixel-centre-aligned bilinear without
+    antialiasing (`diffusionGS._resize_linear_t`'s rule); the two end frames are real input views and get None (the scalar
+    weight alone).  The fused uncertainty is NaN where the warp has no defined reprojection confidence (no rendered depth under
+    the pixel); a map pixel whose resize touches such a value gets confidence 0 - an unknown uncertainty is no reason to trust the
+    diffused pixel, and a NaN weight would make the whole loss NaN.  Pure torch on the tensor's own device, CPU tensors included.
+    That confidence = 1 - uncertainty (and 0 for an undefined one) is this project's choice: UNPINNED."""
+    if unc.dim() != 3:
+        raise ValueError(f"confidence_maps_from_uncertainty: unc must be [n,H,W], got {tuple(unc.shape)}")
+    if unc.shape[0] == 0:
+        return [None, None]
+    small = torch.nn.functional.interpolate(unc.detach().float()[None], size=(int(gs_height), int(gs_width)), mode="bilinear",
+                                            align_corners=False)[0]
+    conf = torch.nan_to_num((1.0 - small).clamp_(0.0, 1.0), nan=0.0)
+    return [None] + [conf[k].contiguous() for k in range(conf.shape[0])] + [None]
+
+
 # ---------------------------------------------------------------------------------------------- O2
 def _perturb_interp_pose_candidates(anchor_poses, perturb_num: int = 5, rng=None):
     """diffusionGS.py:653-714 — per anchor: the pose itself + `perturb_num` copies jittered by
