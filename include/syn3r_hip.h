@@ -296,6 +296,58 @@ int syn3r_raster_backward_raw(int N, int sh_degree, int sh_coeffs, long long P, 
                               float* dL_dconfidence, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Rendering modes of the projection stage: syn3r_raster_preprocess_ex / syn3r_raster_backward_ex carry them in `flags`.
+ * Any other bit is rejected (SYN3R_E_INVALID, message in syn3r_last_error(), nothing launched).
+ *
+ * SYN3R_RASTER_ANTIALIAS - anti-aliased splatting.  With (a, b; b, c) the projected 2D covariance of a Gaussian before the
+ * 0.3 px^2 dilation, h = 0.3, A = a + h, C = c + h, d0 = a c - b^2, d1 = A C - b^2, r = d0 / d1 and
+ *     rho = sqrt(max(r, 0.000025)),
+ * the opacity the blend multiplies is opacity * rho * confidence instead of opacity * confidence: the dilation no longer adds
+ * energy, a splat deposits (up to the floor) the alpha of its undilated footprint whatever its size on screen.  Conic, radius,
+ * tile rectangle, depth key and colour are untouched, so radii and the tile lists are those of a render without the flag.
+ * Backward, G = dL/d(blend opacity): dL/dopacity = G confidence rho (then the sigmoid's chain rule on the raw route),
+ * dL/dconfidence = G opacity rho, dL/drho = G opacity confidence, dL/dr = dL/drho / (2 rho) if r > 0.000025 else 0, and
+ *     dr/da = (c d1 - C d0) / d1^2,  dr/dc = (a d1 - A d0) / d1^2,  dr/db = -2 b (d1 - d0) / d1^2
+ * are added to the covariance gradients before they go on into the 3D covariance, the Jacobian, the mean, scales and rotations.
+ * In fp32 d0 can cancel to zero or below for needle-shaped Gaussians: those sit on the floor (rho = 0.005, no gradient through
+ * rho); nothing becomes NaN.  The geometry buffer holds the opacity WITHOUT rho; the backward forms rho again.
+ * Provenance: the `antialiasing` switch of the published 3DGS rasteriser (GaussianRasterizationSettings.antialiasing), which is
+ * the 2D Mip filter of Mip-Splatting (Yu et al., CVPR 2024).  The constants 0.3 and 0.000025 are RECALLED from the published
+ * code, which is not available to check against: UNPINNED.  FSGS' confidence fork (the rasteriser the reference calls, not
+ * vendored) is not known to have the filter: the flag is an option, and with flags = 0 every bit is what the four entries above
+ * compute.
+ */
+#define SYN3R_RASTER_ANTIALIAS 1
+/*
+ * syn3r_raster_preprocess / syn3r_raster_preprocess_raw with rendering modes: `raw` = 0 takes the activated tensors (scales,
+ * rotations, opacities), `raw` = 1 the trainer's parameters (log-scales, raw quaternions, logits) in the same three arguments;
+ * `flags` = 0 or SYN3R_RASTER_ANTIALIAS (formula and provenance above).  The two old entries are this one with flags = 0.
+ * The backward of the render MUST be syn3r_raster_backward_ex with the SAME `raw` and `flags`.
+ */
+int syn3r_raster_preprocess_ex(int N, int sh_degree, int sh_coeffs, const float* means3D, const float* scales,
+                               const float* rotations, const float* opacities, const float* shs,
+                               const float* confidence, float scale_modifier, const float* viewmatrix,
+                               const float* projmatrix, const float* campos, float tanfovx, float tanfovy, int H,
+                               int W, int* radii, void* geom, size_t geom_bytes, long long* num_rendered_host,
+                               int raw, int flags, void* stream);
+/*
+ * syn3r_raster_backward / syn3r_raster_backward_raw with rendering modes; arguments as theirs, then `raw` and `flags` as
+ * syn3r_raster_preprocess_ex.  `raw` and `flags` MUST be the ones the forward of this render was given: with
+ * SYN3R_RASTER_ANTIALIAS the gradients of opacity, confidence, means, scales and rotations carry the rho terms above, and the
+ * state buffers do not record which mode wrote them.  The two old entries are this one with flags = 0.
+ */
+int syn3r_raster_backward_ex(int N, int sh_degree, int sh_coeffs, long long P, const float* means3D,
+                             const float* scales, const float* rotations, const float* opacities, const float* shs,
+                             const float* confidence, float scale_modifier, const float* viewmatrix,
+                             const float* projmatrix, const float* campos, float tanfovx, float tanfovy, int H, int W,
+                             const float* bg, const int* radii, void* geom, size_t geom_bytes,
+                             const unsigned* point_list, void* image, size_t image_bytes, const float* dL_dcolor,
+                             const float* dL_ddepth, const float* dL_dalpha, float* dL_dmeans3D, float* dL_dscales,
+                             float* dL_drotations, float* dL_dopacities, float* dL_dshs, float* dL_dmeans2D,
+                             float* dL_dconfidence, void* workspace, size_t workspace_bytes, int raw, int flags,
+                             void* stream);
+
+/*
  * Stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits) — the
  * tile/depth sort of the rasteriser (cub::DeviceRadixSort::SortPairs in the
  * published implementation).  Ping-pongs between the two buffer pairs;

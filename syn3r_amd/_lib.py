@@ -21,6 +21,7 @@ c_ll = C.c_longlong
 c_d = C.c_double
 
 F32, F16 = 0, 1
+RASTER_ANTIALIAS = 1          # SYN3R_RASTER_ANTIALIAS: bit 0 of the `flags` of syn3r_raster_preprocess_ex / syn3r_raster_backward_ex
 
 # name -> (restype, argtypes); mirrors include/syn3r_hip.h declaration by declaration
 SIGNATURES = {
@@ -52,6 +53,8 @@ SIGNATURES = {
                                       c_i, c_i, c_p, c_p, c_sz, C.POINTER(c_ll), c_p]),
     "syn3r_raster_preprocess_raw": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_f, c_f,
                                           c_i, c_i, c_p, c_p, c_sz, C.POINTER(c_ll), c_p]),
+    "syn3r_raster_preprocess_ex": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_f, c_f,
+                                         c_i, c_i, c_p, c_p, c_sz, C.POINTER(c_ll), c_i, c_i, c_p]),
     "syn3r_raster_render": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_sz, c_p, c_sz, c_p, c_sz, c_ll, c_p, c_p, c_p,
                                   C.POINTER(c_p), c_p]),
     "syn3r_raster_backward_workspace_bytes": (c_sz, [c_i]),
@@ -61,6 +64,9 @@ SIGNATURES = {
     "syn3r_raster_backward_raw": (c_i, [c_i, c_i, c_i, c_ll, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_f, c_f,
                                         c_i, c_i, c_p, c_p, c_p, c_sz, c_p, c_p, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                         c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "syn3r_raster_backward_ex": (c_i, [c_i, c_i, c_i, c_ll, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_f, c_f,
+                                       c_i, c_i, c_p, c_p, c_p, c_sz, c_p, c_p, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                       c_p, c_p, c_p, c_p, c_sz, c_i, c_i, c_p]),
     "syn3r_sort_pairs_workspace_bytes": (c_sz, [c_ll]),
     "syn3r_sort_pairs": (c_i, [c_p, c_p, c_p, c_p, c_ll, c_i, c_p, c_sz, C.POINTER(c_i), c_p]),
     "syn3r_gaussian_activate": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),

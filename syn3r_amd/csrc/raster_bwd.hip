@@ -354,8 +354,16 @@ __device__ __forceinline__ F3 sh_backward(int D, int M, F3 pos, const float* cam
 // STAGED (sh_coeffs == 16, 16-byte aligned tensors): a block's spherical-harmonics rows (256 x 192 B, contiguous in memory) come in
 // and its gradient rows go out through LDS with coalesced 16-byte accesses; a thread reading and writing its own 192-byte row in
 // global memory touches 64 different cache lines per wave instruction (32 of the kernel's 42 us at 200 000 Gaussians).
+// AA (SYN3R_RASTER_ANTIALIAS; k_preprocess<true> made the forward): the blend multiplied op * rho * confidence, rho = mip_rho(r),
+// r = d0 / d1 with d0 = a c - b^2 the determinant before the dilation and d1 = A C - b^2 (= `den`) after it (A = a + h, C = c + h,
+// h = kLowPass).  G = gr[G_OP] is dL/d(that product), so dL/dop = G cf rho, dL/dcf = G op rho, dL/drho = G op cf, and above the
+// floor dL/dr = dL/drho / (2 rho) (on the floor rho is a constant) enters the covariance gradients through
+//     dr/da = (c d1 - C d0) / d1^2 = h (c C + b^2) / d1^2      dr/dc = (a d1 - A d0) / d1^2 = h (a A + b^2) / d1^2
+//     dr/db = -2 b (d1 - d0) / d1^2 = -2 b h (a + C) / d1^2
+// (the right-hand forms are the same polynomials with A - a = C - c = h taken out: no difference of two large products in fp32).
+// rho is formed again here, by the function k_preprocess<true> called (mip_ratio); GeomState::conic_opacity[3] holds op without it.
 constexpr int kShLd = 49;      // LDS row stride (floats): odd, so the 64 rows of a wavefront fall into 64 banks
-template <bool STAGED>
+template <bool STAGED, bool AA>
 __global__ void __launch_bounds__(256) k_preprocess_bwd(
     int N, int D, int M, const float* __restrict__ means3D, const float* __restrict__ scales,
     const float* __restrict__ rots, const float* __restrict__ opacities, const float* __restrict__ shs,
@@ -421,9 +429,10 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(
     float W00 = v[0], W01 = v[4], W02 = v[8], W10 = v[1], W11 = v[5], W12 = v[9], W20 = v[2], W21 = v[6], W22 = v[10];
     float a0 = c0 * T00 + c1 * T01 + c2 * T02, a1 = c1 * T00 + c3 * T01 + c4 * T02, a2 = c2 * T00 + c4 * T01 + c5 * T02;
     float b0 = c0 * T10 + c1 * T11 + c2 * T12, b1 = c1 * T10 + c3 * T11 + c4 * T12, b2 = c2 * T10 + c4 * T11 + c5 * T12;
-    float A = T00 * a0 + T01 * a1 + T02 * a2 + kLowPass;
+    const float pA = T00 * a0 + T01 * a1 + T02 * a2, pC = T10 * b0 + T11 * b1 + T12 * b2;   // before the dilation
+    float A = pA + kLowPass;
     float B = T00 * b0 + T01 * b1 + T02 * b2;
-    float C = T10 * b0 + T11 * b1 + T12 * b2 + kLowPass;
+    float C = pC + kLowPass;
     float den = A * C - B * B;
     float den2inv = 1.0f / (den * den + 0.0000001f);
     // the blend summed raw moments (k_render_bwd); the factors are the float values IT multiplied: the splat record's conic and its
@@ -436,6 +445,22 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(
         dL_dA = den2inv * (-C * C * gxx + B * C * gxy + (den - A * C) * gyy);
         dL_dC = den2inv * ((den - A * C) * gxx + A * B * gxy - A * A * gyy);
         dL_dB = den2inv * (2.f * B * C * gxx - (den + 2.f * B * B) * gxy + 2.f * A * B * gyy);
+    }
+    // raw (syn3r_raster_backward_raw): `scales` / `rots` / `opacities` are the trainer's PARAMETERS; the activations are formed
+    // again (k_activate's arithmetic, common.h) and the gradients leave through their chain rule (k_activate_bwd's): the same bits
+    // as the two-launch route
+    const float cf = conf ? conf[i] : 1.0f;
+    const float op_a = raw ? act_sigmoid(opacities[i]) : opacities[i];
+    float rho = 1.0f;
+    if constexpr (AA) {
+        const float r = mip_ratio(pA, B, pC), den_inv = 1.0f / den;     // r: the forward's bits (one function, explicit roundings)
+        rho = mip_rho(r);
+        if (r > kMipFloor) {
+            const float k = gr[G_OP] * op_a * cf / (2.0f * rho) * kLowPass * den_inv * den_inv;   // dL/dr h / d1^2
+            dL_dA += k * (pC * C + B * B);
+            dL_dC += k * (pA * A + B * B);
+            dL_dB -= k * 2.0f * B * (pA + C);
+        }
     }
     // dL/dSigma (stored upper triangle; off-diagonals count both symmetric entries)
     float dS0 = T00 * T00 * dL_dA + T00 * T10 * dL_dB + T10 * T10 * dL_dC;
@@ -480,14 +505,10 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(
     dmean = dmean + dm_sh;
     dL_dmeans3D[3 * i] = dmean.x; dL_dmeans3D[3 * i + 1] = dmean.y; dL_dmeans3D[3 * i + 2] = dmean.z;
 
-    // ---- opacity / confidence (blend used opacity * confidence)
-    // raw (syn3r_raster_backward_raw): `scales` / `rots` / `opacities` are the trainer's PARAMETERS; the activations are formed
-    // again (k_activate's arithmetic, common.h) and the gradients leave through their chain rule (k_activate_bwd's): the same bits
-    // as the two-launch route
-    float cf = conf ? conf[i] : 1.0f;
-    const float op_a = raw ? act_sigmoid(opacities[i]) : opacities[i];
-    dL_dopacity[i] = raw ? act_sigmoid_bwd(op_a, gr[G_OP] * cf) : gr[G_OP] * cf;
-    if (dL_dconf) dL_dconf[i] = gr[G_OP] * op_a;
+    // ---- opacity / confidence (blend used opacity * confidence; cf and op_a: above the AA block)
+    const float g_op = AA ? gr[G_OP] * rho : gr[G_OP];      // dL/d(op x cf)
+    dL_dopacity[i] = raw ? act_sigmoid_bwd(op_a, g_op * cf) : g_op * cf;
+    if (dL_dconf) dL_dconf[i] = g_op * op_a;
 
     // ---- Sigma = M M^T, M = R S  -> scale, rotation
     float s0 = scales[3 * i], s1 = scales[3 * i + 1], s2 = scales[3 * i + 2];
@@ -552,7 +573,7 @@ extern "C" size_t syn3r_raster_backward_workspace_bytes(int N) {
     return N > 0 ? align256((size_t)N * kGradSlots * sizeof(float)) : 0;
 }
 
-static int raster_backward(int raw, int N, int sh_degree, int sh_coeffs, long long P, const float* means3D,
+static int raster_backward(int raw, int flags, int N, int sh_degree, int sh_coeffs, long long P, const float* means3D,
                                      const float* scales, const float* rotations, const float* opacities,
                                      const float* shs, const float* confidence, float scale_modifier,
                                      const float* viewmatrix, const float* projmatrix, const float* campos,
@@ -562,6 +583,7 @@ static int raster_backward(int raw, int N, int sh_degree, int sh_coeffs, long lo
                                      const float* dL_dalpha, float* dL_dmeans3D, float* dL_dscales,
                                      float* dL_drotations, float* dL_dopacities, float* dL_dshs, float* dL_dmeans2D,
                                      float* dL_dconfidence, void* workspace, size_t workspace_bytes, void* stream_) {
+    SYN3R_REQUIRE((flags & ~SYN3R_RASTER_ANTIALIAS) == 0, "raster_backward: unknown flag bits 0x%x", (unsigned)flags & ~(unsigned)SYN3R_RASTER_ANTIALIAS);
     SYN3R_REQUIRE(N > 0 && H > 0 && W > 0 && P >= 0, "raster_backward: bad sizes N=%d H=%d W=%d P=%lld", N, H, W, P);
     SYN3R_REQUIRE(sh_degree >= 0 && sh_degree <= 3 && sh_coeffs >= (sh_degree + 1) * (sh_degree + 1),
                   "raster_backward: bad SH configuration");
@@ -596,14 +618,18 @@ static int raster_backward(int raw, int N, int sh_degree, int sh_coeffs, long lo
                            point_list, g.splats, bg[0], bg[1], bg[2], im.n_contrib, im.final_T, dL_dcolor, dL_ddepth,
                            dL_dalpha, grad_rec, tile_order);
     const bool staged = sh_coeffs == 16 && ((((uintptr_t)shs) | ((uintptr_t)dL_dshs)) & 15) == 0;
-    if (staged)
-        SYN3R_LAUNCH(k_preprocess_bwd<true>, dim3(ceil_div(N, 256)), dim3(256), 0, stream, N, sh_degree, sh_coeffs, means3D,
-                       scales, rotations, opacities, shs, confidence, scale_modifier, cam, radii, g, grad_rec,
-                       dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacities, dL_dshs, dL_dmeans2D, dL_dconfidence, raw);
-    else
-        SYN3R_LAUNCH(k_preprocess_bwd<false>, dim3(ceil_div(N, 256)), dim3(256), 0, stream, N, sh_degree, sh_coeffs, means3D,
-                       scales, rotations, opacities, shs, confidence, scale_modifier, cam, radii, g, grad_rec,
-                       dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacities, dL_dshs, dL_dmeans2D, dL_dconfidence, raw);
+    // the anti-aliased instances keep the trace names of the plain ones (the benchmark's per-kernel tables are keyed by them)
+#define PREPROCESS_BWD(name, ...)                                                                                            \
+    SYN3R_LAUNCH_NAMED(name, (k_preprocess_bwd<__VA_ARGS__>), dim3(ceil_div(N, 256)), dim3(256), 0, stream, N, sh_degree,     \
+                       sh_coeffs, means3D, scales, rotations, opacities, shs, confidence, scale_modifier, cam, radii, g,    \
+                       grad_rec, dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacities, dL_dshs, dL_dmeans2D,               \
+                       dL_dconfidence, raw)
+    const bool aa = (flags & SYN3R_RASTER_ANTIALIAS) != 0;
+    if (staged && aa) PREPROCESS_BWD("k_preprocess_bwd<true>", true, true);
+    else if (staged) PREPROCESS_BWD("k_preprocess_bwd<true>", true, false);
+    else if (aa) PREPROCESS_BWD("k_preprocess_bwd<false>", false, true);
+    else PREPROCESS_BWD("k_preprocess_bwd<false>", false, false);
+#undef PREPROCESS_BWD
     SYN3R_LAUNCH_CHECK("raster_backward launch");
     return SYN3R_OK;
 }
@@ -618,7 +644,7 @@ extern "C" int syn3r_raster_backward(int N, int sh_degree, int sh_coeffs, long l
                                      const float* dL_dalpha, float* dL_dmeans3D, float* dL_dscales,
                                      float* dL_drotations, float* dL_dopacities, float* dL_dshs, float* dL_dmeans2D,
                                      float* dL_dconfidence, void* workspace, size_t workspace_bytes, void* stream_) {
-    return raster_backward(0, N, sh_degree, sh_coeffs, P, means3D, scales, rotations, opacities, shs, confidence, scale_modifier,
+    return raster_backward(0, 0, N, sh_degree, sh_coeffs, P, means3D, scales, rotations, opacities, shs, confidence, scale_modifier,
                            viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, bg, radii, geom, geom_bytes_, point_list, image,
                            image_bytes_, dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacities,
                            dL_dshs, dL_dmeans2D, dL_dconfidence, workspace, workspace_bytes, stream_);
@@ -634,10 +660,29 @@ extern "C" int syn3r_raster_backward_raw(int N, int sh_degree, int sh_coeffs, lo
                                          const float* dL_dalpha, float* dL_dmeans3D, float* dL_dlog_scales,
                                          float* dL_draw_rotations, float* dL_dopacity_logits, float* dL_dshs, float* dL_dmeans2D,
                                          float* dL_dconfidence, void* workspace, size_t workspace_bytes, void* stream_) {
-    return raster_backward(1, N, sh_degree, sh_coeffs, P, means3D, log_scales, raw_rotations, opacity_logits, shs, confidence,
+    return raster_backward(1, 0, N, sh_degree, sh_coeffs, P, means3D, log_scales, raw_rotations, opacity_logits, shs, confidence,
                            scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, bg, radii, geom, geom_bytes_,
                            point_list, image, image_bytes_, dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dlog_scales,
                            dL_draw_rotations, dL_dopacity_logits, dL_dshs, dL_dmeans2D, dL_dconfidence, workspace, workspace_bytes,
+                           stream_);
+}
+
+extern "C" int syn3r_raster_backward_ex(int N, int sh_degree, int sh_coeffs, long long P, const float* means3D,
+                                        const float* scales, const float* rotations, const float* opacities,
+                                        const float* shs, const float* confidence, float scale_modifier,
+                                        const float* viewmatrix, const float* projmatrix, const float* campos,
+                                        float tanfovx, float tanfovy, int H, int W, const float* bg, const int* radii,
+                                        void* geom, size_t geom_bytes_, const unsigned* point_list, void* image,
+                                        size_t image_bytes_, const float* dL_dcolor, const float* dL_ddepth,
+                                        const float* dL_dalpha, float* dL_dmeans3D, float* dL_dscales,
+                                        float* dL_drotations, float* dL_dopacities, float* dL_dshs, float* dL_dmeans2D,
+                                        float* dL_dconfidence, void* workspace, size_t workspace_bytes, int raw, int flags,
+                                        void* stream_) {
+    SYN3R_REQUIRE(raw == 0 || raw == 1, "raster_backward_ex: raw must be 0 or 1, got %d", raw);
+    return raster_backward(raw, flags, N, sh_degree, sh_coeffs, P, means3D, scales, rotations, opacities, shs, confidence,
+                           scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, bg, radii, geom, geom_bytes_,
+                           point_list, image, image_bytes_, dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dscales,
+                           dL_drotations, dL_dopacities, dL_dshs, dL_dmeans2D, dL_dconfidence, workspace, workspace_bytes,
                            stream_);
 }
 

@@ -21,6 +21,7 @@ constexpr int kTilePix = kTileX * kTileY;       // 256 threads = 4 wavefronts
 constexpr float kNearClip = 0.2f;               // view-space z cull
 constexpr float kFovGuard = 1.3f;               // clamp of t.x/t.z in the EWA Jacobian
 constexpr float kLowPass = 0.3f;                // added to the 2D covariance diagonal
+constexpr float kMipFloor = 0.000025f;          // anti-aliased splatting: floor of det(cov2D) / det(cov2D + kLowPass I), see mip_rho
 constexpr float kAlphaMin = 1.0f / 255.0f;
 constexpr float kAlphaMax = 0.99f;
 constexpr float kTransmittanceMin = 1e-4f;
@@ -30,7 +31,7 @@ constexpr float kLog2e = 1.4426950408889634f;  // the blend kernels' exp(x) is v
 struct alignas(16) Splat {
     float x, y;            // pixel-space mean
     float cxx, cxy, cyy;   // conic (inverse 2D covariance)
-    float opacity;         // opacity * confidence
+    float opacity;         // opacity * confidence (* rho with SYN3R_RASTER_ANTIALIAS, mip_rho below)
     float r, g, b;         // view-dependent colour (SH evaluated, clamped)
     float depth;           // view-space z
     float pad0, pad1;
@@ -43,7 +44,7 @@ struct GeomState {
     float* depths;           // [N]
     float* means2D;          // [N,2]
     float* cov3D;            // [N,6]
-    float* conic_opacity;    // [N,4] conic + raw opacity (without confidence)
+    float* conic_opacity;    // [N,4] conic + raw opacity (without confidence, and without the anti-aliasing factor rho)
     float* rgb;              // [N,3]
     unsigned* clamped;       // [N] bit c set if colour channel c was clamped at 0
     unsigned* tiles_touched; // [N]
@@ -243,6 +244,22 @@ __device__ __forceinline__ EwaRows ewa_rows(const Camera& cam, float t_x, float 
     o.T00 = J00 * v[0] + J02 * v[2]; o.T01 = J00 * v[4] + J02 * v[6]; o.T02 = J00 * v[8] + J02 * v[10];
     o.T10 = J11 * v[1] + J12 * v[2]; o.T11 = J11 * v[5] + J12 * v[6]; o.T12 = J11 * v[9] + J12 * v[10];
     return o;
+}
+// Anti-aliased splatting (the published 3DGS `antialiasing` switch = the 2D Mip filter of Mip-Splatting, Yu et al. CVPR 2024): the
+// factor on the opacity of a splat whose 2D covariance (a, b; b, c) was dilated to (a + kLowPass, b; b, c + kLowPass),
+//     rho = sqrt(max(r, kMipFloor)),  r = (a c - b^2) / ((a + kLowPass)(c + kLowPass) - b^2),
+// from r.  fmaxf drops a NaN operand, so rho is finite whatever the cancellation in r did.  The constants 0.3 and 0.000025 are
+// RECALLED from the published code, which is not available to check against: UNPINNED.
+__device__ __forceinline__ float mip_rho(float r) { return sqrtf(fmaxf(r, kMipFloor)); }
+// r from the covariance before the dilation.  k_preprocess<true> and k_preprocess_bwd<.., true> must agree to the bit on which
+// side of kMipFloor a Gaussian lies (the forward's rho is a constant there, the backward's gradient through rho zero), so both call
+// this one function, and every rounding in it is spelled out: it does not depend on how the compiler contracts either kernel's
+// own determinant (`det` / `den`, the conic's, which may fuse differently in the two).
+__device__ __forceinline__ float mip_ratio(float a, float b, float c) {
+    const float bb = __fmul_rn(b, b);
+    const float d0 = __fmaf_rn(a, c, -bb);
+    const float d1 = __fmaf_rn(__fadd_rn(a, kLowPass), __fadd_rn(c, kLowPass), -bb);
+    return __fdiv_rn(d0, d1);
 }
 
 #ifdef SYN3R_RASTER_STATS      // developer build, per blend kernel: [0] lane tests, [1] wavefront visits, [2] visits with an active pixel, [3] active pixels

@@ -303,6 +303,13 @@ class OptimizationParams:
     spatial_lr_scale: Optional[float] = 1.0     # multiplier of the position rate; None: cameras_extent() when the optimiser is (re)built
     feature_rest_lr_div: float = 1.0            # 1: one rate for all SH coefficients; else rows 1.. of a Gaussian at feature_lr / div
     sh_degree_interval: int = 0                 # 0: active_sh_degree stays; else oneupSHdegree() every that many iterations
+    # Anti-aliased splatting (`GaussianRasterizationSettings.antialiasing`: the published 3DGS switch, Mip-Splatting's 2D Mip filter;
+    # constants UNPINNED, FSGS' fork not known to have it - off by default).  A RENDERING MODE of this trainer: every render it makes
+    # (train steps on both paths, `render_view` and with it `evaluate`, the capacity-seeding renders and the orchestrator's
+    # render_GS) uses it.  It is NOT stored in checkpoints: a model trained with the filter has to be rendered with it (its
+    # opacities have grown to make up for rho < 1), so pass the option again when a checkpoint is loaded.  Density control,
+    # `reset_opacity` and pruning keep reading the raw opacity, as the published code does.
+    antialiasing: bool = False
 
 
 def expon_lr(step, lr_init: float, lr_final: float, lr_delay_steps: int = 0, lr_delay_mult: float = 1.0,
@@ -674,7 +681,7 @@ class GSTrainer:
             image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
             tanfovy=math.tan(cam.FoVy * 0.5), bg=self.background, scale_modifier=scaling_modifier,
             viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform, sh_degree=g.active_sh_degree,
-            campos=cam.camera_center, prefiltered=False, debug=False)
+            campos=cam.camera_center, prefiltered=False, debug=False, antialiasing=bool(self.opt.antialiasing))
         means2D = torch.zeros_like(g.get_xyz, requires_grad=True)
         color, radii, depth, alpha = GaussianRasterizer(st)(g.get_xyz, means2D, g.get_opacity, shs=g.get_features,
                                                             scales=g.get_scaling, rotations=g.get_rotation,
@@ -724,7 +731,7 @@ class GSTrainer:
                 image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
                 tanfovy=math.tan(cam.FoVy * 0.5), bg=self.background, scale_modifier=1.0,
                 viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform, sh_degree=g.active_sh_degree,
-                campos=cam.camera_center, prefiltered=False, debug=False)
+                campos=cam.camera_center, prefiltered=False, debug=False, antialiasing=bool(self.opt.antialiasing))
             # log-scales / raw quaternions / logits in, THEIR gradients out (syn3r_raster_*_raw)
             color, radii, depth, alpha, rstate = rasterize_forward(g._xyz, g._features, g._opacity, g._scaling, g._rotation,
                                                                    g.confidence, st, raw_params=True)

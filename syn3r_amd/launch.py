@@ -110,6 +110,10 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                          "--position_lr_final (default 1.6e-6) over --position_lr_max_steps, times the camera extent; SH rows 1.. at "
                          "feature_lr / 20; SH degree from 0, one up every 1000 iterations (values recalled, UNPINNED: "
                          "gs/trainer.py OptimizationParams).  constant (default): none of them")
+    ap.add_argument("--antialiasing", type=int, default=0, choices=(0, 1),
+                    help="1: anti-aliased splatting in every render of the trainer (OptimizationParams.antialiasing: the published 3DGS "
+                         "switch = Mip-Splatting's 2D Mip filter; constants recalled, UNPINNED).  Not stored in checkpoints: a model "
+                         "trained with it has to be rendered with it.  0 (default): the plain 0.3 px dilation")
     ap.add_argument("--num_inference_steps", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     # FSGS' parameter groups (scripts/train.py:44-46: -s, --eval, --n_views, --resolution, --use_dust3r ... of the batch scripts)
@@ -118,7 +122,7 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     args, rest = ap.parse_known_args(given)
     # argparse takes `--percent_dens` for an abbreviation of `--percent_dense`: while that flag sat in FSGS_FLAGS the token was an
     # unknown argument, and a misspelling stays one
-    declared = ["--" + f for f, _ in TRAINER_FLAGS] + ["--gs_schedule", "--pixel_confidence"]
+    declared = ["--" + f for f, _ in TRAINER_FLAGS] + ["--gs_schedule", "--pixel_confidence", "--antialiasing"]
     cut = [t for t in given if t.startswith("--") and any(d != t.split("=")[0] and d.startswith(t.split("=")[0]) for d in declared)]
     if cut:
         ap.error(f"unknown argument(s): {' '.join(cut)} (the trainer's flags are not abbreviated)")
@@ -147,7 +151,8 @@ def apply_trainer_flags(opt, args):
     """-> a copy of `opt` (gs.OptimizationParams) with the TRAINER_FLAGS that were given (not None) in their fields, and with
     `--gs_schedule published` the switches of the three published optimiser rules: decay to --position_lr_final or 1.6e-6,
     spatial_lr_scale = None (the camera extent), feature_rest_lr_div = 20, sh_degree_interval = 1000.  Pure: no GPU, `opt`
-    untouched.  (--sh_degree describes the model, not the optimiser: the scene factory reads it.)"""
+    untouched.  `--antialiasing 1` sets `antialiasing` (0, the default, leaves the field as `opt` has it).  (--sh_degree
+    describes the model, not the optimiser: the scene factory reads it.)"""
     import dataclasses
     new = {}
     for flag, _ in TRAINER_FLAGS:
@@ -158,6 +163,8 @@ def apply_trainer_flags(opt, args):
         if new.get("position_lr_final", opt.position_lr_final) is None:
             new["position_lr_final"] = 1.6e-6
         new.update(spatial_lr_scale=None, feature_rest_lr_div=20.0, sh_degree_interval=1000)
+    if getattr(args, "antialiasing", 0):
+        new["antialiasing"] = True
     return dataclasses.replace(opt, **new)
 
 

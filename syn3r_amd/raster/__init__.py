@@ -28,6 +28,11 @@ class GaussianRasterizationSettings(NamedTuple):
     campos: torch.Tensor
     prefiltered: bool = False
     debug: bool = False
+    # The published rasteriser's switch (last field there too): anti-aliased splatting, the 2D Mip filter of Mip-Splatting.  The
+    # 0.3 px^2 dilation stays and the blend opacity is multiplied by sqrt(max(det(cov2D) / det(cov2D + 0.3 I), 0.000025)), so a
+    # splat keeps its energy whatever its size on screen (SYN3R_RASTER_ANTIALIAS in include/syn3r_hip.h; constants UNPINNED).
+    # Off by default: FSGS' confidence fork is not known to have it.  Radii and tile lists do not depend on it.
+    antialiasing: bool = False
 
 
 _host_cache: dict = {}
@@ -131,6 +136,11 @@ def capacity_key(dev: torch.device, N: int, H: int, W: int):
     return (dev.index, int(N), int(H), int(W))
 
 
+def _flags(s: GaussianRasterizationSettings) -> int:
+    """the `flags` of syn3r_raster_preprocess_ex / syn3r_raster_backward_ex for these settings"""
+    return L.RASTER_ANTIALIAS if s.antialiasing else 0
+
+
 class RasterState:
     """What `rasterize_forward` leaves for `rasterize_backward`: the (detached, contiguous fp32) inputs, the device state of the two
     forward stages and the host-side constants.  A plain object: the autograd Function stores its tensors through
@@ -140,10 +150,11 @@ class RasterState:
 
 def rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, settings: GaussianRasterizationSettings,
                       raw_params: bool = False):
-    """Both forward stages (`syn3r_raster_preprocess[_raw]`, `syn3r_raster_render`); returns (color, radii, depth, alpha, state).
+    """Both forward stages (`syn3r_raster_preprocess_ex`, `syn3r_raster_render`); returns (color, radii, depth, alpha, state).
     `raw_params`: `scales`, `rotations`, `opacities` are the trainer's PARAMETERS (log-scales, unnormalised quaternions, logits);
     the published activations run inside the projection kernel and `rasterize_backward` returns the gradients of the parameters
-    (`syn3r_raster_backward_raw`)."""
+    (`syn3r_raster_backward_ex` with raw = 1).  `settings.antialiasing` goes to both passes as SYN3R_RASTER_ANTIALIAS: the state
+    keeps the settings, so `rasterize_backward` cannot be given another mode than the forward."""
     s = settings
     dev = L.require_gpu(means3D, shs, opacities, scales, rotations)
     lib = L.load()
@@ -175,12 +186,11 @@ def rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, se
             raise err
     use_async = use_async and key in _capacity
     P = C.c_longlong(0)
-    preprocess = lib.syn3r_raster_preprocess_raw if raw_params else lib.syn3r_raster_preprocess
-    rc = preprocess(N, int(s.sh_degree), M, L.ptr(m3), L.ptr(sc), L.ptr(ro), L.ptr(op), L.ptr(sh),
-                    L.ptr(cf), float(s.scale_modifier), view, proj, campos, float(s.tanfovx),
-                    float(s.tanfovy), H, W, L.ptr(radii), L.ptr(geom), geom.numel(),
-                    None if use_async else C.byref(P), stream)
-    L.check(rc, "syn3r_raster_preprocess")
+    rc = lib.syn3r_raster_preprocess_ex(N, int(s.sh_degree), M, L.ptr(m3), L.ptr(sc), L.ptr(ro), L.ptr(op), L.ptr(sh),
+                                        L.ptr(cf), float(s.scale_modifier), view, proj, campos, float(s.tanfovx),
+                                        float(s.tanfovy), H, W, L.ptr(radii), L.ptr(geom), geom.numel(),
+                                        None if use_async else C.byref(P), int(bool(raw_params)), _flags(s), stream)
+    L.check(rc, "syn3r_raster_preprocess_ex")
     if use_async:
         P = _capacity[key]                          # capacity; the kernels read the live count on the device
     else:
@@ -220,7 +230,7 @@ def rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, se
 
 
 def rasterize_backward(st: RasterState, g_color, g_depth=None, g_alpha=None):
-    """Backward of both stages (`syn3r_raster_backward[_raw]`): (d_means3D, d_means2D, d_shs, d_opacities, d_scales, d_rotations,
+    """Backward of both stages (`syn3r_raster_backward_ex`, in the forward's mode): (d_means3D, d_means2D, d_shs, d_opacities, d_scales, d_rotations,
     d_confidence or None) - with `raw_params` the gradients of the log-scales / raw quaternions / logits."""
     m3, sc, ro, op, sh, cf, radii, geom, binning, image = st.tensors
     s = st.settings
@@ -236,14 +246,13 @@ def rasterize_backward(st: RasterState, g_color, g_depth=None, g_alpha=None):
     d_m3, d_sc, d_ro, d_op, d_sh, d_m2 = new(N, 3), new(N, 3), new(N, 4), new(N), new(N, M, 3), new(N, 3)
     d_cf = new(N) if st.has_conf else None
     ws = L.workspace(dev, lib.syn3r_raster_backward_workspace_bytes(N), "raster_bwd")
-    backward = lib.syn3r_raster_backward_raw if st.raw_params else lib.syn3r_raster_backward
-    rc = backward(
+    rc = lib.syn3r_raster_backward_ex(
         N, int(s.sh_degree), M, st.P, L.ptr(m3), L.ptr(sc), L.ptr(ro), L.ptr(op), L.ptr(sh),
         L.ptr(cf) if st.has_conf else None, float(s.scale_modifier), view, proj, campos, float(s.tanfovx),
         float(s.tanfovy), H, W, bg, L.ptr(radii), L.ptr(geom), geom.numel(), st.plist, L.ptr(image), image.numel(),
         L.ptr(gc), L.ptr(gd), L.ptr(ga), L.ptr(d_m3), L.ptr(d_sc), L.ptr(d_ro), L.ptr(d_op), L.ptr(d_sh),
-        L.ptr(d_m2), L.ptr(d_cf), L.ptr(ws), ws.numel(), L.stream_ptr(dev))
-    L.check(rc, "syn3r_raster_backward")
+        L.ptr(d_m2), L.ptr(d_cf), L.ptr(ws), ws.numel(), int(st.raw_params), _flags(s), L.stream_ptr(dev))
+    L.check(rc, "syn3r_raster_backward_ex")
     return d_m3, d_m2, d_sh, d_op.reshape(st.opacity_shape), d_sc, d_ro, d_cf
 
 
