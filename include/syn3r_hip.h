@@ -348,6 +348,62 @@ int syn3r_raster_backward_ex(int N, int sh_degree, int sh_coeffs, long long P, c
                              void* stream);
 
 /*
+ * 3D smoothing filter of Mip-Splatting (Yu et al., CVPR 2024, section 4.1), the other half of the method next to
+ * SYN3R_RASTER_ANTIALIAS: every Gaussian is bounded from below by the sampling rate of the cameras that trained it, so that a
+ * render from closer than any training view shows no needles or holes.
+ *
+ * syn3r_filter3d_compute - the per-Gaussian filter.  xyz [n,3]; cams [n_cams,16] DEVICE floats, per camera the 12 entries of the
+ * world-to-view matrix [R | t] row by row (x = c0 px + c1 py + c2 pz + c3, y from c4..c7, z from c8..c11), then fx, fy, W, H in
+ * pixels.  Camera c SEES Gaussian k iff z > near and (fx x / z + W / 2, fy y / z + H / 2) lies in [-margin W, (1 + margin) W] x
+ * [-margin H, (1 + margin) H].  The sampling rate is nu_k = max over the seeing cameras of fx / z (the paper's Eq. 6; the released
+ * code's min depth / max focal when all focal lengths agree) and
+ *     filter_out[k] = sqrt(variance) / nu_k.
+ * A Gaussian no camera sees gets the LARGEST filter among the seen ones (the released code's rule); if none is seen at all every
+ * filter is 0.  Never NaN or inf for finite inputs.  variance = 0.2, near = 0.2, margin = 0.15 are RECALLED from the released
+ * Mip-Splatting code (compute_3D_filter), which is not available to check against: UNPINNED, hence arguments.
+ * ws: syn3r_filter3d_workspace_bytes(n) bytes of device scratch (0 for n outside 1 .. 2^24).  Two launches and a 4-byte memset on
+ * `stream`; no host read, no synchronisation.  Rejected on the host before any HIP call: null pointers, n or n_cams outside
+ * 1 .. 2^24, variance / near not positive, margin negative (SYN3R_E_INVALID), a short workspace (SYN3R_E_WORKSPACE).
+ */
+size_t syn3r_filter3d_workspace_bytes(int n);
+int syn3r_filter3d_compute(const float* xyz, int n, const float* cams, int n_cams, float variance, float near, float margin,
+                           float* filter_out, void* ws, size_t ws_bytes, void* stream);
+/*
+ * syn3r_raster_preprocess_ex with the filter: arguments as there, then `filter3d` ([N] device floats >= 0, or NULL) before the
+ * stream.  NULL is syn3r_raster_preprocess_ex bit for bit; `raw` and `flags` are validated exactly as there.  With a filter f and the
+ * ACTIVATED scales s_i (raw = 1: after the exp) the Gaussian is rendered with
+ *     q_i = sqrt(s_i^2 + f^2)   (the covariance is built from scale_modifier q_i)   and   coef = prod_i s_i / q_i
+ * on its opacity: the blend multiplies opacity * coef * confidence, with SYN3R_RASTER_ANTIALIAS opacity * coef * rho * confidence
+ * where rho comes from the FILTERED covariance.  coef = sqrt(det Sigma / det(Sigma + f^2 I)) is formed as the product of the three
+ * ratios, so a scale of 1e-6 under a filter of 1e-2 is 1e-12, not a NaN.  Radii, tile lists and depth keys are those of the
+ * filtered Gaussian and differ from an unfiltered render; the geometry buffer holds the opacity WITHOUT coef (and without rho).
+ */
+int syn3r_raster_preprocess_f3d(int N, int sh_degree, int sh_coeffs, const float* means3D, const float* scales,
+                                const float* rotations, const float* opacities, const float* shs,
+                                const float* confidence, float scale_modifier, const float* viewmatrix,
+                                const float* projmatrix, const float* campos, float tanfovx, float tanfovy, int H,
+                                int W, int* radii, void* geom, size_t geom_bytes, long long* num_rendered_host,
+                                int raw, int flags, const float* filter3d, void* stream);
+/*
+ * syn3r_raster_backward_ex with the filter; `raw`, `flags` and `filter3d` MUST be the forward's (NULL: syn3r_raster_backward_ex
+ * bit for bit).  With G = dL/d(blend opacity): dL/dopacity = G coef [rho] confidence, dL/dconfidence = G opacity coef [rho], the
+ * rho terms of SYN3R_RASTER_ANTIALIAS carry coef, and
+ *     dL/ds_i = dL/dq_i s_i / q_i + G opacity confidence [rho] coef f^2 / (s_i q_i^2),
+ * evaluated without the division by s_i (raw = 1: dL/dlog s_i = dL/dq_i s_i^2 / q_i + G opacity confidence [rho] coef f^2 / q_i^2).
+ * coef is formed again with the forward's arithmetic.  The filter receives no gradient.
+ */
+int syn3r_raster_backward_f3d(int N, int sh_degree, int sh_coeffs, long long P, const float* means3D,
+                              const float* scales, const float* rotations, const float* opacities, const float* shs,
+                              const float* confidence, float scale_modifier, const float* viewmatrix,
+                              const float* projmatrix, const float* campos, float tanfovx, float tanfovy, int H, int W,
+                              const float* bg, const int* radii, void* geom, size_t geom_bytes,
+                              const unsigned* point_list, void* image, size_t image_bytes, const float* dL_dcolor,
+                              const float* dL_ddepth, const float* dL_dalpha, float* dL_dmeans3D, float* dL_dscales,
+                              float* dL_drotations, float* dL_dopacities, float* dL_dshs, float* dL_dmeans2D,
+                              float* dL_dconfidence, void* workspace, size_t workspace_bytes, int raw, int flags,
+                              const float* filter3d, void* stream);
+
+/*
  * Stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits) — the
  * tile/depth sort of the rasteriser (cub::DeviceRadixSort::SortPairs in the
  * published implementation).  Ping-pongs between the two buffer pairs;

@@ -23,6 +23,9 @@ c_d = C.c_double
 F32, F16 = 0, 1
 RASTER_ANTIALIAS = 1          # SYN3R_RASTER_ANTIALIAS: bit 0 of the `flags` of syn3r_raster_preprocess_ex / syn3r_raster_backward_ex
 
+# Mip-Splatting's 3D smoothing filter (syn3r_filter3d_compute): RECALLED from the released code, UNPINNED (include/syn3r_hip.h)
+FILTER3D_VARIANCE, FILTER3D_NEAR, FILTER3D_MARGIN = 0.2, 0.2, 0.15
+
 # name -> (restype, argtypes); mirrors include/syn3r_hip.h declaration by declaration
 SIGNATURES = {
     "syn3r_last_error": (C.c_char_p, []),
@@ -67,6 +70,13 @@ SIGNATURES = {
     "syn3r_raster_backward_ex": (c_i, [c_i, c_i, c_i, c_ll, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_f, c_f,
                                        c_i, c_i, c_p, c_p, c_p, c_sz, c_p, c_p, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                        c_p, c_p, c_p, c_p, c_sz, c_i, c_i, c_p]),
+    "syn3r_filter3d_workspace_bytes": (c_sz, [c_i]),
+    "syn3r_filter3d_compute": (c_i, [c_p, c_i, c_p, c_i, c_f, c_f, c_f, c_p, c_p, c_sz, c_p]),
+    "syn3r_raster_preprocess_f3d": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_f, c_f,
+                                          c_i, c_i, c_p, c_p, c_sz, C.POINTER(c_ll), c_i, c_i, c_p, c_p]),
+    "syn3r_raster_backward_f3d": (c_i, [c_i, c_i, c_i, c_ll, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_f, c_f,
+                                        c_i, c_i, c_p, c_p, c_p, c_sz, c_p, c_p, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                        c_p, c_p, c_p, c_p, c_sz, c_i, c_i, c_p, c_p]),
     "syn3r_sort_pairs_workspace_bytes": (c_sz, [c_ll]),
     "syn3r_sort_pairs": (c_i, [c_p, c_p, c_p, c_p, c_ll, c_i, c_p, c_sz, C.POINTER(c_i), c_p]),
     "syn3r_gaussian_activate": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),

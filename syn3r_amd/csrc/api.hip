@@ -13,7 +13,7 @@ void set_error(const char* fmt, ...) {
 }  // namespace syn3r
 
 extern "C" const char* syn3r_last_error(void) { return syn3r::g_err; }
-extern "C" int syn3r_version(void) { return 300; }
+extern "C" int syn3r_version(void) { return 310; }
 extern "C" const char* syn3r_arch(void) { return "gfx950"; }
 
 // ---------------------------------------------------------------- kernel tracer

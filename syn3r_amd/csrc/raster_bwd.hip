@@ -362,15 +362,24 @@ __device__ __forceinline__ F3 sh_backward(int D, int M, F3 pos, const float* cam
 //     dr/db = -2 b (d1 - d0) / d1^2 = -2 b h (a + C) / d1^2
 // (the right-hand forms are the same polynomials with A - a = C - c = h taken out: no difference of two large products in fp32).
 // rho is formed again here, by the function k_preprocess<true> called (mip_ratio); GeomState::conic_opacity[3] holds op without it.
+// F3D (syn3r_raster_backward_f3d with a filter; k_preprocess<.., true> made the forward): the covariance was built from
+// q_i = sqrt(s_i^2 + f^2) and the blend multiplied op * coef [* rho] * cf, coef = prod r_i, r_i = s_i / q_i (f3d_scales, raster_common.h:
+// formed again here, the forward's bits).  With G = gr[G_OP]: dL/dop = G coef [rho] cf, dL/dcf = G op coef [rho], the rho terms above
+// carry coef, and the scales receive
+//     dL/ds_i = dL/dq_i r_i + G op cf [rho] coef f^2 / (s_i q_i^2)         (dq_i/ds_i = r_i, dcoef/ds_i = coef f^2 / (s_i q_i^2))
+// evaluated WITHOUT the division by s_i: coef / s_i = prod_{j != i} r_j / q_i on the activated route, and on the raw route the
+// chain rule's factor s_i cancels it (dL/dlog s_i = dL/dq_i r_i s_i + G op cf [rho] coef f^2 / q_i^2).  The filter gets no gradient.
+// The scales are loaded BEFORE the opacity gradient is written on this path only (coef is needed there); F3D = false is the code
+// of the `_ex` entries.
 constexpr int kShLd = 49;      // LDS row stride (floats): odd, so the 64 rows of a wavefront fall into 64 banks
-template <bool STAGED, bool AA>
+template <bool STAGED, bool AA, bool F3D>
 __global__ void __launch_bounds__(256) k_preprocess_bwd(
     int N, int D, int M, const float* __restrict__ means3D, const float* __restrict__ scales,
     const float* __restrict__ rots, const float* __restrict__ opacities, const float* __restrict__ shs,
     const float* __restrict__ conf, float scale_mod, Camera cam, const int* __restrict__ radii, GeomState g,
     const float* __restrict__ grad_rec, float* __restrict__ dL_dmeans3D, float* __restrict__ dL_dscales,
     float* __restrict__ dL_drots, float* __restrict__ dL_dopacity, float* __restrict__ dL_dshs,
-    float* __restrict__ dL_dmeans2D, float* __restrict__ dL_dconf, int raw) {
+    float* __restrict__ dL_dmeans2D, float* __restrict__ dL_dconf, int raw, const float* __restrict__ filter3d) {
     __shared__ float shl[STAGED ? 256 * kShLd : 1];
     const int i = blockIdx.x * 256 + threadIdx.x;
     const size_t blk0 = (size_t)blockIdx.x * 256 * 48;                // first float of the block's rows
@@ -451,12 +460,20 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(
     // as the two-launch route
     const float cf = conf ? conf[i] : 1.0f;
     const float op_a = raw ? act_sigmoid(opacities[i]) : opacities[i];
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+    F3dScales fs;
+    if constexpr (F3D) {
+        s0 = scales[3 * i]; s1 = scales[3 * i + 1]; s2 = scales[3 * i + 2];
+        if (raw) { s0 = act_exp(s0); s1 = act_exp(s1); s2 = act_exp(s2); }
+        fs = f3d_scales(s0, s1, s2, filter3d[i]);
+    }
     float rho = 1.0f;
     if constexpr (AA) {
         const float r = mip_ratio(pA, B, pC), den_inv = 1.0f / den;     // r: the forward's bits (one function, explicit roundings)
         rho = mip_rho(r);
         if (r > kMipFloor) {
-            const float k = gr[G_OP] * op_a * cf / (2.0f * rho) * kLowPass * den_inv * den_inv;   // dL/dr h / d1^2
+            float k = gr[G_OP] * op_a * cf / (2.0f * rho) * kLowPass * den_inv * den_inv;   // dL/dr h / d1^2
+            if constexpr (F3D) k *= fs.coef;
             dL_dA += k * (pC * C + B * B);
             dL_dC += k * (pA * A + B * B);
             dL_dB -= k * 2.0f * B * (pA + C);
@@ -506,20 +523,22 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(
     dL_dmeans3D[3 * i] = dmean.x; dL_dmeans3D[3 * i + 1] = dmean.y; dL_dmeans3D[3 * i + 2] = dmean.z;
 
     // ---- opacity / confidence (blend used opacity * confidence; cf and op_a: above the AA block)
-    const float g_op = AA ? gr[G_OP] * rho : gr[G_OP];      // dL/d(op x cf)
+    float g_op = AA ? gr[G_OP] * rho : gr[G_OP];            // dL/d(op x cf)
+    if constexpr (F3D) g_op *= fs.coef;                     // (the blend multiplied op x coef x cf)
     dL_dopacity[i] = raw ? act_sigmoid_bwd(op_a, g_op * cf) : g_op * cf;
     if (dL_dconf) dL_dconf[i] = g_op * op_a;
 
     // ---- Sigma = M M^T, M = R S  -> scale, rotation
-    float s0 = scales[3 * i], s1 = scales[3 * i + 1], s2 = scales[3 * i + 2];
+    if constexpr (!F3D) { s0 = scales[3 * i]; s1 = scales[3 * i + 1]; s2 = scales[3 * i + 2]; }
     float4 q4 = make_float4(rots[4 * i], rots[4 * i + 1], rots[4 * i + 2], rots[4 * i + 3]);
     float q_inv = 1.0f;
     if (raw) {
-        s0 = act_exp(s0); s1 = act_exp(s1); s2 = act_exp(s2);
+        if constexpr (!F3D) { s0 = act_exp(s0); s1 = act_exp(s1); s2 = act_exp(s2); }
         q_inv = act_quat_inv_norm(q4);
         q4 = act_quat(q4, q_inv);
     }
     float sx = scale_mod * s0, sy = scale_mod * s1, sz = scale_mod * s2;
+    if constexpr (F3D) { sx = scale_mod * fs.q0; sy = scale_mod * fs.q1; sz = scale_mod * fs.q2; }   // the covariance's scales
     float qr = q4.x, qx = q4.y, qy = q4.z, qz = q4.w;
     const auto [R00, R01, R02, R10, R11, R12, R20, R21, R22] = quat_rotation(q4);
     float m00 = R00 * sx, m01 = R01 * sy, m02 = R02 * sz;
@@ -547,7 +566,26 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(
                   2.f * qy * dR22);
     dq.w = 2.f * (-2.f * qz * dR00 - qr * dR01 + qx * dR02 + qr * dR10 - 2.f * qz * dR11 + qy * dR12 +
                   qx * dR20 + qy * dR21);
-    if (raw) {
+    if constexpr (F3D) {
+        // ds_i is dL/dq_i so far; kc = G op cf [rho] = dL/dcoef.  fs.ff == 0: coef is the constant 1 (and q_i may be 0)
+        const float kc = (AA ? gr[G_OP] * rho : gr[G_OP]) * op_a * cf;
+        if (raw) {
+            ds0 *= fs.r0 * s0; ds1 *= fs.r1 * s1; ds2 *= fs.r2 * s2;
+            if (fs.ff > 0.0f) {
+                const float kf = kc * fs.coef * fs.ff;
+                ds0 += kf / (fs.q0 * fs.q0); ds1 += kf / (fs.q1 * fs.q1); ds2 += kf / (fs.q2 * fs.q2);
+            }
+        } else {
+            ds0 *= fs.r0; ds1 *= fs.r1; ds2 *= fs.r2;
+            if (fs.ff > 0.0f) {
+                const float kf = kc * fs.ff;
+                ds0 += kf * (fs.r1 * fs.r2) / (fs.q0 * fs.q0 * fs.q0);
+                ds1 += kf * (fs.r0 * fs.r2) / (fs.q1 * fs.q1 * fs.q1);
+                ds2 += kf * (fs.r0 * fs.r1) / (fs.q2 * fs.q2 * fs.q2);
+            }
+        }
+        if (raw) dq = act_quat_bwd(q4, dq, q_inv);
+    } else if (raw) {
         ds0 *= s0; ds1 *= s1; ds2 *= s2;
         dq = act_quat_bwd(q4, dq, q_inv);
     }
@@ -582,7 +620,8 @@ static int raster_backward(int raw, int flags, int N, int sh_degree, int sh_coef
                                      size_t image_bytes_, const float* dL_dcolor, const float* dL_ddepth,
                                      const float* dL_dalpha, float* dL_dmeans3D, float* dL_dscales,
                                      float* dL_drotations, float* dL_dopacities, float* dL_dshs, float* dL_dmeans2D,
-                                     float* dL_dconfidence, void* workspace, size_t workspace_bytes, void* stream_) {
+                                     float* dL_dconfidence, void* workspace, size_t workspace_bytes, const float* filter3d,
+                                     void* stream_) {
     SYN3R_REQUIRE((flags & ~SYN3R_RASTER_ANTIALIAS) == 0, "raster_backward: unknown flag bits 0x%x", (unsigned)flags & ~(unsigned)SYN3R_RASTER_ANTIALIAS);
     SYN3R_REQUIRE(N > 0 && H > 0 && W > 0 && P >= 0, "raster_backward: bad sizes N=%d H=%d W=%d P=%lld", N, H, W, P);
     SYN3R_REQUIRE(sh_degree >= 0 && sh_degree <= 3 && sh_coeffs >= (sh_degree + 1) * (sh_degree + 1),
@@ -623,12 +662,18 @@ static int raster_backward(int raw, int flags, int N, int sh_degree, int sh_coef
     SYN3R_LAUNCH_NAMED(name, (k_preprocess_bwd<__VA_ARGS__>), dim3(ceil_div(N, 256)), dim3(256), 0, stream, N, sh_degree,     \
                        sh_coeffs, means3D, scales, rotations, opacities, shs, confidence, scale_modifier, cam, radii, g,    \
                        grad_rec, dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacities, dL_dshs, dL_dmeans2D,               \
-                       dL_dconfidence, raw)
+                       dL_dconfidence, raw, filter3d)
     const bool aa = (flags & SYN3R_RASTER_ANTIALIAS) != 0;
-    if (staged && aa) PREPROCESS_BWD("k_preprocess_bwd<true>", true, true);
-    else if (staged) PREPROCESS_BWD("k_preprocess_bwd<true>", true, false);
-    else if (aa) PREPROCESS_BWD("k_preprocess_bwd<false>", false, true);
-    else PREPROCESS_BWD("k_preprocess_bwd<false>", false, false);
+    if (filter3d) {
+        if (staged && aa) PREPROCESS_BWD("k_preprocess_bwd<true>", true, true, true);
+        else if (staged) PREPROCESS_BWD("k_preprocess_bwd<true>", true, false, true);
+        else if (aa) PREPROCESS_BWD("k_preprocess_bwd<false>", false, true, true);
+        else PREPROCESS_BWD("k_preprocess_bwd<false>", false, false, true);
+    }
+    else if (staged && aa) PREPROCESS_BWD("k_preprocess_bwd<true>", true, true, false);
+    else if (staged) PREPROCESS_BWD("k_preprocess_bwd<true>", true, false, false);
+    else if (aa) PREPROCESS_BWD("k_preprocess_bwd<false>", false, true, false);
+    else PREPROCESS_BWD("k_preprocess_bwd<false>", false, false, false);
 #undef PREPROCESS_BWD
     SYN3R_LAUNCH_CHECK("raster_backward launch");
     return SYN3R_OK;
@@ -647,7 +692,7 @@ extern "C" int syn3r_raster_backward(int N, int sh_degree, int sh_coeffs, long l
     return raster_backward(0, 0, N, sh_degree, sh_coeffs, P, means3D, scales, rotations, opacities, shs, confidence, scale_modifier,
                            viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, bg, radii, geom, geom_bytes_, point_list, image,
                            image_bytes_, dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacities,
-                           dL_dshs, dL_dmeans2D, dL_dconfidence, workspace, workspace_bytes, stream_);
+                           dL_dshs, dL_dmeans2D, dL_dconfidence, workspace, workspace_bytes, nullptr, stream_);
 }
 
 extern "C" int syn3r_raster_backward_raw(int N, int sh_degree, int sh_coeffs, long long P, const float* means3D,
@@ -664,7 +709,7 @@ extern "C" int syn3r_raster_backward_raw(int N, int sh_degree, int sh_coeffs, lo
                            scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, bg, radii, geom, geom_bytes_,
                            point_list, image, image_bytes_, dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dlog_scales,
                            dL_draw_rotations, dL_dopacity_logits, dL_dshs, dL_dmeans2D, dL_dconfidence, workspace, workspace_bytes,
-                           stream_);
+                           nullptr, stream_);
 }
 
 extern "C" int syn3r_raster_backward_ex(int N, int sh_degree, int sh_coeffs, long long P, const float* means3D,
@@ -683,7 +728,26 @@ extern "C" int syn3r_raster_backward_ex(int N, int sh_degree, int sh_coeffs, lon
                            scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, bg, radii, geom, geom_bytes_,
                            point_list, image, image_bytes_, dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dscales,
                            dL_drotations, dL_dopacities, dL_dshs, dL_dmeans2D, dL_dconfidence, workspace, workspace_bytes,
-                           stream_);
+                           nullptr, stream_);
+}
+
+extern "C" int syn3r_raster_backward_f3d(int N, int sh_degree, int sh_coeffs, long long P, const float* means3D,
+                                         const float* scales, const float* rotations, const float* opacities,
+                                         const float* shs, const float* confidence, float scale_modifier,
+                                         const float* viewmatrix, const float* projmatrix, const float* campos,
+                                         float tanfovx, float tanfovy, int H, int W, const float* bg, const int* radii,
+                                         void* geom, size_t geom_bytes_, const unsigned* point_list, void* image,
+                                         size_t image_bytes_, const float* dL_dcolor, const float* dL_ddepth,
+                                         const float* dL_dalpha, float* dL_dmeans3D, float* dL_dscales,
+                                         float* dL_drotations, float* dL_dopacities, float* dL_dshs, float* dL_dmeans2D,
+                                         float* dL_dconfidence, void* workspace, size_t workspace_bytes, int raw, int flags,
+                                         const float* filter3d, void* stream_) {
+    SYN3R_REQUIRE(raw == 0 || raw == 1, "raster_backward_f3d: raw must be 0 or 1, got %d", raw);
+    return raster_backward(raw, flags, N, sh_degree, sh_coeffs, P, means3D, scales, rotations, opacities, shs, confidence,
+                           scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, bg, radii, geom, geom_bytes_,
+                           point_list, image, image_bytes_, dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dscales,
+                           dL_drotations, dL_dopacities, dL_dshs, dL_dmeans2D, dL_dconfidence, workspace, workspace_bytes,
+                           filter3d, stream_);
 }
 
 #ifdef SYN3R_RASTER_STATS

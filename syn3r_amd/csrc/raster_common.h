@@ -262,7 +262,26 @@ __device__ __forceinline__ float mip_ratio(float a, float b, float c) {
     return __fdiv_rn(d0, d1);
 }
 
-#ifdef SYN3R_RASTER_STATS      // developer build, per blend kernel: [0] lane tests, [1] wavefront visits, [2] visits with an active pixel, [3] active pixels
+// 3D smoothing filter of Mip-Splatting (Yu et al. CVPR 2024, section 4.1; syn3r_raster_preprocess_f3d in the header): a Gaussian with
+// activated scales s_i and filter f (csrc/filter3d.hip: sqrt(variance) / its largest sampling rate over the training cameras) is
+// rendered with  q_i = sqrt(s_i^2 + f^2)  and its opacity times  coef = prod_i s_i / q_i  (= sqrt(det Sigma / det(Sigma + f^2 I)):
+// the rotation drops out).  coef is the product of the three per-axis ratios r_i, never a ratio of determinants: s = 1e-6 against
+// f = 1e-2 gives r = 1e-4 and coef = 1e-12, where s^6 would have left fp32.  k_preprocess<.., true> and k_preprocess_bwd<.., true>
+// call this one function with every rounding spelled out, so the backward's coef is the forward's bits.  f = 0 (no camera saw any
+// Gaussian) leaves q = s, r = 1, also for s = 0.
+struct F3dScales { float q0, q1, q2, r0, r1, r2, coef, ff; };
+__device__ __forceinline__ F3dScales f3d_scales(float s0, float s1, float s2, float f) {
+    F3dScales o;
+    o.ff = __fmul_rn(f, f);
+    o.q0 = sqrtf(__fmaf_rn(s0, s0, o.ff)); o.q1 = sqrtf(__fmaf_rn(s1, s1, o.ff)); o.q2 = sqrtf(__fmaf_rn(s2, s2, o.ff));
+    o.r0 = o.q0 > 0.0f ? __fdiv_rn(s0, o.q0) : 1.0f;
+    o.r1 = o.q1 > 0.0f ? __fdiv_rn(s1, o.q1) : 1.0f;
+    o.r2 = o.q2 > 0.0f ? __fdiv_rn(s2, o.q2) : 1.0f;
+    o.coef = __fmul_rn(__fmul_rn(o.r0, o.r1), o.r2);
+    return o;
+}
+
+#ifdef SYN3R_RASTER_STATS     // developer build, per blend kernel: [0] lane tests, [1] wavefront visits, [2] visits with an active pixel, [3] active pixels
 #define RASTER_STAT(arr, i, n) do { if (lane == 0) atomicAdd(&arr[i], (unsigned long long)(n)); } while (0)
 #else
 #define RASTER_STAT(arr, i, n)

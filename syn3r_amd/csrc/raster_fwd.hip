@@ -141,14 +141,18 @@ __device__ float3 sh_to_rgb(int D, int M, float3 pos, const float* campos, const
 // as with AA = false (same expressions), so the tile lists are too.  GeomState::conic_opacity[3] keeps `op` WITHOUT rho:
 // k_preprocess_bwd<.., true> forms rho again through the same function (mip_ratio, raster_common.h: explicit roundings).
 // In fp32 the first determinant can cancel to zero or below (needles): the max puts those on the floor, never a NaN.
-template <bool AA>
+// F3D (syn3r_raster_preprocess_f3d with a filter: Mip-Splatting's 3D smoothing filter, f3d_scales in raster_common.h): the covariance
+// is built from q_i = sqrt(s_i^2 + f^2) instead of the activated scales s_i and the blend opacity carries coef = prod s_i / q_i (with
+// AA: op * coef * rho * cf, rho from the FILTERED covariance).  conic_opacity[3] keeps the plain op here too; radii, tile lists and
+// depth keys are those of the filtered Gaussian.  F3D = false is the code of the `_ex` entries, instruction for instruction.
+template <bool AA, bool F3D>
 __global__ void __launch_bounds__(256) k_preprocess(int N, int D, int M, const float* __restrict__ means3D,
                                                     const float* __restrict__ scales,
                                                     const float* __restrict__ rots,
                                                     const float* __restrict__ opacities,
                                                     const float* __restrict__ shs, const float* __restrict__ conf,
                                                     float scale_mod, Camera cam, int* __restrict__ radii,
-                                                    GeomState g, int raw) {
+                                                    GeomState g, int raw, const float* __restrict__ filter3d) {
     int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
     if (i < 4) g.header[i] = 0u;            // pair count (written by the scan that follows) and overflow flag
@@ -170,6 +174,11 @@ __global__ void __launch_bounds__(256) k_preprocess(int N, int D, int M, const f
     if (raw) {
         s0 = act_exp(s0); s1 = act_exp(s1); s2 = act_exp(s2);
         q4 = act_quat(q4, act_quat_inv_norm(q4));
+    }
+    float coef = 1.0f;
+    if constexpr (F3D) {
+        const F3dScales fs = f3d_scales(s0, s1, s2, filter3d[i]);
+        s0 = fs.q0; s1 = fs.q1; s2 = fs.q2; coef = fs.coef;
     }
     float sx = scale_mod * s0, sy = scale_mod * s1, sz = scale_mod * s2;
     const Rot3 k = quat_rotation(q4);
@@ -215,6 +224,7 @@ __global__ void __launch_bounds__(256) k_preprocess(int N, int D, int M, const f
     float cf = conf ? conf[i] : 1.0f;
     float blend_op = op * cf;
     if constexpr (AA) blend_op = op * mip_rho(mip_ratio(pxx, cxy, pyy)) * cf;
+    if constexpr (F3D) blend_op = AA ? op * coef * mip_rho(mip_ratio(pxx, cxy, pyy)) * cf : op * coef * cf;
     g.depths[i] = t.z;
     g.dkeys_a[i] = __float_as_uint(t.z);    // t.z > kNearClip > 0: the bit pattern orders like the float
     radii[i] = radius;
@@ -371,7 +381,7 @@ static int raster_preprocess(int raw, int flags, int N, int sh_degree, int sh_co
                              const float* shs, const float* confidence, float scale_modifier,
                              const float* viewmatrix, const float* projmatrix, const float* campos,
                              float tanfovx, float tanfovy, int H, int W, int* radii, void* geom,
-                             size_t geom_bytes_, long long* num_rendered_host, void* stream_) {
+                             size_t geom_bytes_, long long* num_rendered_host, const float* filter3d, void* stream_) {
     SYN3R_REQUIRE((flags & ~SYN3R_RASTER_ANTIALIAS) == 0, "raster_preprocess: unknown flag bits 0x%x", (unsigned)flags & ~(unsigned)SYN3R_RASTER_ANTIALIAS);
     SYN3R_REQUIRE(SYN3R_DIM_OK(N) && SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W), "raster_preprocess: bad sizes N=%d H=%d W=%d", N, H, W);
     SYN3R_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "raster_preprocess: sh_degree %d not in 0..3", sh_degree);
@@ -390,12 +400,16 @@ static int raster_preprocess(int raw, int flags, int N, int sh_degree, int sh_co
     Camera cam;
     raster_fill_camera(cam, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W);
     // both instances keep the one trace name: the benchmark's per-kernel tables are keyed by it
-    if (flags & SYN3R_RASTER_ANTIALIAS)
-        SYN3R_LAUNCH_NAMED("k_preprocess", k_preprocess<true>, dim3(ceil_div(N, 256)), dim3(256), 0, stream, N, sh_degree, sh_coeffs,
-                           means3D, scales, rotations, opacities, shs, confidence, scale_modifier, cam, radii, g, raw);
-    else
-        SYN3R_LAUNCH_NAMED("k_preprocess", k_preprocess<false>, dim3(ceil_div(N, 256)), dim3(256), 0, stream, N, sh_degree, sh_coeffs,
-                           means3D, scales, rotations, opacities, shs, confidence, scale_modifier, cam, radii, g, raw);
+#define PREPROCESS(...)                                                                                                         \
+    SYN3R_LAUNCH_NAMED("k_preprocess", (k_preprocess<__VA_ARGS__>), dim3(ceil_div(N, 256)), dim3(256), 0, stream, N, sh_degree,   \
+                       sh_coeffs, means3D, scales, rotations, opacities, shs, confidence, scale_modifier, cam, radii, g, raw,  \
+                       filter3d)
+    const bool aa = (flags & SYN3R_RASTER_ANTIALIAS) != 0;
+    if (aa && filter3d) PREPROCESS(true, true);
+    else if (aa) PREPROCESS(true, false);
+    else if (filter3d) PREPROCESS(false, true);
+    else PREPROCESS(false, false);
+#undef PREPROCESS
     int rc = raster_bin_prepare(g, N, cam.grid_x, cam.grid_y, num_rendered_host != nullptr, stream);
     if (rc) return rc;
     SYN3R_LAUNCH_CHECK("raster_preprocess launch");
@@ -418,7 +432,7 @@ extern "C" int syn3r_raster_preprocess(int N, int sh_degree, int sh_coeffs, cons
                                        size_t geom_bytes_, long long* num_rendered_host, void* stream_) {
     return raster_preprocess(0, 0, N, sh_degree, sh_coeffs, means3D, scales, rotations, opacities, shs, confidence, scale_modifier,
                              viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, radii, geom, geom_bytes_, num_rendered_host,
-                             stream_);
+                             nullptr, stream_);
 }
 
 extern "C" int syn3r_raster_preprocess_raw(int N, int sh_degree, int sh_coeffs, const float* means3D,
@@ -429,7 +443,7 @@ extern "C" int syn3r_raster_preprocess_raw(int N, int sh_degree, int sh_coeffs, 
                                            size_t geom_bytes_, long long* num_rendered_host, void* stream_) {
     return raster_preprocess(1, 0, N, sh_degree, sh_coeffs, means3D, log_scales, raw_rotations, opacity_logits, shs, confidence,
                              scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, radii, geom, geom_bytes_,
-                             num_rendered_host, stream_);
+                             num_rendered_host, nullptr, stream_);
 }
 
 extern "C" int syn3r_raster_preprocess_ex(int N, int sh_degree, int sh_coeffs, const float* means3D, const float* scales,
@@ -441,7 +455,19 @@ extern "C" int syn3r_raster_preprocess_ex(int N, int sh_degree, int sh_coeffs, c
     SYN3R_REQUIRE(raw == 0 || raw == 1, "raster_preprocess_ex: raw must be 0 or 1, got %d", raw);
     return raster_preprocess(raw, flags, N, sh_degree, sh_coeffs, means3D, scales, rotations, opacities, shs, confidence,
                              scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, radii, geom, geom_bytes_,
-                             num_rendered_host, stream_);
+                             num_rendered_host, nullptr, stream_);
+}
+
+extern "C" int syn3r_raster_preprocess_f3d(int N, int sh_degree, int sh_coeffs, const float* means3D, const float* scales,
+                                           const float* rotations, const float* opacities, const float* shs,
+                                           const float* confidence, float scale_modifier, const float* viewmatrix,
+                                           const float* projmatrix, const float* campos, float tanfovx, float tanfovy, int H,
+                                           int W, int* radii, void* geom, size_t geom_bytes_, long long* num_rendered_host,
+                                           int raw, int flags, const float* filter3d, void* stream_) {
+    SYN3R_REQUIRE(raw == 0 || raw == 1, "raster_preprocess_f3d: raw must be 0 or 1, got %d", raw);
+    return raster_preprocess(raw, flags, N, sh_degree, sh_coeffs, means3D, scales, rotations, opacities, shs, confidence,
+                             scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, radii, geom, geom_bytes_,
+                             num_rendered_host, filter3d, stream_);
 }
 
 extern "C" int syn3r_raster_render(int N, int H, int W, const float* bg, const int* radii, void* geom,

@@ -318,6 +318,40 @@ def knn3_graph(points: torch.Tensor):
     return dist2, index
 
 
+def camera_table(cams) -> torch.Tensor:
+    """The [C,16] fp32 HOST table `compute_filter_3D` takes, from FSGS-style cameras (`world_view_transform` = the transposed
+    world-to-view matrix, `FoVx` / `FoVy`, `image_width` / `image_height`): per camera the 12 entries of [R | t] row by row, then
+    fx, fy, W, H (include/syn3r_hip.h).  One device -> host read per camera: build it when the camera list changes, not per step."""
+    import math
+    rows = []
+    for c in cams:
+        w2c = c.world_view_transform.detach().to("cpu", torch.float32).t()
+        W, H = float(c.image_width), float(c.image_height)
+        fx, fy = W / (2.0 * math.tan(c.FoVx * 0.5)), H / (2.0 * math.tan(c.FoVy * 0.5))
+        rows.append(torch.cat([w2c[:3, :].reshape(-1), torch.tensor([fx, fy, W, H], dtype=torch.float32)]))
+    return torch.stack(rows) if rows else torch.zeros((0, 16), dtype=torch.float32)
+
+
+def compute_filter_3D(xyz: torch.Tensor, cam_table: torch.Tensor, variance: float = L.FILTER3D_VARIANCE, near: float = L.FILTER3D_NEAR,
+                      margin: float = L.FILTER3D_MARGIN) -> torch.Tensor:
+    """Mip-Splatting's 3D smoothing filter size per Gaussian (`syn3r_filter3d_compute`, csrc/filter3d.hip): [N] fp32,
+    sqrt(variance) / (max over the cameras that see the Gaussian of fx / z); unseen Gaussians take the largest filter among the
+    seen ones, all zero when none is seen.  `xyz` [N,3] and `cam_table` [C,16] (`camera_table`) are fp32 DEVICE tensors.  Two
+    launches on the current stream: no host read, no synchronisation.  The constants are RECALLED from the released code: UNPINNED."""
+    dev = L.require_gpu(xyz, cam_table)
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or cam_table.dim() != 2 or cam_table.shape[1] != 16:
+        raise ValueError(f"compute_filter_3D: xyz must be [N,3] and cam_table [C,16], got {tuple(xyz.shape)} and {tuple(cam_table.shape)}")
+    pts = xyz.detach().to(torch.float32).contiguous()
+    tab = cam_table.detach().to(torch.float32).contiguous()
+    n = pts.shape[0]
+    lib = L.load()
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    ws = L.workspace(dev, lib.syn3r_filter3d_workspace_bytes(n), "filter3d")
+    L.check(lib.syn3r_filter3d_compute(L.ptr(pts), n, L.ptr(tab), int(tab.shape[0]), float(variance), float(near), float(margin),
+                                       L.ptr(out), L.ptr(ws), ws.numel(), L.stream_ptr(dev)), "filter3d_compute")
+    return out
+
+
 def proximity_unpool(xyz: torch.Tensor, log_scales: torch.Tensor, opacity_logits: torch.Tensor, confidence: torch.Tensor,
                      score_thresh: float, log_scale_thresh: float) -> dict:
     """FSGS' proximity-guided Gaussian unpooling (Zhu et al., ECCV 2024, section 3.2) on raw parameters: Gaussian i is a source when the

@@ -20,6 +20,7 @@ import torch
 
 from .. import _lib as L
 from ..raster import GaussianRasterizationSettings, GaussianRasterizer
+from .train_ops import camera_table, compute_filter_3D
 from .train_ops import FusedAdam, depth_correlation_loss, image_metrics, knn3_mean_dist2, l1_loss, photometric_loss
 from .train_ops import proximity_unpool as _proximity_unpool_op
 
@@ -147,6 +148,9 @@ class GaussianModel:
         self._xyz, self._scaling, self._rotation = p(xyz), p(log_scales), p(rotations)
         self._opacity, self._features = p(opacity_logits), p(shs)
         self.confidence = torch.ones(self._xyz.shape[0], device=dev)
+        # Mip-Splatting's 3D smoothing filter: None, or one filter size per Gaussian ([N] fp32, `train_ops.compute_filter_3D`; kept
+        # by `GSTrainer.ensure_filter_3D` when `OptimizationParams.filter_3d` is on).  Data, not a parameter.
+        self.filter_3D: Optional[torch.Tensor] = None
         self.max_sh_degree = sh_degree
         self.active_sh_degree = sh_degree if active_sh_degree is None else int(active_sh_degree)
         if not 0 <= self.active_sh_degree <= self.max_sh_degree:
@@ -201,11 +205,15 @@ class GaussianModel:
             self.max_radii2D[update_filter] = torch.max(self.max_radii2D[update_filter], radii[update_filter].to(self.max_radii2D.dtype))
 
     def capture(self) -> dict:
-        """Parameter tensors of a checkpoint (published 3DGS `GaussianModel.capture`, reduced to what this model holds)."""
-        return dict(active_sh_degree=self.active_sh_degree, xyz=self._xyz.detach().clone(),
-                    features=self._features.detach().clone(), scaling=self._scaling.detach().clone(),
-                    rotation=self._rotation.detach().clone(), opacity=self._opacity.detach().clone(),
-                    confidence=self.confidence.clone())
+        """Parameter tensors of a checkpoint (published 3DGS `GaussianModel.capture`, reduced to what this model holds).
+        `filter_3D` is added only when the model has one: a checkpoint written with the option off has the keys it always had."""
+        state = dict(active_sh_degree=self.active_sh_degree, xyz=self._xyz.detach().clone(),
+                     features=self._features.detach().clone(), scaling=self._scaling.detach().clone(),
+                     rotation=self._rotation.detach().clone(), opacity=self._opacity.detach().clone(),
+                     confidence=self.confidence.clone())
+        if self.filter_3D is not None:
+            state["filter_3D"] = self.filter_3D.detach().clone()
+        return state
 
     def restore(self, state: dict):
         dev = self._xyz.device
@@ -214,6 +222,8 @@ class GaussianModel:
         self._rotation, self._opacity = p(state["rotation"]), p(state["opacity"])
         self.confidence = state["confidence"].to(dev)
         self.active_sh_degree = int(state["active_sh_degree"])
+        f3 = state.get("filter_3D")
+        self.filter_3D = f3.to(dev, torch.float32).contiguous() if f3 is not None else None
 
     def set_from_pcd(self, points: np.ndarray, colors: np.ndarray, append: bool):
         """Published 3DGS `create_from_pcd`: DC colour = (rgb - 0.5) / C0, higher SH zero, isotropic scale =
@@ -246,6 +256,7 @@ class GaussianModel:
         self._scaling, self._rotation = p(cat(self._scaling, scales)), p(cat(self._rotation, rots))
         self._opacity = p(cat(self._opacity, opac))
         self.confidence = cat(self.confidence, conf)
+        self.filter_3D = None                 # another set of Gaussians (GSTrainer.ensure_filter_3D computes it again)
 
     def to(self, device):
         """diffusionGS.py:901-907 moves the Gaussians off and back on the GPU around svd_render; with 288 GB of HBM
@@ -255,6 +266,8 @@ class GaussianModel:
             t = getattr(self, name)
             t.data = t.data.to(dev)
         self.confidence = self.confidence.to(dev)
+        if self.filter_3D is not None:
+            self.filter_3D = self.filter_3D.to(dev)
         return self
 
 
@@ -310,6 +323,19 @@ class OptimizationParams:
     # opacities have grown to make up for rho < 1), so pass the option again when a checkpoint is loaded.  Density control,
     # `reset_opacity` and pruning keep reading the raw opacity, as the published code does.
     antialiasing: bool = False
+    # Mip-Splatting's 3D smoothing filter (Yu et al., CVPR 2024, section 4.1; syn3r_filter3d_compute / syn3r_raster_preprocess_f3d in
+    # include/syn3r_hip.h), the other half of the method: every Gaussian is rendered with scales sqrt(s^2 + f^2) and its opacity
+    # times prod s / sqrt(s^2 + f^2), f = sqrt(filter_3d_variance) / (its largest sampling rate fx / z over the training cameras that
+    # see it), so no Gaussian is finer than what a training view could resolve and a render from CLOSER shows no needles or holes.
+    # `GSTrainer.ensure_filter_3D` keeps `GaussianModel.filter_3D` current (every `filter_3d_interval` steps - positions move - and
+    # whenever the set of Gaussians or the camera list changes); every render of the trainer passes it, a view that is not a training
+    # camera does NOT recompute it.  Variance 0.2 and the interval 100 are RECALLED from the released code: UNPINNED; FSGS' fork is
+    # not known to have the filter - off by default.  Density control (clone / split / prune, `reset_opacity`) keeps reading the
+    # PLAIN scales and opacity, the decision taken for `antialiasing`; the released Mip-Splatting reads the filtered ones there and
+    # has its own `reset_opacity`: UNPINNED, out of scope.  Unlike `antialiasing` the filter IS stored in checkpoints.
+    filter_3d: bool = False
+    filter_3d_variance: float = 0.2
+    filter_3d_interval: int = 100
 
 
 def expon_lr(step, lr_init: float, lr_final: float, lr_delay_steps: int = 0, lr_delay_mult: float = 1.0,
@@ -364,6 +390,8 @@ class GSTrainer:
         self.densify = False              # adaptive density control inside train_step (training / finetune set it)
         self.last_unpooled = 0            # Gaussians the proximity unpooling added in the last densify_and_prune call
         self.truncated_renders = 0        # renders whose (Gaussian, tile) pair list outgrew the async capacity (see _loop)
+        self.filter_3d_computes = 0       # how often ensure_filter_3D has computed the filter
+        self._f3d_cams, self._f3d_len, self._f3d_table, self._f3d_age = None, -1, None, 0
         self.background = torch.tensor(background, dtype=torch.float32, device=gaussians._xyz.device)
         self._rng = np.random.default_rng(self.opt.seed)
         self.reset_optimizers()
@@ -561,6 +589,7 @@ class GSTrainer:
             self._swap_param(attr, torch.cat([getattr(g, attr).detach(), e]),
                              moments=lambda m, e=e: torch.cat([m, torch.zeros_like(e)]))
         g.confidence = torch.cat([g.confidence, confidence])
+        g.filter_3D = None                    # (ensure_filter_3D: a prune after a clone may give the old N back)
         g.xyz_gradient_accum = None           # statistics restart after every change of the set (published postfix)
         g.ensure_stats()
 
@@ -571,6 +600,7 @@ class GSTrainer:
         for attr in self._PARAM_ATTRS:
             self._swap_param(attr, getattr(g, attr).detach()[keep], moments=lambda m: m[keep])
         g.confidence = g.confidence[keep]
+        g.filter_3D = None
         g.xyz_gradient_accum, g.denom, g.max_radii2D = g.xyz_gradient_accum[keep], g.denom[keep], g.max_radii2D[keep]
 
     def _split_noise(self, n: int) -> torch.Tensor:
@@ -674,9 +704,39 @@ class GSTrainer:
         if it % o.opacity_reset_interval == 0:
             self.reset_opacity()
 
+    def ensure_filter_3D(self) -> Optional[torch.Tensor]:
+        """`opt.filter_3d`: keep `gaussians.filter_3D` (Mip-Splatting's 3D smoothing filter, `train_ops.compute_filter_3D`) current and
+        return it; None with the option off (nothing is touched).  Called at the top of every step and of `render_view`.  The
+        filter is computed again when it is missing or its length is not N (clone, split, unpooling, prune, `set_from_pcd`,
+        `restore`), when the camera list `scene.train_cameras[1.0]` is another object or has another length (`update_cameras`, the
+        orchestrator's restore), or after `opt.filter_3d_interval` optimisation steps (positions move).  The cameras are ALL
+        registered ones, pseudo-views included while they are registered; the view being rendered plays no part - rendering from a
+        camera that did not train the Gaussians must not adapt them to it.  The [C,16] camera table is built (one host read per
+        camera) and uploaded only when the list changes; the computation itself is two launches with no host synchronisation, so
+        the training loop stays free of round trips.  No cameras: all-zero filters."""
+        g, o = self.gaussians, self.opt
+        if not o.filter_3d:
+            return None
+        cams = self.scene.train_cameras[1.0]
+        n, dev = g._xyz.shape[0], g._xyz.device
+        stale = g.filter_3D is None or g.filter_3D.shape[0] != n or self._f3d_age >= max(int(o.filter_3d_interval), 1)
+        if self._f3d_cams is not cams or self._f3d_len != len(cams) or self._f3d_table is None or self._f3d_table.device != dev:
+            self._f3d_cams, self._f3d_len = cams, len(cams)              # (the reference keeps the list alive: no recycled id)
+            self._f3d_table = camera_table(cams).to(dev)
+            stale = True
+        if stale:
+            if len(cams) == 0:
+                g.filter_3D = torch.zeros(n, dtype=torch.float32, device=dev)
+            else:
+                g.filter_3D = compute_filter_3D(g._xyz, self._f3d_table, variance=float(o.filter_3d_variance))
+            self._f3d_age = 0
+            self.filter_3d_computes += 1
+        return g.filter_3D
+
     def render_view(self, cam: Camera, scaling_modifier: float = 1.0):
         """-> {'render' [3,H,W], 'depth' [1,H,W], 'alpha' [1,H,W], ...} (diffusionGS.py:154-172)."""
         g = self.gaussians
+        f3 = self.ensure_filter_3D()
         st = GaussianRasterizationSettings(
             image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
             tanfovy=math.tan(cam.FoVy * 0.5), bg=self.background, scale_modifier=scaling_modifier,
@@ -685,7 +745,7 @@ class GSTrainer:
         means2D = torch.zeros_like(g.get_xyz, requires_grad=True)
         color, radii, depth, alpha = GaussianRasterizer(st)(g.get_xyz, means2D, g.get_opacity, shs=g.get_features,
                                                             scales=g.get_scaling, rotations=g.get_rotation,
-                                                            confidence=g.confidence)
+                                                            confidence=g.confidence, filter_3D=f3)
         return {"render": color, "depth": depth, "alpha": alpha, "viewspace_points": means2D,
                 "visibility_filter": radii > 0, "radii": radii}
 
@@ -726,6 +786,7 @@ class GSTrainer:
         if conf is not None and getattr(conf, "requires_grad", False):
             raise ValueError("_explicit_step: a confidence tensor that requires grad needs train_step(explicit=False)")
         prior = self._depth_term_prior(cam)
+        f3 = self.ensure_filter_3D()
         with torch.no_grad():
             st = GaussianRasterizationSettings(
                 image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
@@ -734,7 +795,7 @@ class GSTrainer:
                 campos=cam.camera_center, prefiltered=False, debug=False, antialiasing=bool(self.opt.antialiasing))
             # log-scales / raw quaternions / logits in, THEIR gradients out (syn3r_raster_*_raw)
             color, radii, depth, alpha, rstate = rasterize_forward(g._xyz, g._features, g._opacity, g._scaling, g._rotation,
-                                                                   g.confidence, st, raw_params=True)
+                                                                   g.confidence, st, raw_params=True, filter_3D=f3)
             w, wmap = float(cam.cam_confidence), getattr(cam, "confidence_map", None)
             if self.opt.lambda_dssim > 0.0:
                 loss, _, d_color = photometric_loss_step(color, cam.original_image, self.opt.lambda_dssim, w, weight_map=wmap)
@@ -808,6 +869,7 @@ class GSTrainer:
         if not changed:                       # (the gradients of this step belong to the old set of Gaussians)
             self.optimizer.step()
         self.iteration += 1
+        self._f3d_age += 1                    # (ensure_filter_3D: steps since the filter was computed)
         if self.opt.sh_degree_interval > 0 and self.iteration % self.opt.sh_degree_interval == 0:
             self.gaussians.oneupSHdegree()
         return loss.detach()

@@ -114,6 +114,10 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                     help="1: anti-aliased splatting in every render of the trainer (OptimizationParams.antialiasing: the published 3DGS "
                          "switch = Mip-Splatting's 2D Mip filter; constants recalled, UNPINNED).  Not stored in checkpoints: a model "
                          "trained with it has to be rendered with it.  0 (default): the plain 0.3 px dilation")
+    ap.add_argument("--filter_3d", type=int, default=0, choices=(0, 1),
+                    help="1: Mip-Splatting's 3D smoothing filter in every render of the trainer (OptimizationParams.filter_3d: every "
+                         "Gaussian bounded from below by the sampling rate of the training cameras; constants recalled, UNPINNED).  "
+                         "The filter is stored in checkpoints.  0 (default): off")
     ap.add_argument("--num_inference_steps", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     # FSGS' parameter groups (scripts/train.py:44-46: -s, --eval, --n_views, --resolution, --use_dust3r ... of the batch scripts)
@@ -122,7 +126,7 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     args, rest = ap.parse_known_args(given)
     # argparse takes `--percent_dens` for an abbreviation of `--percent_dense`: while that flag sat in FSGS_FLAGS the token was an
     # unknown argument, and a misspelling stays one
-    declared = ["--" + f for f, _ in TRAINER_FLAGS] + ["--gs_schedule", "--pixel_confidence", "--antialiasing"]
+    declared = ["--" + f for f, _ in TRAINER_FLAGS] + ["--gs_schedule", "--pixel_confidence", "--antialiasing", "--filter_3d"]
     cut = [t for t in given if t.startswith("--") and any(d != t.split("=")[0] and d.startswith(t.split("=")[0]) for d in declared)]
     if cut:
         ap.error(f"unknown argument(s): {' '.join(cut)} (the trainer's flags are not abbreviated)")
@@ -151,7 +155,8 @@ def apply_trainer_flags(opt, args):
     """-> a copy of `opt` (gs.OptimizationParams) with the TRAINER_FLAGS that were given (not None) in their fields, and with
     `--gs_schedule published` the switches of the three published optimiser rules: decay to --position_lr_final or 1.6e-6,
     spatial_lr_scale = None (the camera extent), feature_rest_lr_div = 20, sh_degree_interval = 1000.  Pure: no GPU, `opt`
-    untouched.  `--antialiasing 1` sets `antialiasing` (0, the default, leaves the field as `opt` has it).  (--sh_degree
+    untouched.  `--antialiasing 1` sets `antialiasing`, `--filter_3d 1` sets `filter_3d` (0, the default, leaves the field as `opt` has
+    it).  (--sh_degree
     describes the model, not the optimiser: the scene factory reads it.)"""
     import dataclasses
     new = {}
@@ -165,6 +170,8 @@ def apply_trainer_flags(opt, args):
         new.update(spatial_lr_scale=None, feature_rest_lr_div=20.0, sh_degree_interval=1000)
     if getattr(args, "antialiasing", 0):
         new["antialiasing"] = True
+    if getattr(args, "filter_3d", 0):
+        new["filter_3d"] = True
     return dataclasses.replace(opt, **new)
 
 

@@ -145,16 +145,19 @@ class RasterState:
     """What `rasterize_forward` leaves for `rasterize_backward`: the (detached, contiguous fp32) inputs, the device state of the two
     forward stages and the host-side constants.  A plain object: the autograd Function stores its tensors through
     `save_for_backward`, a caller that drives the two passes itself (`GSTrainer._explicit_step`) just keeps it."""
-    __slots__ = ("settings", "host", "P", "M", "plist", "has_conf", "opacity_shape", "raw_params", "tensors")
+    __slots__ = ("settings", "host", "P", "M", "plist", "has_conf", "opacity_shape", "raw_params", "tensors", "filter_3D")
 
 
 def rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, settings: GaussianRasterizationSettings,
-                      raw_params: bool = False):
-    """Both forward stages (`syn3r_raster_preprocess_ex`, `syn3r_raster_render`); returns (color, radii, depth, alpha, state).
+                      raw_params: bool = False, filter_3D: Optional[torch.Tensor] = None):
+    """Both forward stages (`syn3r_raster_preprocess_f3d`, `syn3r_raster_render`); returns (color, radii, depth, alpha, state).
     `raw_params`: `scales`, `rotations`, `opacities` are the trainer's PARAMETERS (log-scales, unnormalised quaternions, logits);
     the published activations run inside the projection kernel and `rasterize_backward` returns the gradients of the parameters
     (`syn3r_raster_backward_ex` with raw = 1).  `settings.antialiasing` goes to both passes as SYN3R_RASTER_ANTIALIAS: the state
-    keeps the settings, so `rasterize_backward` cannot be given another mode than the forward."""
+    keeps the settings, so `rasterize_backward` cannot be given another mode than the forward.
+    `filter_3D` ([N] fp32, default None = the unfiltered render, bit for bit): Mip-Splatting's 3D smoothing filter
+    (`train_ops.compute_filter_3D`), applied to the scales and the opacity inside the projection kernel; the state remembers it for
+    `rasterize_backward`.  It is data: no gradient flows into it."""
     s = settings
     dev = L.require_gpu(means3D, shs, opacities, scales, rotations)
     lib = L.load()
@@ -166,6 +169,12 @@ def rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, se
     f32 = lambda t: t.detach().to(torch.float32).contiguous()
     m3, sh, op, sc, ro = f32(means3D), f32(shs), f32(opacities).reshape(-1), f32(scales), f32(rotations)
     cf = f32(confidence).reshape(-1) if confidence is not None else None
+    f3 = None
+    if filter_3D is not None:
+        L.require_gpu(means3D, filter_3D)
+        f3 = f32(filter_3D).reshape(-1)
+        if f3.shape != (N,):
+            raise ValueError(f"rasteriser: filter_3D must hold one value per Gaussian ({N}), got {tuple(filter_3D.shape)}")
     if m3.shape != (N, 3) or sc.shape != (N, 3) or ro.shape != (N, 4) or op.shape != (N,) or sh.shape != (N, M, 3):
         raise ValueError("rasteriser: inconsistent Gaussian tensor shapes")
     view, proj = _host16(s.viewmatrix), _host16(s.projmatrix)
@@ -186,11 +195,11 @@ def rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, se
             raise err
     use_async = use_async and key in _capacity
     P = C.c_longlong(0)
-    rc = lib.syn3r_raster_preprocess_ex(N, int(s.sh_degree), M, L.ptr(m3), L.ptr(sc), L.ptr(ro), L.ptr(op), L.ptr(sh),
-                                        L.ptr(cf), float(s.scale_modifier), view, proj, campos, float(s.tanfovx),
-                                        float(s.tanfovy), H, W, L.ptr(radii), L.ptr(geom), geom.numel(),
-                                        None if use_async else C.byref(P), int(bool(raw_params)), _flags(s), stream)
-    L.check(rc, "syn3r_raster_preprocess_ex")
+    rc = lib.syn3r_raster_preprocess_f3d(N, int(s.sh_degree), M, L.ptr(m3), L.ptr(sc), L.ptr(ro), L.ptr(op), L.ptr(sh),
+                                         L.ptr(cf), float(s.scale_modifier), view, proj, campos, float(s.tanfovx),
+                                         float(s.tanfovy), H, W, L.ptr(radii), L.ptr(geom), geom.numel(),
+                                         None if use_async else C.byref(P), int(bool(raw_params)), _flags(s), L.ptr(f3), stream)
+    L.check(rc, "syn3r_raster_preprocess_f3d")
     if use_async:
         P = _capacity[key]                          # capacity; the kernels read the live count on the device
     else:
@@ -225,12 +234,13 @@ def rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, se
     st = RasterState()
     st.settings, st.host, st.P, st.M, st.plist = s, (view, proj, campos, bg), P, M, plist.value
     st.has_conf, st.opacity_shape, st.raw_params = cf is not None, opacities.shape, bool(raw_params)
+    st.filter_3D = f3
     st.tensors = (m3, sc, ro, op, sh, cf if cf is not None else torch.empty(0, device=dev), radii, geom, binning, image)
     return color, radii, depth, alpha, st
 
 
 def rasterize_backward(st: RasterState, g_color, g_depth=None, g_alpha=None):
-    """Backward of both stages (`syn3r_raster_backward_ex`, in the forward's mode): (d_means3D, d_means2D, d_shs, d_opacities, d_scales, d_rotations,
+    """Backward of both stages (`syn3r_raster_backward_f3d`, in the forward's mode and with the forward's `filter_3D`): (d_means3D, d_means2D, d_shs, d_opacities, d_scales, d_rotations,
     d_confidence or None) - with `raw_params` the gradients of the log-scales / raw quaternions / logits."""
     m3, sc, ro, op, sh, cf, radii, geom, binning, image = st.tensors
     s = st.settings
@@ -246,13 +256,13 @@ def rasterize_backward(st: RasterState, g_color, g_depth=None, g_alpha=None):
     d_m3, d_sc, d_ro, d_op, d_sh, d_m2 = new(N, 3), new(N, 3), new(N, 4), new(N), new(N, M, 3), new(N, 3)
     d_cf = new(N) if st.has_conf else None
     ws = L.workspace(dev, lib.syn3r_raster_backward_workspace_bytes(N), "raster_bwd")
-    rc = lib.syn3r_raster_backward_ex(
+    rc = lib.syn3r_raster_backward_f3d(
         N, int(s.sh_degree), M, st.P, L.ptr(m3), L.ptr(sc), L.ptr(ro), L.ptr(op), L.ptr(sh),
         L.ptr(cf) if st.has_conf else None, float(s.scale_modifier), view, proj, campos, float(s.tanfovx),
         float(s.tanfovy), H, W, bg, L.ptr(radii), L.ptr(geom), geom.numel(), st.plist, L.ptr(image), image.numel(),
         L.ptr(gc), L.ptr(gd), L.ptr(ga), L.ptr(d_m3), L.ptr(d_sc), L.ptr(d_ro), L.ptr(d_op), L.ptr(d_sh),
-        L.ptr(d_m2), L.ptr(d_cf), L.ptr(ws), ws.numel(), int(st.raw_params), _flags(s), L.stream_ptr(dev))
-    L.check(rc, "syn3r_raster_backward_ex")
+        L.ptr(d_m2), L.ptr(d_cf), L.ptr(ws), ws.numel(), int(st.raw_params), _flags(s), L.ptr(st.filter_3D), L.stream_ptr(dev))
+    L.check(rc, "syn3r_raster_backward_f3d")
     return d_m3, d_m2, d_sh, d_op.reshape(st.opacity_shape), d_sc, d_ro, d_cf
 
 
@@ -261,8 +271,9 @@ class _Rasterize(torch.autograd.Function):
     debug_state = None
 
     @staticmethod
-    def forward(ctx, means3D, means2D, shs, opacities, scales, rotations, confidence, settings):
-        color, radii, depth, alpha, st = rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, settings)
+    def forward(ctx, means3D, means2D, shs, opacities, scales, rotations, confidence, settings, filter_3D=None):
+        color, radii, depth, alpha, st = rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, settings,
+                                                           filter_3D=filter_3D)
         ctx.save_for_backward(*st.tensors)
         st.tensors = None
         ctx.state = st
@@ -279,7 +290,7 @@ class _Rasterize(torch.autograd.Function):
             d_m3, d_m2, d_sh, d_op, d_sc, d_ro, d_cf = rasterize_backward(st, g_color, g_depth, g_alpha)
         finally:
             st.tensors = None
-        return d_m3, d_m2, d_sh, d_op, d_sc, d_ro, d_cf, None
+        return d_m3, d_m2, d_sh, d_op, d_sc, d_ro, d_cf, None, None
 
 
 class GaussianRasterizer(torch.nn.Module):
@@ -288,14 +299,16 @@ class GaussianRasterizer(torch.nn.Module):
         self.raster_settings = raster_settings
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, confidence: Optional[torch.Tensor] = None):
+                cov3D_precomp=None, confidence: Optional[torch.Tensor] = None, filter_3D: Optional[torch.Tensor] = None):
         if (shs is None) == (colors_precomp is None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if colors_precomp is not None or cov3D_precomp is not None:
             raise NotImplementedError("precomputed colours / covariances are not used by the SYN3R hot path")
         if scales is None or rotations is None:
             raise Exception("Please provide scales and rotations")
-        return _Rasterize.apply(means3D, means2D, shs, opacities, scales, rotations, confidence, self.raster_settings)
+        if filter_3D is not None:
+            filter_3D = filter_3D.detach()       # data (Mip-Splatting's 3D smoothing filter, `rasterize_forward`): no gradient
+        return _Rasterize.apply(means3D, means2D, shs, opacities, scales, rotations, confidence, self.raster_settings, filter_3D)
 
 
 def sort_pairs(keys: torch.Tensor, vals: torch.Tensor, nbits: int = 64):
