@@ -26,6 +26,14 @@ RASTER_ANTIALIAS = 1          # SYN3R_RASTER_ANTIALIAS: bit 0 of the `flags` of 
 # Mip-Splatting's 3D smoothing filter (syn3r_filter3d_compute): RECALLED from the released code, UNPINNED (include/syn3r_hip.h)
 FILTER3D_VARIANCE, FILTER3D_NEAR, FILTER3D_MARGIN = 0.2, 0.2, 0.15
 
+# The four projection and the four backward entries of the rasteriser share their leading parameters; what follows is the stream
+# alone (the plain and `_raw` entries), raw and flags before it (`_ex`), or raw, flags and the filter (`_f3d`).
+_SCENE = [c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_f, c_f, c_i, c_i]   # means3D .. confidence, scale_modifier, camera, H, W
+_RASTER_PREPROCESS = [c_i, c_i, c_i] + _SCENE + [c_p, c_p, c_sz, C.POINTER(c_ll)]
+_RASTER_BACKWARD = ([c_i, c_i, c_i, c_ll] + _SCENE + [c_p, c_p, c_p, c_sz, c_p, c_p, c_sz]   # bg .. image_bytes
+                    + [c_p] * 10 + [c_p, c_sz])                                           # 3 upstream, 7 gradients, workspace
+_STREAM, _EX, _F3D = [c_p], [c_i, c_i, c_p], [c_i, c_i, c_p, c_p]
+
 # name -> (restype, argtypes); mirrors include/syn3r_hip.h declaration by declaration
 SIGNATURES = {
     "syn3r_last_error": (C.c_char_p, []),
@@ -52,31 +60,19 @@ SIGNATURES = {
     "syn3r_raster_geom_bytes": (c_sz, [c_i]),
     "syn3r_raster_image_bytes": (c_sz, [c_i, c_i]),
     "syn3r_raster_binning_bytes": (c_sz, [c_ll]),
-    "syn3r_raster_preprocess": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_f, c_f,
-                                      c_i, c_i, c_p, c_p, c_sz, C.POINTER(c_ll), c_p]),
-    "syn3r_raster_preprocess_raw": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_f, c_f,
-                                          c_i, c_i, c_p, c_p, c_sz, C.POINTER(c_ll), c_p]),
-    "syn3r_raster_preprocess_ex": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_f, c_f,
-                                         c_i, c_i, c_p, c_p, c_sz, C.POINTER(c_ll), c_i, c_i, c_p]),
+    "syn3r_raster_preprocess": (c_i, _RASTER_PREPROCESS + _STREAM),
+    "syn3r_raster_preprocess_raw": (c_i, _RASTER_PREPROCESS + _STREAM),
+    "syn3r_raster_preprocess_ex": (c_i, _RASTER_PREPROCESS + _EX),
+    "syn3r_raster_preprocess_f3d": (c_i, _RASTER_PREPROCESS + _F3D),
     "syn3r_raster_render": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_sz, c_p, c_sz, c_p, c_sz, c_ll, c_p, c_p, c_p,
                                   C.POINTER(c_p), c_p]),
     "syn3r_raster_backward_workspace_bytes": (c_sz, [c_i]),
-    "syn3r_raster_backward": (c_i, [c_i, c_i, c_i, c_ll, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_f, c_f,
-                                    c_i, c_i, c_p, c_p, c_p, c_sz, c_p, c_p, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                    c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "syn3r_raster_backward_raw": (c_i, [c_i, c_i, c_i, c_ll, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_f, c_f,
-                                        c_i, c_i, c_p, c_p, c_p, c_sz, c_p, c_p, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                        c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "syn3r_raster_backward_ex": (c_i, [c_i, c_i, c_i, c_ll, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_f, c_f,
-                                       c_i, c_i, c_p, c_p, c_p, c_sz, c_p, c_p, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                       c_p, c_p, c_p, c_p, c_sz, c_i, c_i, c_p]),
+    "syn3r_raster_backward": (c_i, _RASTER_BACKWARD + _STREAM),
+    "syn3r_raster_backward_raw": (c_i, _RASTER_BACKWARD + _STREAM),
+    "syn3r_raster_backward_ex": (c_i, _RASTER_BACKWARD + _EX),
+    "syn3r_raster_backward_f3d": (c_i, _RASTER_BACKWARD + _F3D),
     "syn3r_filter3d_workspace_bytes": (c_sz, [c_i]),
     "syn3r_filter3d_compute": (c_i, [c_p, c_i, c_p, c_i, c_f, c_f, c_f, c_p, c_p, c_sz, c_p]),
-    "syn3r_raster_preprocess_f3d": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_f, c_f,
-                                          c_i, c_i, c_p, c_p, c_sz, C.POINTER(c_ll), c_i, c_i, c_p, c_p]),
-    "syn3r_raster_backward_f3d": (c_i, [c_i, c_i, c_i, c_ll, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_f, c_f,
-                                        c_i, c_i, c_p, c_p, c_p, c_sz, c_p, c_p, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                        c_p, c_p, c_p, c_p, c_sz, c_i, c_i, c_p, c_p]),
     "syn3r_sort_pairs_workspace_bytes": (c_sz, [c_ll]),
     "syn3r_sort_pairs": (c_i, [c_p, c_p, c_p, c_p, c_ll, c_i, c_p, c_sz, C.POINTER(c_i), c_p]),
     "syn3r_gaussian_activate": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),

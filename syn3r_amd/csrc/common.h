@@ -8,6 +8,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <atomic>
+#include <type_traits>
 #include "../../include/syn3r_hip.h"
 
 namespace syn3r {
@@ -96,6 +97,14 @@ constexpr int tune_env(const char*, int dflt) { return dflt; }
         hipError_t e__ = hipGetLastError();                             \
         if (e__ != hipSuccess) return syn3r::check_hip(e__, name);      \
     } while (0)
+
+// Runtime bools to template arguments: with_bools(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}), so a launch
+// over template booleans is written once, with `decltype(x)::value` for each parameter x of the generic lambda f.
+template <class F> inline void with_bools(F&& f) { f(); }
+template <class F, class... Rest> inline void with_bools(F&& f, bool b, Rest... rest) {
+    if (b) with_bools([&](auto... t) { f(std::true_type{}, t...); }, rest...);
+    else with_bools([&](auto... t) { f(std::false_type{}, t...); }, rest...);
+}
 
 // Workgroups are dealt to the 8 XCDs round-robin by blockIdx; this bijection hands every XCD one CONTIGUOUS
 // chunk of logical ids, so neighbouring tiles (which share operands) meet in the same 4 MB L2.

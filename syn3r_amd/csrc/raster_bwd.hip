@@ -354,23 +354,21 @@ __device__ __forceinline__ F3 sh_backward(int D, int M, F3 pos, const float* cam
 // STAGED (sh_coeffs == 16, 16-byte aligned tensors): a block's spherical-harmonics rows (256 x 192 B, contiguous in memory) come in
 // and its gradient rows go out through LDS with coalesced 16-byte accesses; a thread reading and writing its own 192-byte row in
 // global memory touches 64 different cache lines per wave instruction (32 of the kernel's 42 us at 200 000 Gaussians).
-// AA (SYN3R_RASTER_ANTIALIAS; k_preprocess<true> made the forward): the blend multiplied op * rho * confidence, rho = mip_rho(r),
-// r = d0 / d1 with d0 = a c - b^2 the determinant before the dilation and d1 = A C - b^2 (= `den`) after it (A = a + h, C = c + h,
-// h = kLowPass).  G = gr[G_OP] is dL/d(that product), so dL/dop = G cf rho, dL/dcf = G op rho, dL/drho = G op cf, and above the
-// floor dL/dr = dL/drho / (2 rho) (on the floor rho is a constant) enters the covariance gradients through
+// AA and F3D are explained where the forward's values are formed (mip_rho, f3d_scales, mode_factors in raster_common.h: this kernel
+// calls the same functions, so rho and coef are the forward's bits); here, the derivatives.  G = gr[G_OP] is dL/d(the blend opacity)
+// = dL/d(op [coef] [rho] cf).
+// AA: rho = mip_rho(r), r = d0 / d1 with d0 = a c - b^2 the determinant before the dilation and d1 = A C - b^2 (= `den`) after it
+// (A = a + h, C = c + h, h = kLowPass).  dL/dop = G cf rho, dL/dcf = G op rho, dL/drho = G op cf, and above the floor
+// dL/dr = dL/drho / (2 rho) (on the floor rho is a constant) enters the covariance gradients through
 //     dr/da = (c d1 - C d0) / d1^2 = h (c C + b^2) / d1^2      dr/dc = (a d1 - A d0) / d1^2 = h (a A + b^2) / d1^2
 //     dr/db = -2 b (d1 - d0) / d1^2 = -2 b h (a + C) / d1^2
 // (the right-hand forms are the same polynomials with A - a = C - c = h taken out: no difference of two large products in fp32).
-// rho is formed again here, by the function k_preprocess<true> called (mip_ratio); GeomState::conic_opacity[3] holds op without it.
-// F3D (syn3r_raster_backward_f3d with a filter; k_preprocess<.., true> made the forward): the covariance was built from
-// q_i = sqrt(s_i^2 + f^2) and the blend multiplied op * coef [* rho] * cf, coef = prod r_i, r_i = s_i / q_i (f3d_scales, raster_common.h:
-// formed again here, the forward's bits).  With G = gr[G_OP]: dL/dop = G coef [rho] cf, dL/dcf = G op coef [rho], the rho terms above
-// carry coef, and the scales receive
+// F3D: q_i = sqrt(s_i^2 + f^2), coef = prod r_i, r_i = s_i / q_i.  dL/dop = G coef [rho] cf, dL/dcf = G op coef [rho], the rho terms
+// above carry coef, and the scales receive
 //     dL/ds_i = dL/dq_i r_i + G op cf [rho] coef f^2 / (s_i q_i^2)         (dq_i/ds_i = r_i, dcoef/ds_i = coef f^2 / (s_i q_i^2))
 // evaluated WITHOUT the division by s_i: coef / s_i = prod_{j != i} r_j / q_i on the activated route, and on the raw route the
 // chain rule's factor s_i cancels it (dL/dlog s_i = dL/dq_i r_i s_i + G op cf [rho] coef f^2 / q_i^2).  The filter gets no gradient.
-// The scales are loaded BEFORE the opacity gradient is written on this path only (coef is needed there); F3D = false is the code
-// of the `_ex` entries.
+// The scales are loaded BEFORE the opacity gradient is written on the F3D path only (coef is needed there).
 constexpr int kShLd = 49;      // LDS row stride (floats): odd, so the 64 rows of a wavefront fall into 64 banks
 template <bool STAGED, bool AA, bool F3D>
 __global__ void __launch_bounds__(256) k_preprocess_bwd(
@@ -421,10 +419,9 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(
         break;
     }
     const float* gr = grad_rec + (size_t)i * kGradSlots;
-    F3 p = f3(means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]);
+    const float3 p = make_float3(means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]);
     const float* v = cam.view;
-    F3 t = f3(v[0] * p.x + v[4] * p.y + v[8] * p.z + v[12], v[1] * p.x + v[5] * p.y + v[9] * p.z + v[13],
-              v[2] * p.x + v[6] * p.y + v[10] * p.z + v[14]);
+    const float3 t = xf43(v, p);
 
     // ---- conic -> 2D covariance
     const float* cv = g.cov3D + 6 * (size_t)i;
@@ -436,11 +433,8 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(
     const EwaRows w = ewa_rows(cam, t.x, t.y, t.z);
     const float tx = w.tx, ty = w.ty, T00 = w.T00, T01 = w.T01, T02 = w.T02, T10 = w.T10, T11 = w.T11, T12 = w.T12;
     float W00 = v[0], W01 = v[4], W02 = v[8], W10 = v[1], W11 = v[5], W12 = v[9], W20 = v[2], W21 = v[6], W22 = v[10];
-    float a0 = c0 * T00 + c1 * T01 + c2 * T02, a1 = c1 * T00 + c3 * T01 + c4 * T02, a2 = c2 * T00 + c4 * T01 + c5 * T02;
-    float b0 = c0 * T10 + c1 * T11 + c2 * T12, b1 = c1 * T10 + c3 * T11 + c4 * T12, b2 = c2 * T10 + c4 * T11 + c5 * T12;
-    const float pA = T00 * a0 + T01 * a1 + T02 * a2, pC = T10 * b0 + T11 * b1 + T12 * b2;   // before the dilation
+    const auto [a0, a1, a2, b0, b1, b2, pA, pC, B] = ewa_cov(w, c0, c1, c2, c3, c4, c5);   // (pA, B; B, pC): before the dilation
     float A = pA + kLowPass;
-    float B = T00 * b0 + T01 * b1 + T02 * b2;
     float C = pC + kLowPass;
     float den = A * C - B * B;
     float den2inv = 1.0f / (den * den + 0.0000001f);
@@ -504,11 +498,9 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(
 
     // ---- screen-space mean (NDC) -> mean
     const float* pj = cam.proj;
-    float hx = pj[0] * p.x + pj[4] * p.y + pj[8] * p.z + pj[12];
-    float hy = pj[1] * p.x + pj[5] * p.y + pj[9] * p.z + pj[13];
-    float hw = pj[3] * p.x + pj[7] * p.y + pj[11] * p.z + pj[15];
-    float mw = 1.0f / (hw + 0.0000001f);
-    float mul1 = hx * mw * mw, mul2 = hy * mw * mw;
+    const float4 ph = xf44(pj, p);
+    float mw = 1.0f / (ph.w + 0.0000001f);
+    float mul1 = ph.x * mw * mw, mul2 = ph.y * mw * mw;
     float g2x = -0.5f * (float)cam.W * s_op * (s_cxx * gr[G_MX] + s_cxy * gr[G_MY]);
     float g2y = -0.5f * (float)cam.H * s_op * (s_cyy * gr[G_MY] + s_cxy * gr[G_MX]);
     dmean.x += (pj[0] * mw - pj[3] * mul1) * g2x + (pj[1] * mw - pj[3] * mul2) * g2y;
@@ -517,14 +509,15 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(
     dL_dmeans2D[3 * i] = g2x; dL_dmeans2D[3 * i + 1] = g2y; dL_dmeans2D[3 * i + 2] = 0.f;
 
     // ---- colour -> SH and mean
-    F3 dm_sh = sh_backward<STAGED>(D, M, p, cam.campos, STAGED ? (const float*)osh : shs + (size_t)i * M * 3, g.clamped[i],
+    F3 dm_sh = sh_backward<STAGED>(D, M, f3(p.x, p.y, p.z), cam.campos, STAGED ? (const float*)osh : shs + (size_t)i * M * 3, g.clamped[i],
                                    f3(gr[G_R], gr[G_G], gr[G_B]), osh);
     dmean = dmean + dm_sh;
     dL_dmeans3D[3 * i] = dmean.x; dL_dmeans3D[3 * i + 1] = dmean.y; dL_dmeans3D[3 * i + 2] = dmean.z;
 
     // ---- opacity / confidence (blend used opacity * confidence; cf and op_a: above the AA block)
-    float g_op = AA ? gr[G_OP] * rho : gr[G_OP];            // dL/d(op x cf)
-    if constexpr (F3D) g_op *= fs.coef;                     // (the blend multiplied op x coef x cf)
+    // rho goes on G first and coef second, as this kernel has always multiplied them: g_rho = G [rho] = dL/d(op coef cf) / (op cf)
+    const float g_rho = mode_factors(gr[G_OP], 1.0f, rho);
+    const float g_op = mode_factors(g_rho, F3D ? fs.coef : 1.0f, 1.0f);   // dL/d(op x cf)
     dL_dopacity[i] = raw ? act_sigmoid_bwd(op_a, g_op * cf) : g_op * cf;
     if (dL_dconf) dL_dconf[i] = g_op * op_a;
 
@@ -568,7 +561,7 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(
                   qx * dR20 + qy * dR21);
     if constexpr (F3D) {
         // ds_i is dL/dq_i so far; kc = G op cf [rho] = dL/dcoef.  fs.ff == 0: coef is the constant 1 (and q_i may be 0)
-        const float kc = (AA ? gr[G_OP] * rho : gr[G_OP]) * op_a * cf;
+        const float kc = g_rho * op_a * cf;
         if (raw) {
             ds0 *= fs.r0 * s0; ds1 *= fs.r1 * s1; ds2 *= fs.r2 * s2;
             if (fs.ff > 0.0f) {
@@ -611,24 +604,20 @@ extern "C" size_t syn3r_raster_backward_workspace_bytes(int N) {
     return N > 0 ? align256((size_t)N * kGradSlots * sizeof(float)) : 0;
 }
 
-static int raster_backward(int raw, int flags, int N, int sh_degree, int sh_coeffs, long long P, const float* means3D,
-                                     const float* scales, const float* rotations, const float* opacities,
-                                     const float* shs, const float* confidence, float scale_modifier,
-                                     const float* viewmatrix, const float* projmatrix, const float* campos,
-                                     float tanfovx, float tanfovy, int H, int W, const float* bg, const int* radii,
-                                     void* geom, size_t geom_bytes_, const unsigned* point_list, void* image,
-                                     size_t image_bytes_, const float* dL_dcolor, const float* dL_ddepth,
-                                     const float* dL_dalpha, float* dL_dmeans3D, float* dL_dscales,
-                                     float* dL_drotations, float* dL_dopacities, float* dL_dshs, float* dL_dmeans2D,
-                                     float* dL_dconfidence, void* workspace, size_t workspace_bytes, const float* filter3d,
-                                     void* stream_) {
-    SYN3R_REQUIRE((flags & ~SYN3R_RASTER_ANTIALIAS) == 0, "raster_backward: unknown flag bits 0x%x", (unsigned)flags & ~(unsigned)SYN3R_RASTER_ANTIALIAS);
-    SYN3R_REQUIRE(N > 0 && H > 0 && W > 0 && P >= 0, "raster_backward: bad sizes N=%d H=%d W=%d P=%lld", N, H, W, P);
-    SYN3R_REQUIRE(sh_degree >= 0 && sh_degree <= 3 && sh_coeffs >= (sh_degree + 1) * (sh_degree + 1),
-                  "raster_backward: bad SH configuration");
-    SYN3R_REQUIRE(means3D && scales && rotations && opacities && shs && viewmatrix && projmatrix && campos && bg && radii,
-                  "raster_backward: null input");
-    SYN3R_REQUIRE(dL_dcolor && dL_dmeans3D && dL_dscales && dL_drotations && dL_dopacities && dL_dshs && dL_dmeans2D,
+// the three upstream gradients (depth, alpha: may be null) and the seven gradient outputs (confidence: may be null)
+struct RasterGrads {
+    const float *dL_dcolor, *dL_ddepth, *dL_dalpha;
+    float *dL_dmeans3D, *dL_dscales, *dL_drotations, *dL_dopacities, *dL_dshs, *dL_dmeans2D, *dL_dconfidence;
+};
+
+static int raster_backward(const RasterScene& s, long long P, const float* bg, const int* radii, void* geom, size_t geom_bytes_,
+                           const unsigned* point_list, void* image, size_t image_bytes_, const RasterGrads& d, void* workspace,
+                           size_t workspace_bytes, void* stream_) {
+    if (int rc = raster_check_scene("raster_backward", s)) return rc;
+    const int N = s.N, H = s.H, W = s.W;
+    SYN3R_REQUIRE(P >= 0, "raster_backward: bad sizes P=%lld", P);
+    SYN3R_REQUIRE(bg && radii, "raster_backward: null input");
+    SYN3R_REQUIRE(d.dL_dcolor && d.dL_dmeans3D && d.dL_dscales && d.dL_drotations && d.dL_dopacities && d.dL_dshs && d.dL_dmeans2D,
                   "raster_backward: null gradient buffer");
     SYN3R_REQUIRE(P == 0 || point_list, "raster_backward: point list required");
     size_t need = syn3r_raster_backward_workspace_bytes(N);
@@ -641,40 +630,29 @@ static int raster_backward(int raw, int flags, int N, int sh_degree, int sh_coef
     GeomState g = carve_geom(geom, N);
     ImageState im = carve_image(image, H, W);
     Camera cam;
-    raster_fill_camera(cam, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W);
+    raster_fill_camera(cam, s.viewmatrix, s.projmatrix, s.campos, s.tanfovx, s.tanfovy, H, W);
     float* grad_rec = (float*)workspace;
     int rc = check_hip(hipMemsetAsync(grad_rec, 0, need, stream), "memset grads");
     if (rc) return rc;
     const unsigned tiles = (unsigned)(cam.grid_x * cam.grid_y);
     const unsigned* tile_order = raster_tiles_ordered(N, cam.grid_x, cam.grid_y) ? im.tile_order : nullptr;
-    // both instances keep the one trace name: the benchmark's per-kernel tables are keyed by it
-    if (P > 0 && dL_ddepth)
-        SYN3R_LAUNCH_NAMED("k_render_bwd", k_render_bwd<true>, dim3(tiles), dim3(kBwdThreads), 0, stream, H, W, cam.grid_x, cam.grid_y, im.ranges,
-                           point_list, g.splats, bg[0], bg[1], bg[2], im.n_contrib, im.final_T, dL_dcolor, dL_ddepth,
-                           dL_dalpha, grad_rec, tile_order);
-    else if (P > 0)        // no depth gradient (a colour-only loss): slot G_DEPTH keeps the memset's zero
-        SYN3R_LAUNCH_NAMED("k_render_bwd", k_render_bwd<false>, dim3(tiles), dim3(kBwdThreads), 0, stream, H, W, cam.grid_x, cam.grid_y, im.ranges,
-                           point_list, g.splats, bg[0], bg[1], bg[2], im.n_contrib, im.final_T, dL_dcolor, dL_ddepth,
-                           dL_dalpha, grad_rec, tile_order);
-    const bool staged = sh_coeffs == 16 && ((((uintptr_t)shs) | ((uintptr_t)dL_dshs)) & 15) == 0;
-    // the anti-aliased instances keep the trace names of the plain ones (the benchmark's per-kernel tables are keyed by them)
-#define PREPROCESS_BWD(name, ...)                                                                                            \
-    SYN3R_LAUNCH_NAMED(name, (k_preprocess_bwd<__VA_ARGS__>), dim3(ceil_div(N, 256)), dim3(256), 0, stream, N, sh_degree,     \
-                       sh_coeffs, means3D, scales, rotations, opacities, shs, confidence, scale_modifier, cam, radii, g,    \
-                       grad_rec, dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacities, dL_dshs, dL_dmeans2D,               \
-                       dL_dconfidence, raw, filter3d)
-    const bool aa = (flags & SYN3R_RASTER_ANTIALIAS) != 0;
-    if (filter3d) {
-        if (staged && aa) PREPROCESS_BWD("k_preprocess_bwd<true>", true, true, true);
-        else if (staged) PREPROCESS_BWD("k_preprocess_bwd<true>", true, false, true);
-        else if (aa) PREPROCESS_BWD("k_preprocess_bwd<false>", false, true, true);
-        else PREPROCESS_BWD("k_preprocess_bwd<false>", false, false, true);
-    }
-    else if (staged && aa) PREPROCESS_BWD("k_preprocess_bwd<true>", true, true, false);
-    else if (staged) PREPROCESS_BWD("k_preprocess_bwd<true>", true, false, false);
-    else if (aa) PREPROCESS_BWD("k_preprocess_bwd<false>", false, true, false);
-    else PREPROCESS_BWD("k_preprocess_bwd<false>", false, false, false);
-#undef PREPROCESS_BWD
+    // both instances keep the one trace name: the benchmark's per-kernel tables are keyed by it.  Without a depth gradient (a
+    // colour-only loss) slot G_DEPTH keeps the memset's zero.
+    if (P > 0)
+        with_bools([&](auto depth) {
+            SYN3R_LAUNCH_NAMED("k_render_bwd", k_render_bwd<decltype(depth)::value>, dim3(tiles), dim3(kBwdThreads), 0, stream, H, W,
+                               cam.grid_x, cam.grid_y, im.ranges, point_list, g.splats, bg[0], bg[1], bg[2], im.n_contrib, im.final_T,
+                               d.dL_dcolor, d.dL_ddepth, d.dL_dalpha, grad_rec, tile_order);
+        }, d.dL_ddepth != nullptr);
+    // the trace name says `staged` alone, as before the anti-aliased and filtered instances existed (the benchmark's tables again)
+    const bool staged = s.sh_coeffs == 16 && ((((uintptr_t)s.shs) | ((uintptr_t)d.dL_dshs)) & 15) == 0;
+    with_bools([&](auto st, auto aa, auto f3d) {
+        SYN3R_LAUNCH_NAMED(staged ? "k_preprocess_bwd<true>" : "k_preprocess_bwd<false>",
+                           (k_preprocess_bwd<decltype(st)::value, decltype(aa)::value, decltype(f3d)::value>), dim3(ceil_div(N, 256)),
+                           dim3(256), 0, stream, N, s.sh_degree, s.sh_coeffs, s.means3D, s.scales, s.rotations, s.opacities, s.shs,
+                           s.confidence, s.scale_modifier, cam, radii, g, grad_rec, d.dL_dmeans3D, d.dL_dscales, d.dL_drotations,
+                           d.dL_dopacities, d.dL_dshs, d.dL_dmeans2D, d.dL_dconfidence, s.raw, s.filter3d);
+    }, staged, (s.flags & SYN3R_RASTER_ANTIALIAS) != 0, s.filter3d != nullptr);
     SYN3R_LAUNCH_CHECK("raster_backward launch");
     return SYN3R_OK;
 }
@@ -689,10 +667,12 @@ extern "C" int syn3r_raster_backward(int N, int sh_degree, int sh_coeffs, long l
                                      const float* dL_dalpha, float* dL_dmeans3D, float* dL_dscales,
                                      float* dL_drotations, float* dL_dopacities, float* dL_dshs, float* dL_dmeans2D,
                                      float* dL_dconfidence, void* workspace, size_t workspace_bytes, void* stream_) {
-    return raster_backward(0, 0, N, sh_degree, sh_coeffs, P, means3D, scales, rotations, opacities, shs, confidence, scale_modifier,
-                           viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, bg, radii, geom, geom_bytes_, point_list, image,
-                           image_bytes_, dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacities,
-                           dL_dshs, dL_dmeans2D, dL_dconfidence, workspace, workspace_bytes, nullptr, stream_);
+    return raster_backward(raster_scene(N, sh_degree, sh_coeffs, means3D, scales, rotations, opacities, shs, confidence,
+                                        scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, 0, 0, nullptr),
+                           P, bg, radii, geom, geom_bytes_, point_list, image, image_bytes_,
+                           RasterGrads{dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacities,
+                                       dL_dshs, dL_dmeans2D, dL_dconfidence},
+                           workspace, workspace_bytes, stream_);
 }
 
 extern "C" int syn3r_raster_backward_raw(int N, int sh_degree, int sh_coeffs, long long P, const float* means3D,
@@ -705,11 +685,12 @@ extern "C" int syn3r_raster_backward_raw(int N, int sh_degree, int sh_coeffs, lo
                                          const float* dL_dalpha, float* dL_dmeans3D, float* dL_dlog_scales,
                                          float* dL_draw_rotations, float* dL_dopacity_logits, float* dL_dshs, float* dL_dmeans2D,
                                          float* dL_dconfidence, void* workspace, size_t workspace_bytes, void* stream_) {
-    return raster_backward(1, 0, N, sh_degree, sh_coeffs, P, means3D, log_scales, raw_rotations, opacity_logits, shs, confidence,
-                           scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, bg, radii, geom, geom_bytes_,
-                           point_list, image, image_bytes_, dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dlog_scales,
-                           dL_draw_rotations, dL_dopacity_logits, dL_dshs, dL_dmeans2D, dL_dconfidence, workspace, workspace_bytes,
-                           nullptr, stream_);
+    return raster_backward(raster_scene(N, sh_degree, sh_coeffs, means3D, log_scales, raw_rotations, opacity_logits, shs, confidence,
+                                        scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, 1, 0, nullptr),
+                           P, bg, radii, geom, geom_bytes_, point_list, image, image_bytes_,
+                           RasterGrads{dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dlog_scales, dL_draw_rotations,
+                                       dL_dopacity_logits, dL_dshs, dL_dmeans2D, dL_dconfidence},
+                           workspace, workspace_bytes, stream_);
 }
 
 extern "C" int syn3r_raster_backward_ex(int N, int sh_degree, int sh_coeffs, long long P, const float* means3D,
@@ -723,12 +704,12 @@ extern "C" int syn3r_raster_backward_ex(int N, int sh_degree, int sh_coeffs, lon
                                         float* dL_drotations, float* dL_dopacities, float* dL_dshs, float* dL_dmeans2D,
                                         float* dL_dconfidence, void* workspace, size_t workspace_bytes, int raw, int flags,
                                         void* stream_) {
-    SYN3R_REQUIRE(raw == 0 || raw == 1, "raster_backward_ex: raw must be 0 or 1, got %d", raw);
-    return raster_backward(raw, flags, N, sh_degree, sh_coeffs, P, means3D, scales, rotations, opacities, shs, confidence,
-                           scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, bg, radii, geom, geom_bytes_,
-                           point_list, image, image_bytes_, dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dscales,
-                           dL_drotations, dL_dopacities, dL_dshs, dL_dmeans2D, dL_dconfidence, workspace, workspace_bytes,
-                           nullptr, stream_);
+    return raster_backward(raster_scene(N, sh_degree, sh_coeffs, means3D, scales, rotations, opacities, shs, confidence,
+                                        scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, raw, flags, nullptr),
+                           P, bg, radii, geom, geom_bytes_, point_list, image, image_bytes_,
+                           RasterGrads{dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacities,
+                                       dL_dshs, dL_dmeans2D, dL_dconfidence},
+                           workspace, workspace_bytes, stream_);
 }
 
 extern "C" int syn3r_raster_backward_f3d(int N, int sh_degree, int sh_coeffs, long long P, const float* means3D,
@@ -742,12 +723,12 @@ extern "C" int syn3r_raster_backward_f3d(int N, int sh_degree, int sh_coeffs, lo
                                          float* dL_drotations, float* dL_dopacities, float* dL_dshs, float* dL_dmeans2D,
                                          float* dL_dconfidence, void* workspace, size_t workspace_bytes, int raw, int flags,
                                          const float* filter3d, void* stream_) {
-    SYN3R_REQUIRE(raw == 0 || raw == 1, "raster_backward_f3d: raw must be 0 or 1, got %d", raw);
-    return raster_backward(raw, flags, N, sh_degree, sh_coeffs, P, means3D, scales, rotations, opacities, shs, confidence,
-                           scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, bg, radii, geom, geom_bytes_,
-                           point_list, image, image_bytes_, dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dscales,
-                           dL_drotations, dL_dopacities, dL_dshs, dL_dmeans2D, dL_dconfidence, workspace, workspace_bytes,
-                           filter3d, stream_);
+    return raster_backward(raster_scene(N, sh_degree, sh_coeffs, means3D, scales, rotations, opacities, shs, confidence,
+                                        scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, raw, flags, filter3d),
+                           P, bg, radii, geom, geom_bytes_, point_list, image, image_bytes_,
+                           RasterGrads{dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacities,
+                                       dL_dshs, dL_dmeans2D, dL_dconfidence},
+                           workspace, workspace_bytes, stream_);
 }
 
 #ifdef SYN3R_RASTER_STATS

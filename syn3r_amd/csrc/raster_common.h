@@ -115,6 +115,27 @@ void raster_fill_camera(Camera& cam, const float* view, const float* proj, const
 ImageState carve_image(void* buf, int H, int W);
 BinningState carve_binning(void* buf, long long P);
 
+// What both passes are told about the scene: the common leading parameters of the four projection and the four backward entries
+// (include/syn3r_hip.h), in their order, then raw / flags / filter3d from their tails (0 / 0 / null where an entry has none).
+struct RasterScene {
+    int N, sh_degree, sh_coeffs;
+    const float *means3D, *scales, *rotations, *opacities, *shs, *confidence;   // confidence: may be null
+    float scale_modifier;
+    const float *viewmatrix, *projmatrix, *campos;
+    float tanfovx, tanfovy;
+    int H, W, raw, flags;
+    const float* filter3d;                                                      // may be null
+};
+inline RasterScene raster_scene(int N, int sh_degree, int sh_coeffs, const float* means3D, const float* scales,
+                                const float* rotations, const float* opacities, const float* shs, const float* confidence,
+                                float scale_modifier, const float* viewmatrix, const float* projmatrix, const float* campos,
+                                float tanfovx, float tanfovy, int H, int W, int raw, int flags, const float* filter3d) {
+    return RasterScene{N, sh_degree, sh_coeffs, means3D, scales, rotations, opacities, shs, confidence, scale_modifier,
+                       viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, raw, flags, filter3d};
+}
+// SYN3R_OK, or SYN3R_E_INVALID with the error text set ("<who>: ..."): the one scene check of both passes, before anything is launched
+int raster_check_scene(const char* who, const RasterScene& s);
+
 // Tile binning (raster_bin.hip).  After k_preprocess: the depth argsort and the tile counts scanned in that order (pair-sort
 // shapes), or the plain scan if the caller wants the exact pair count (header[0]) now (hierarchical binning: else nothing).
 int raster_bin_prepare(const GeomState& g, int N, int gx, int gy, bool want_count, hipStream_t stream);
@@ -213,13 +234,23 @@ __device__ __forceinline__ BlendEval blend_eval(const float4& a, const float4& b
     return e;
 }
 
-// ---- Projection pieces k_preprocess and k_preprocess_bwd share.
+// ---- The projection pieces k_preprocess and k_preprocess_bwd share.  The backward forms several of the forward's values again, some
+// of them to the bit (rho, coef, the raw route's activations of common.h): those come from ONE function with its roundings spelled out.
 constexpr float SH_C0 = 0.28209479177387814f;
 constexpr float SH_C1 = 0.4886025119029199f;
 static __constant__ float SH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
                                       -1.0925484305920792f, 0.5462742152960396f};
 static __constant__ float SH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
                                       -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
+// world -> view (three rows) and world -> clip (four) of a column-major 4 x 4 matrix (Camera::view, Camera::proj)
+__device__ __forceinline__ float3 xf43(const float* m, float3 p) {
+    return make_float3(m[0] * p.x + m[4] * p.y + m[8] * p.z + m[12], m[1] * p.x + m[5] * p.y + m[9] * p.z + m[13],
+                       m[2] * p.x + m[6] * p.y + m[10] * p.z + m[14]);
+}
+__device__ __forceinline__ float4 xf44(const float* m, float3 p) {
+    return make_float4(m[0] * p.x + m[4] * p.y + m[8] * p.z + m[12], m[1] * p.x + m[5] * p.y + m[9] * p.z + m[13],
+                       m[2] * p.x + m[6] * p.y + m[10] * p.z + m[14], m[3] * p.x + m[7] * p.y + m[11] * p.z + m[15]);
+}
 // rotation of the quaternion q = (r, x, y, z) (not renormalised here); the kernels form M = R S themselves (Sigma = M M^T)
 struct Rot3 { float R00, R01, R02, R10, R11, R12, R20, R21, R22; };
 __device__ __forceinline__ Rot3 quat_rotation(float4 q) {
@@ -245,16 +276,30 @@ __device__ __forceinline__ EwaRows ewa_rows(const Camera& cam, float t_x, float 
     o.T10 = J11 * v[1] + J12 * v[2]; o.T11 = J11 * v[5] + J12 * v[6]; o.T12 = J11 * v[9] + J12 * v[10];
     return o;
 }
-// Anti-aliased splatting (the published 3DGS `antialiasing` switch = the 2D Mip filter of Mip-Splatting, Yu et al. CVPR 2024): the
-// factor on the opacity of a splat whose 2D covariance (a, b; b, c) was dilated to (a + kLowPass, b; b, c + kLowPass),
+// cov2D = T Sigma T^T with Sigma = (c0 c1 c2; c1 c3 c4; c2 c4 c5): the products Sigma T_0^T = (a0, a1, a2), Sigma T_1^T = (b0, b1, b2)
+// (the backward's dL/dT needs them) and the covariance (xx, xy; xy, yy) BEFORE the dilation; both kernels add kLowPass to xx and yy
+// where they use it.
+struct EwaCov { float a0, a1, a2, b0, b1, b2, xx, yy, xy; };
+__device__ __forceinline__ EwaCov ewa_cov(const EwaRows& w, float c0, float c1, float c2, float c3, float c4, float c5) {
+    EwaCov o;
+    o.a0 = c0 * w.T00 + c1 * w.T01 + c2 * w.T02; o.a1 = c1 * w.T00 + c3 * w.T01 + c4 * w.T02; o.a2 = c2 * w.T00 + c4 * w.T01 + c5 * w.T02;
+    o.b0 = c0 * w.T10 + c1 * w.T11 + c2 * w.T12; o.b1 = c1 * w.T10 + c3 * w.T11 + c4 * w.T12; o.b2 = c2 * w.T10 + c4 * w.T11 + c5 * w.T12;
+    o.xx = w.T00 * o.a0 + w.T01 * o.a1 + w.T02 * o.a2;
+    o.yy = w.T10 * o.b0 + w.T11 * o.b1 + w.T12 * o.b2;
+    o.xy = w.T00 * o.b0 + w.T01 * o.b1 + w.T02 * o.b2;
+    return o;
+}
+// AA (SYN3R_RASTER_ANTIALIAS, the published 3DGS `antialiasing` switch = the 2D Mip filter of Mip-Splatting, Yu et al. CVPR 2024): the
+// dilation of the 2D covariance (a, b; b, c) to (a + kLowPass, b; b, c + kLowPass) stays and the opacity the blend multiplies carries
 //     rho = sqrt(max(r, kMipFloor)),  r = (a c - b^2) / ((a + kLowPass)(c + kLowPass) - b^2),
-// from r.  fmaxf drops a NaN operand, so rho is finite whatever the cancellation in r did.  The constants 0.3 and 0.000025 are
-// RECALLED from the published code, which is not available to check against: UNPINNED.
+// so a splat keeps its energy whatever its size on screen.  Conic, radius, tile rectangle, depth key and colour are the same values as
+// without AA (same expressions), so the tile lists are too.  In fp32 the first determinant can cancel to zero or below (needles):
+// fmaxf drops a NaN operand and puts those on the floor, so rho is finite whatever the cancellation in r did.  The constants 0.3 and
+// 0.000025 are RECALLED from the published code, which is not available to check against: UNPINNED.
 __device__ __forceinline__ float mip_rho(float r) { return sqrtf(fmaxf(r, kMipFloor)); }
-// r from the covariance before the dilation.  k_preprocess<true> and k_preprocess_bwd<.., true> must agree to the bit on which
-// side of kMipFloor a Gaussian lies (the forward's rho is a constant there, the backward's gradient through rho zero), so both call
-// this one function, and every rounding in it is spelled out: it does not depend on how the compiler contracts either kernel's
-// own determinant (`det` / `den`, the conic's, which may fuse differently in the two).
+// r from the covariance before the dilation.  The forward and the backward must agree to the bit on which side of kMipFloor a Gaussian
+// lies (the forward's rho is a constant there, the backward's gradient through rho zero), so every rounding is spelled out: r does not
+// depend on how the compiler contracts either kernel's own determinant (`det` / `den`, the conic's, which may fuse differently in the two).
 __device__ __forceinline__ float mip_ratio(float a, float b, float c) {
     const float bb = __fmul_rn(b, b);
     const float d0 = __fmaf_rn(a, c, -bb);
@@ -262,13 +307,13 @@ __device__ __forceinline__ float mip_ratio(float a, float b, float c) {
     return __fdiv_rn(d0, d1);
 }
 
-// 3D smoothing filter of Mip-Splatting (Yu et al. CVPR 2024, section 4.1; syn3r_raster_preprocess_f3d in the header): a Gaussian with
-// activated scales s_i and filter f (csrc/filter3d.hip: sqrt(variance) / its largest sampling rate over the training cameras) is
-// rendered with  q_i = sqrt(s_i^2 + f^2)  and its opacity times  coef = prod_i s_i / q_i  (= sqrt(det Sigma / det(Sigma + f^2 I)):
-// the rotation drops out).  coef is the product of the three per-axis ratios r_i, never a ratio of determinants: s = 1e-6 against
-// f = 1e-2 gives r = 1e-4 and coef = 1e-12, where s^6 would have left fp32.  k_preprocess<.., true> and k_preprocess_bwd<.., true>
-// call this one function with every rounding spelled out, so the backward's coef is the forward's bits.  f = 0 (no camera saw any
-// Gaussian) leaves q = s, r = 1, also for s = 0.
+// F3D (the `_f3d` entries with a filter: the 3D smoothing filter of Mip-Splatting, section 4.1): a Gaussian with activated scales s_i
+// and filter f (csrc/filter3d.hip: sqrt(variance) / its largest sampling rate over the training cameras) is rendered with
+// q_i = sqrt(s_i^2 + f^2)  and its opacity times  coef = prod_i s_i / q_i  (= sqrt(det Sigma / det(Sigma + f^2 I)): the rotation
+// drops out); radii, tile lists and depth keys are those of the filtered Gaussian, and with AA rho comes from the FILTERED covariance.
+// coef is the product of the three per-axis ratios r_i, never a ratio of determinants: s = 1e-6 against f = 1e-2 gives r = 1e-4 and
+// coef = 1e-12, where s^6 would have left fp32.  Every rounding is spelled out, so the backward's coef is the forward's bits.  f = 0
+// (no camera saw any Gaussian) leaves q = s, r = 1, also for s = 0.
 struct F3dScales { float q0, q1, q2, r0, r1, r2, coef, ff; };
 __device__ __forceinline__ F3dScales f3d_scales(float s0, float s1, float s2, float f) {
     F3dScales o;
@@ -280,6 +325,10 @@ __device__ __forceinline__ F3dScales f3d_scales(float s0, float s1, float s2, fl
     o.coef = __fmul_rn(__fmul_rn(o.r0, o.r1), o.r2);
     return o;
 }
+// x times what the blend opacity carries besides the opacity and the confidence: coef (1 without F3D), then rho (1 without AA), in
+// THIS order - the forward's Splat::opacity is mode_factors(op, coef, rho) * cf, and the bits depend on the order (a factor 1 is
+// exact and folds away).  GeomState::conic_opacity[3] keeps the plain op in every mode; the backward forms rho and coef again.
+__device__ __forceinline__ float mode_factors(float x, float coef, float rho) { return x * coef * rho; }
 
 #ifdef SYN3R_RASTER_STATS     // developer build, per blend kernel: [0] lane tests, [1] wavefront visits, [2] visits with an active pixel, [3] active pixels
 #define RASTER_STAT(arr, i, n) do { if (lane == 0) atomicAdd(&arr[i], (unsigned long long)(n)); } while (0)

@@ -86,15 +86,6 @@ ImageState carve_image(void* buf, int H, int W) {
 
 namespace {
 
-__device__ __forceinline__ float3 xf43(const float* m, float3 p) {
-    return make_float3(m[0] * p.x + m[4] * p.y + m[8] * p.z + m[12], m[1] * p.x + m[5] * p.y + m[9] * p.z + m[13],
-                       m[2] * p.x + m[6] * p.y + m[10] * p.z + m[14]);
-}
-__device__ __forceinline__ float4 xf44(const float* m, float3 p) {
-    return make_float4(m[0] * p.x + m[4] * p.y + m[8] * p.z + m[12], m[1] * p.x + m[5] * p.y + m[9] * p.z + m[13],
-                       m[2] * p.x + m[6] * p.y + m[10] * p.z + m[14], m[3] * p.x + m[7] * p.y + m[11] * p.z + m[15]);
-}
-
 __device__ __forceinline__ float ndc2pix(float v, int S) { return ((v + 1.0f) * (float)S - 1.0f) * 0.5f; }
 
 // view-dependent colour from spherical harmonics (degree D <= 3), +0.5, clamped at 0
@@ -135,16 +126,9 @@ __device__ float3 sh_to_rgb(int D, int M, float3 pos, const float* campos, const
     return make_float3(fmaxf(res.x, 0.0f), fmaxf(res.y, 0.0f), fmaxf(res.z, 0.0f));
 }
 
-// AA (SYN3R_RASTER_ANTIALIAS, the published `antialiasing` switch = Mip-Splatting's 2D Mip filter): the dilation by kLowPass stays
-// and the opacity the blend multiplies becomes op * rho * confidence, rho = sqrt(max(det(cov2D) / det(cov2D + kLowPass I), kMipFloor)):
-// a splat keeps its energy whatever its size on screen.  Conic, radius, tile rectangle, depth key and colour are the same values
-// as with AA = false (same expressions), so the tile lists are too.  GeomState::conic_opacity[3] keeps `op` WITHOUT rho:
-// k_preprocess_bwd<.., true> forms rho again through the same function (mip_ratio, raster_common.h: explicit roundings).
-// In fp32 the first determinant can cancel to zero or below (needles): the max puts those on the floor, never a NaN.
-// F3D (syn3r_raster_preprocess_f3d with a filter: Mip-Splatting's 3D smoothing filter, f3d_scales in raster_common.h): the covariance
-// is built from q_i = sqrt(s_i^2 + f^2) instead of the activated scales s_i and the blend opacity carries coef = prod s_i / q_i (with
-// AA: op * coef * rho * cf, rho from the FILTERED covariance).  conic_opacity[3] keeps the plain op here too; radii, tile lists and
-// depth keys are those of the filtered Gaussian.  F3D = false is the code of the `_ex` entries, instruction for instruction.
+// Projection.  AA and F3D are explained at mip_rho, f3d_scales and mode_factors in raster_common.h.  What stays for the later stages:
+// GeomState (cov3D of the possibly FILTERED Gaussian; conic_opacity[3] = the plain op, without confidence, rho or coef: the
+// backward forms those again) and the blend's Splat record, whose opacity is the whole product.  F3D = false never reads `filter3d`.
 template <bool AA, bool F3D>
 __global__ void __launch_bounds__(256) k_preprocess(int N, int D, int M, const float* __restrict__ means3D,
                                                     const float* __restrict__ scales,
@@ -196,12 +180,10 @@ __global__ void __launch_bounds__(256) k_preprocess(int N, int D, int M, const f
 
     // EWA: cov2D = (J W) Sigma (J W)^T, W = rotation part of the view matrix
     const EwaRows w = ewa_rows(cam, t.x, t.y, t.z);
-    const float T00 = w.T00, T01 = w.T01, T02 = w.T02, T10 = w.T10, T11 = w.T11, T12 = w.T12;
-    float a0 = c0 * T00 + c1 * T01 + c2 * T02, a1 = c1 * T00 + c3 * T01 + c4 * T02, a2 = c2 * T00 + c4 * T01 + c5 * T02;
-    float b0 = c0 * T10 + c1 * T11 + c2 * T12, b1 = c1 * T10 + c3 * T11 + c4 * T12, b2 = c2 * T10 + c4 * T11 + c5 * T12;
-    const float pxx = T00 * a0 + T01 * a1 + T02 * a2, pyy = T10 * b0 + T11 * b1 + T12 * b2;   // before the dilation
+    const EwaCov e = ewa_cov(w, c0, c1, c2, c3, c4, c5);
+    const float pxx = e.xx, pyy = e.yy;                                                       // before the dilation
     float cxx = pxx + kLowPass;
-    float cxy = T00 * b0 + T01 * b1 + T02 * b2;
+    float cxy = e.xy;
     float cyy = pyy + kLowPass;
 
     float det = cxx * cyy - cxy * cxy;
@@ -222,9 +204,8 @@ __global__ void __launch_bounds__(256) k_preprocess(int N, int D, int M, const f
     float3 rgb = sh_to_rgb(D, M, p, cam.campos, shs + (size_t)i * M * 3, cl);
     float op = raw ? act_sigmoid(opacities[i]) : opacities[i];
     float cf = conf ? conf[i] : 1.0f;
-    float blend_op = op * cf;
-    if constexpr (AA) blend_op = op * mip_rho(mip_ratio(pxx, cxy, pyy)) * cf;
-    if constexpr (F3D) blend_op = AA ? op * coef * mip_rho(mip_ratio(pxx, cxy, pyy)) * cf : op * coef * cf;
+    const float rho = AA ? mip_rho(mip_ratio(pxx, cxy, pyy)) : 1.0f;
+    const float blend_op = mode_factors(op, coef, rho) * cf;
     g.depths[i] = t.z;
     g.dkeys_a[i] = __float_as_uint(t.z);    // t.z > kNearClip > 0: the bit pattern orders like the float
     radii[i] = radius;
@@ -376,21 +357,28 @@ extern "C" size_t syn3r_raster_geom_bytes(int N) { return SYN3R_DIM_OK(N) ? geom
 extern "C" size_t syn3r_raster_image_bytes(int H, int W) { return (SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W)) ? image_bytes(H, W) : 0; }
 extern "C" size_t syn3r_raster_binning_bytes(long long P) { return P >= 0 ? binning_bytes(P) : 0; }
 
-static int raster_preprocess(int raw, int flags, int N, int sh_degree, int sh_coeffs, const float* means3D,
-                             const float* scales, const float* rotations, const float* opacities,
-                             const float* shs, const float* confidence, float scale_modifier,
-                             const float* viewmatrix, const float* projmatrix, const float* campos,
-                             float tanfovx, float tanfovy, int H, int W, int* radii, void* geom,
-                             size_t geom_bytes_, long long* num_rendered_host, const float* filter3d, void* stream_) {
-    SYN3R_REQUIRE((flags & ~SYN3R_RASTER_ANTIALIAS) == 0, "raster_preprocess: unknown flag bits 0x%x", (unsigned)flags & ~(unsigned)SYN3R_RASTER_ANTIALIAS);
-    SYN3R_REQUIRE(SYN3R_DIM_OK(N) && SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W), "raster_preprocess: bad sizes N=%d H=%d W=%d", N, H, W);
-    SYN3R_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "raster_preprocess: sh_degree %d not in 0..3", sh_degree);
-    SYN3R_REQUIRE(sh_coeffs >= (sh_degree + 1) * (sh_degree + 1) && sh_coeffs <= 1024,
-                  "raster_preprocess: sh_degree %d needs >= %d coefficients, got %d", sh_degree,
-                  (sh_degree + 1) * (sh_degree + 1), sh_coeffs);
-    SYN3R_REQUIRE(means3D && scales && rotations && opacities && shs && viewmatrix && projmatrix && campos && radii,
-                  "raster_preprocess: null argument");
-    SYN3R_REQUIRE(tanfovx > 0 && tanfovy > 0, "raster_preprocess: bad field of view");
+namespace syn3r {
+int raster_check_scene(const char* who, const RasterScene& s) {
+    SYN3R_REQUIRE(s.raw == 0 || s.raw == 1, "%s: raw must be 0 or 1, got %d", who, s.raw);
+    SYN3R_REQUIRE((s.flags & ~SYN3R_RASTER_ANTIALIAS) == 0, "%s: unknown flag bits 0x%x", who,
+                  (unsigned)s.flags & ~(unsigned)SYN3R_RASTER_ANTIALIAS);
+    SYN3R_REQUIRE(SYN3R_DIM_OK(s.N) && SYN3R_SIDE_OK(s.H) && SYN3R_SIDE_OK(s.W), "%s: bad sizes N=%d H=%d W=%d", who, s.N, s.H, s.W);
+    SYN3R_REQUIRE(s.sh_degree >= 0 && s.sh_degree <= 3, "%s: sh_degree %d not in 0..3", who, s.sh_degree);
+    SYN3R_REQUIRE(s.sh_coeffs >= (s.sh_degree + 1) * (s.sh_degree + 1) && s.sh_coeffs <= 1024,
+                  "%s: sh_degree %d needs >= %d coefficients (<= 1024), got %d", who, s.sh_degree, (s.sh_degree + 1) * (s.sh_degree + 1),
+                  s.sh_coeffs);
+    SYN3R_REQUIRE(s.means3D && s.scales && s.rotations && s.opacities && s.shs && s.viewmatrix && s.projmatrix && s.campos,
+                  "%s: null scene argument", who);
+    SYN3R_REQUIRE(s.tanfovx > 0 && s.tanfovy > 0, "%s: bad field of view", who);
+    return SYN3R_OK;
+}
+}  // namespace syn3r
+
+static int raster_preprocess(const RasterScene& s, int* radii, void* geom, size_t geom_bytes_, long long* num_rendered_host,
+                             void* stream_) {
+    if (int rc = raster_check_scene("raster_preprocess", s)) return rc;
+    SYN3R_REQUIRE(radii, "raster_preprocess: null argument");
+    const int N = s.N;
     if (!geom || geom_bytes_ < geom_bytes(N)) {
         set_error("raster_preprocess: geometry buffer %zu < %zu", geom_bytes_, geom_bytes(N));
         return SYN3R_E_WORKSPACE;
@@ -398,18 +386,13 @@ static int raster_preprocess(int raw, int flags, int N, int sh_degree, int sh_co
     hipStream_t stream = (hipStream_t)stream_;
     GeomState g = carve_geom(geom, N);
     Camera cam;
-    raster_fill_camera(cam, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W);
-    // both instances keep the one trace name: the benchmark's per-kernel tables are keyed by it
-#define PREPROCESS(...)                                                                                                         \
-    SYN3R_LAUNCH_NAMED("k_preprocess", (k_preprocess<__VA_ARGS__>), dim3(ceil_div(N, 256)), dim3(256), 0, stream, N, sh_degree,   \
-                       sh_coeffs, means3D, scales, rotations, opacities, shs, confidence, scale_modifier, cam, radii, g, raw,  \
-                       filter3d)
-    const bool aa = (flags & SYN3R_RASTER_ANTIALIAS) != 0;
-    if (aa && filter3d) PREPROCESS(true, true);
-    else if (aa) PREPROCESS(true, false);
-    else if (filter3d) PREPROCESS(false, true);
-    else PREPROCESS(false, false);
-#undef PREPROCESS
+    raster_fill_camera(cam, s.viewmatrix, s.projmatrix, s.campos, s.tanfovx, s.tanfovy, s.H, s.W);
+    // every instance keeps the one trace name: the benchmark's per-kernel tables are keyed by it
+    with_bools([&](auto aa, auto f3d) {
+        SYN3R_LAUNCH_NAMED("k_preprocess", (k_preprocess<decltype(aa)::value, decltype(f3d)::value>), dim3(ceil_div(N, 256)),
+                           dim3(256), 0, stream, N, s.sh_degree, s.sh_coeffs, s.means3D, s.scales, s.rotations, s.opacities, s.shs,
+                           s.confidence, s.scale_modifier, cam, radii, g, s.raw, s.filter3d);
+    }, (s.flags & SYN3R_RASTER_ANTIALIAS) != 0, s.filter3d != nullptr);
     int rc = raster_bin_prepare(g, N, cam.grid_x, cam.grid_y, num_rendered_host != nullptr, stream);
     if (rc) return rc;
     SYN3R_LAUNCH_CHECK("raster_preprocess launch");
@@ -430,9 +413,9 @@ extern "C" int syn3r_raster_preprocess(int N, int sh_degree, int sh_coeffs, cons
                                        const float* viewmatrix, const float* projmatrix, const float* campos,
                                        float tanfovx, float tanfovy, int H, int W, int* radii, void* geom,
                                        size_t geom_bytes_, long long* num_rendered_host, void* stream_) {
-    return raster_preprocess(0, 0, N, sh_degree, sh_coeffs, means3D, scales, rotations, opacities, shs, confidence, scale_modifier,
-                             viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, radii, geom, geom_bytes_, num_rendered_host,
-                             nullptr, stream_);
+    return raster_preprocess(raster_scene(N, sh_degree, sh_coeffs, means3D, scales, rotations, opacities, shs, confidence, scale_modifier,
+                                          viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, 0, 0, nullptr),
+                             radii, geom, geom_bytes_, num_rendered_host, stream_);
 }
 
 extern "C" int syn3r_raster_preprocess_raw(int N, int sh_degree, int sh_coeffs, const float* means3D,
@@ -441,9 +424,9 @@ extern "C" int syn3r_raster_preprocess_raw(int N, int sh_degree, int sh_coeffs, 
                                            const float* viewmatrix, const float* projmatrix, const float* campos,
                                            float tanfovx, float tanfovy, int H, int W, int* radii, void* geom,
                                            size_t geom_bytes_, long long* num_rendered_host, void* stream_) {
-    return raster_preprocess(1, 0, N, sh_degree, sh_coeffs, means3D, log_scales, raw_rotations, opacity_logits, shs, confidence,
-                             scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, radii, geom, geom_bytes_,
-                             num_rendered_host, nullptr, stream_);
+    return raster_preprocess(raster_scene(N, sh_degree, sh_coeffs, means3D, log_scales, raw_rotations, opacity_logits, shs, confidence, scale_modifier,
+                                          viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, 1, 0, nullptr),
+                             radii, geom, geom_bytes_, num_rendered_host, stream_);
 }
 
 extern "C" int syn3r_raster_preprocess_ex(int N, int sh_degree, int sh_coeffs, const float* means3D, const float* scales,
@@ -452,10 +435,9 @@ extern "C" int syn3r_raster_preprocess_ex(int N, int sh_degree, int sh_coeffs, c
                                           const float* projmatrix, const float* campos, float tanfovx, float tanfovy, int H,
                                           int W, int* radii, void* geom, size_t geom_bytes_, long long* num_rendered_host,
                                           int raw, int flags, void* stream_) {
-    SYN3R_REQUIRE(raw == 0 || raw == 1, "raster_preprocess_ex: raw must be 0 or 1, got %d", raw);
-    return raster_preprocess(raw, flags, N, sh_degree, sh_coeffs, means3D, scales, rotations, opacities, shs, confidence,
-                             scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, radii, geom, geom_bytes_,
-                             num_rendered_host, nullptr, stream_);
+    return raster_preprocess(raster_scene(N, sh_degree, sh_coeffs, means3D, scales, rotations, opacities, shs, confidence, scale_modifier,
+                                          viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, raw, flags, nullptr),
+                             radii, geom, geom_bytes_, num_rendered_host, stream_);
 }
 
 extern "C" int syn3r_raster_preprocess_f3d(int N, int sh_degree, int sh_coeffs, const float* means3D, const float* scales,
@@ -464,10 +446,9 @@ extern "C" int syn3r_raster_preprocess_f3d(int N, int sh_degree, int sh_coeffs, 
                                            const float* projmatrix, const float* campos, float tanfovx, float tanfovy, int H,
                                            int W, int* radii, void* geom, size_t geom_bytes_, long long* num_rendered_host,
                                            int raw, int flags, const float* filter3d, void* stream_) {
-    SYN3R_REQUIRE(raw == 0 || raw == 1, "raster_preprocess_f3d: raw must be 0 or 1, got %d", raw);
-    return raster_preprocess(raw, flags, N, sh_degree, sh_coeffs, means3D, scales, rotations, opacities, shs, confidence,
-                             scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, radii, geom, geom_bytes_,
-                             num_rendered_host, filter3d, stream_);
+    return raster_preprocess(raster_scene(N, sh_degree, sh_coeffs, means3D, scales, rotations, opacities, shs, confidence, scale_modifier,
+                                          viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, raw, flags, filter3d),
+                             radii, geom, geom_bytes_, num_rendered_host, stream_);
 }
 
 extern "C" int syn3r_raster_render(int N, int H, int W, const float* bg, const int* radii, void* geom,

@@ -55,10 +55,6 @@ def _host_floats(m: torch.Tensor):
     return vals
 
 
-def _host16(m: torch.Tensor):
-    return _host_floats(m)
-
-
 # ---- pair-count mode ------------------------------------------------------------------------------------
 # "sync"  (default): read the exact number of (Gaussian, tile) pairs back after the projection stage, as the
 #                    published implementation does, and size the binning buffer exactly.
@@ -143,9 +139,11 @@ def _flags(s: GaussianRasterizationSettings) -> int:
 
 class RasterState:
     """What `rasterize_forward` leaves for `rasterize_backward`: the (detached, contiguous fp32) inputs, the device state of the two
-    forward stages and the host-side constants.  A plain object: the autograd Function stores its tensors through
+    forward stages and the host-side constants.  `scene` is the argument prefix the projection and the backward entries share (N,
+    sh_degree, sh_coeffs, the six tensors of `tensors` by address, scale_modifier, the camera by value, H, W): built once, so the
+    backward cannot describe another scene than the forward did.  A plain object: the autograd Function stores its tensors through
     `save_for_backward`, a caller that drives the two passes itself (`GSTrainer._explicit_step`) just keeps it."""
-    __slots__ = ("settings", "host", "P", "M", "plist", "has_conf", "opacity_shape", "raw_params", "tensors", "filter_3D")
+    __slots__ = ("settings", "scene", "bg", "P", "plist", "has_conf", "opacity_shape", "raw_params", "tensors", "filter_3D")
 
 
 def rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, settings: GaussianRasterizationSettings,
@@ -177,9 +175,9 @@ def rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, se
             raise ValueError(f"rasteriser: filter_3D must hold one value per Gaussian ({N}), got {tuple(filter_3D.shape)}")
     if m3.shape != (N, 3) or sc.shape != (N, 3) or ro.shape != (N, 4) or op.shape != (N,) or sh.shape != (N, M, 3):
         raise ValueError("rasteriser: inconsistent Gaussian tensor shapes")
-    view, proj = _host16(s.viewmatrix), _host16(s.projmatrix)
-    campos = _host_floats(s.campos)
     bg = _host_floats(s.bg)
+    scene = (N, int(s.sh_degree), M, L.ptr(m3), L.ptr(sc), L.ptr(ro), L.ptr(op), L.ptr(sh), L.ptr(cf), float(s.scale_modifier),
+             _host_floats(s.viewmatrix), _host_floats(s.projmatrix), _host_floats(s.campos), float(s.tanfovx), float(s.tanfovy), H, W)
     stream = L.stream_ptr(dev)
 
     geom = torch.empty(lib.syn3r_raster_geom_bytes(N), dtype=torch.uint8, device=dev)
@@ -195,10 +193,8 @@ def rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, se
             raise err
     use_async = use_async and key in _capacity
     P = C.c_longlong(0)
-    rc = lib.syn3r_raster_preprocess_f3d(N, int(s.sh_degree), M, L.ptr(m3), L.ptr(sc), L.ptr(ro), L.ptr(op), L.ptr(sh),
-                                         L.ptr(cf), float(s.scale_modifier), view, proj, campos, float(s.tanfovx),
-                                         float(s.tanfovy), H, W, L.ptr(radii), L.ptr(geom), geom.numel(),
-                                         None if use_async else C.byref(P), int(bool(raw_params)), _flags(s), L.ptr(f3), stream)
+    rc = lib.syn3r_raster_preprocess_f3d(*scene, L.ptr(radii), L.ptr(geom), geom.numel(), None if use_async else C.byref(P),
+                                         int(bool(raw_params)), _flags(s), L.ptr(f3), stream)
     L.check(rc, "syn3r_raster_preprocess_f3d")
     if use_async:
         P = _capacity[key]                          # capacity; the kernels read the live count on the device
@@ -232,7 +228,7 @@ def rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, se
             depths=geom[256:256 + 4 * N].view(torch.float32).clone(),
         )
     st = RasterState()
-    st.settings, st.host, st.P, st.M, st.plist = s, (view, proj, campos, bg), P, M, plist.value
+    st.settings, st.scene, st.bg, st.P, st.plist = s, scene, bg, P, plist.value
     st.has_conf, st.opacity_shape, st.raw_params = cf is not None, opacities.shape, bool(raw_params)
     st.filter_3D = f3
     st.tensors = (m3, sc, ro, op, sh, cf if cf is not None else torch.empty(0, device=dev), radii, geom, binning, image)
@@ -242,13 +238,14 @@ def rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, se
 def rasterize_backward(st: RasterState, g_color, g_depth=None, g_alpha=None):
     """Backward of both stages (`syn3r_raster_backward_f3d`, in the forward's mode and with the forward's `filter_3D`): (d_means3D, d_means2D, d_shs, d_opacities, d_scales, d_rotations,
     d_confidence or None) - with `raw_params` the gradients of the log-scales / raw quaternions / logits."""
-    m3, sc, ro, op, sh, cf, radii, geom, binning, image = st.tensors
+    radii, geom, binning, image = st.tensors[6:]
+    if tuple(L.ptr(t) for t in st.tensors[:5]) != st.scene[3:8]:     # (`scene` holds the addresses the forward was given)
+        raise L.Syn3rError("rasterize_backward: the state's tensors are not the ones rasterize_forward stored")
     s = st.settings
     lib = L.load()
-    dev = m3.device
-    N, M = m3.shape[0], st.M
-    H, W = int(s.image_height), int(s.image_width)
-    view, proj, campos, bg = st.host
+    dev = radii.device
+    N, _, M = st.scene[:3]
+    H, W = st.scene[-2:]
     gc = g_color.detach().to(torch.float32).contiguous() if g_color is not None else torch.zeros((3, H, W), device=dev)
     gd = g_depth.detach().to(torch.float32).contiguous() if g_depth is not None else None
     ga = g_alpha.detach().to(torch.float32).contiguous() if g_alpha is not None else None
@@ -257,9 +254,7 @@ def rasterize_backward(st: RasterState, g_color, g_depth=None, g_alpha=None):
     d_cf = new(N) if st.has_conf else None
     ws = L.workspace(dev, lib.syn3r_raster_backward_workspace_bytes(N), "raster_bwd")
     rc = lib.syn3r_raster_backward_f3d(
-        N, int(s.sh_degree), M, st.P, L.ptr(m3), L.ptr(sc), L.ptr(ro), L.ptr(op), L.ptr(sh),
-        L.ptr(cf) if st.has_conf else None, float(s.scale_modifier), view, proj, campos, float(s.tanfovx),
-        float(s.tanfovy), H, W, bg, L.ptr(radii), L.ptr(geom), geom.numel(), st.plist, L.ptr(image), image.numel(),
+        *st.scene[:3], st.P, *st.scene[3:], st.bg, L.ptr(radii), L.ptr(geom), geom.numel(), st.plist, L.ptr(image), image.numel(),
         L.ptr(gc), L.ptr(gd), L.ptr(ga), L.ptr(d_m3), L.ptr(d_sc), L.ptr(d_ro), L.ptr(d_op), L.ptr(d_sh),
         L.ptr(d_m2), L.ptr(d_cf), L.ptr(ws), ws.numel(), int(st.raw_params), _flags(s), L.ptr(st.filter_3D), L.stream_ptr(dev))
     L.check(rc, "syn3r_raster_backward_f3d")

@@ -5,7 +5,6 @@ the filter exists for.  Every test needs the new entries.
 
 Where a test asks for the SAME BITS of gradients from two launches, the upstream gradient is non-zero on ONE 16 x 8 half-tile at a
 time, as in tests/test_raster_aa_gpu.py (its module docstring has the reason: the blend backward's float atomics)."""
-import ctypes as C
 import inspect
 import math
 import sys
@@ -19,6 +18,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent))
 
 import raster_aa_ref as A  # noqa: E402
 import raster_f3d_ref as F  # noqa: E402
+from raster_direct import half_tile_masks, render_direct  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -42,14 +42,6 @@ def hip_forward(sc, dev, deg, aa, filt, raw):
     with torch.no_grad():
         return rasterize_forward(f(sc["m"]), f(sc["sh"]), f(p["o"]), f(p["s"]), f(p["q"]), cf, settings(sc, dev, deg, aa), raw_params=raw,
                                  filter_3D=f(filt) if filt is not None else None)
-
-
-def half_tile_masks(H, W, dev):
-    for y0 in range(0, H, 8):
-        for x0 in range(0, W, 16):
-            m = torch.zeros(1, H, W, device=dev)
-            m[:, y0:y0 + 8, x0:x0 + 16] = 1.0
-            yield m
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1
@@ -212,54 +204,6 @@ def test_backward_vs_reference_autograd(shape, raw, aa, gpu, measurements):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4
-def _a256(x):
-    return (x + 255) & ~255
-
-
-def _direct(lib, sc, dev, deg, entry, raw, flags):
-    """One render through the C-ABI itself: the `_ex` entries or the `_f3d` ones with a NULL filter.  Every state buffer starts
-    from zeros, so two renders can be compared byte for byte.  -> (color, depth, alpha, radii, geometry bytes, backward)"""
-    from syn3r_amd import _lib as L
-    f = lambda t: t.float().to(dev).contiguous()
-    N, H, W = sc["N"], sc["H"], sc["W"]
-    p = F.raw_params(sc) if raw else sc
-    m3, s, q, o, sh, cf = f(sc["m"]), f(p["s"]), f(p["q"]), f(p["o"]), f(sc["sh"]), f(sc["cf"])
-    M = sh.shape[1]
-    host = lambda t: L.host_f32(t.double().reshape(-1).tolist())
-    view, proj, campos, bg = host(sc["view"].float()), host(sc["proj"].float()), host(sc["campos"].float()), host(sc["bg"].float())
-    stream = L.stream_ptr(dev)
-    u8 = lambda n: torch.zeros(max(int(n), 256), dtype=torch.uint8, device=dev)
-    geom, image = u8(lib.syn3r_raster_geom_bytes(N)), u8(lib.syn3r_raster_image_bytes(H, W))
-    radii = torch.zeros(N, dtype=torch.int32, device=dev)
-    P = C.c_longlong(0)
-    tail = (raw, flags, stream) if entry == "ex" else (raw, flags, None, stream)
-    pre = lib.syn3r_raster_preprocess_ex if entry == "ex" else lib.syn3r_raster_preprocess_f3d
-    L.check(pre(N, deg, M, L.ptr(m3), L.ptr(s), L.ptr(q), L.ptr(o), L.ptr(sh), L.ptr(cf), 1.0, view, proj, campos, float(sc["tfx"]),
-                float(sc["tfy"]), H, W, L.ptr(radii), L.ptr(geom), geom.numel(), C.byref(P), *tail), "preprocess")
-    P = int(P.value)
-    binning = u8(lib.syn3r_raster_binning_bytes(P))
-    new = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-    color, depth, alpha = new(3, H, W), new(1, H, W), new(1, H, W)
-    plist = C.c_void_p(0)
-    L.check(lib.syn3r_raster_render(N, H, W, bg, L.ptr(radii), L.ptr(geom), geom.numel(), L.ptr(binning), binning.numel(), L.ptr(image),
-                                    image.numel(), P, L.ptr(color), L.ptr(depth), L.ptr(alpha), C.byref(plist), stream), "render")
-    # header, depths, means2D, cov3D, conic_opacity, rgb, clamped, tiles_touched, point_offsets, splats (csrc/raster_fwd.hip carve_geom)
-    state = 256 + sum(_a256(N * b) for b in (4, 8, 24, 16, 12, 4, 4, 4, 48))
-    geometry = geom[:state].clone()
-    ws = u8(lib.syn3r_raster_backward_workspace_bytes(N))
-    bwd = lib.syn3r_raster_backward_ex if entry == "ex" else lib.syn3r_raster_backward_f3d
-
-    def backward(gc, gd, ga):
-        d = [new(N, 3), new(N, 3), new(N, 4), new(N), new(N, M, 3), new(N, 3), new(N)]
-        L.check(bwd(N, deg, M, P, L.ptr(m3), L.ptr(s), L.ptr(q), L.ptr(o), L.ptr(sh), L.ptr(cf), 1.0, view, proj, campos, float(sc["tfx"]),
-                    float(sc["tfy"]), H, W, bg, L.ptr(radii), L.ptr(geom), geom.numel(), plist.value, L.ptr(image), image.numel(),
-                    L.ptr(gc), L.ptr(gd), L.ptr(ga), *[L.ptr(t) for t in d], L.ptr(ws), ws.numel(), *tail), "backward")
-        return d
-
-    backward.keep = (m3, s, q, o, sh, cf, geom, image, binning, ws)
-    return color, depth, alpha, radii, geometry, backward
-
-
 @pytest.mark.parametrize("raw,flags", [(0, 0), (1, 1), (0, 1), (1, 0)], ids=["activated", "raw_antialias", "activated_antialias", "raw"])
 def test_null_filter_is_the_ex_entries_bit_for_bit(raw, flags, gpu):
     """`filter3d` = NULL through the `_f3d` entries against the `_ex` entries: colour, depth, alpha, radii and the geometry state
@@ -269,8 +213,8 @@ def test_null_filter_is_the_ex_entries_bit_for_bit(raw, flags, gpu):
     N, H, W, conf, deg, scale = shape
     sc = A.scene(N, H, W, conf, scale)
     lib = L.load()
-    old = _direct(lib, sc, gpu, deg, "ex", raw, flags)
-    new = _direct(lib, sc, gpu, deg, "f3d", raw, flags)
+    old = render_direct(lib, sc, gpu, deg, "ex", raw, flags)
+    new = render_direct(lib, sc, gpu, deg, "f3d", raw, flags)
     for a, b in zip(old[:5], new[:5]):
         assert torch.equal(a, b)
     assert int((old[3] > 0).sum()) > N // 2 and int(old[4].count_nonzero()) > 1000
@@ -294,7 +238,7 @@ def test_python_surface_without_a_filter_is_unchanged(gpu):
     shape = A.SHAPES[1]
     N, H, W, conf, deg, scale = shape
     sc = A.scene(N, H, W, conf, scale)
-    old = _direct(L.load(), sc, gpu, deg, "ex", 0, 1)
+    old = render_direct(L.load(), sc, gpu, deg, "ex", 0, 1)
     color, radii, depth, alpha, _ = hip_forward(sc, gpu, deg, True, None, False)
     for a, b in zip(old[:4], (color, depth, alpha, radii)):
         assert torch.equal(a, b)

@@ -21,6 +21,7 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 
 import raster_aa_ref as R  # noqa: E402
+from raster_direct import half_tile_masks, render_direct  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -43,15 +44,6 @@ def hip_render(sc, dev, deg, aa, requires_grad=False, debug=False):
     out = GaussianRasterizer(settings(sc, dev, deg, aa, debug))(p["m"], m2, p["o"], shs=p["sh"], scales=p["s"], rotations=p["q"],
                                                                 confidence=p["cf"])
     return out, p, m2
-
-
-def half_tile_masks(H, W, dev):
-    """[1,H,W] masks of the 16 x 8 pixel halves a wavefront of the blend kernels owns (rows 16 t + 8 w .. + 7 of tile column j)"""
-    for y0 in range(0, H, 8):
-        for x0 in range(0, W, 16):
-            m = torch.zeros(1, H, W, device=dev)
-            m[:, y0:y0 + 8, x0:x0 + 16] = 1.0
-            yield m
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1, 2
@@ -166,52 +158,6 @@ def test_raw_route_equals_activate_then_rasterise(gpu):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4
-def _direct(lib, sc, dev, deg, ex, flags=0):
-    """One render through the C-ABI itself: the four old entries (`ex` False) or the `_ex` ones.  -> (color, depth, alpha, radii,
-    backward(gc, gd, ga) -> [d_means3D, d_scales, d_rotations, d_opacities, d_shs, d_means2D, d_confidence])"""
-    from syn3r_amd import _lib as L
-    f = lambda t: t.float().to(dev).contiguous()
-    N, H, W = sc["N"], sc["H"], sc["W"]
-    m3, s, q, o, sh, cf = (f(sc[k]) for k in ("m", "s", "q", "o", "sh", "cf"))
-    M = sh.shape[1]
-    host = lambda t: L.host_f32(t.double().reshape(-1).tolist())
-    view, proj, campos, bg = host(sc["view"].float()), host(sc["proj"].float()), host(sc["campos"].float()), host(sc["bg"].float())
-    stream = L.stream_ptr(dev)
-    u8 = lambda n: torch.empty(max(int(n), 256), dtype=torch.uint8, device=dev)
-    geom, image = u8(lib.syn3r_raster_geom_bytes(N)), u8(lib.syn3r_raster_image_bytes(H, W))
-    radii = torch.empty(N, dtype=torch.int32, device=dev)
-    P = C.c_longlong(0)
-    head = (N, deg, M, L.ptr(m3), L.ptr(s), L.ptr(q), L.ptr(o), L.ptr(sh), L.ptr(cf), 1.0, view, proj, campos, float(sc["tfx"]),
-            float(sc["tfy"]), H, W, L.ptr(radii), L.ptr(geom), geom.numel(), C.byref(P))
-    if ex:
-        L.check(lib.syn3r_raster_preprocess_ex(*head, 0, flags, stream), "preprocess_ex")
-    else:
-        L.check(lib.syn3r_raster_preprocess(*head, stream), "preprocess")
-    P = int(P.value)
-    binning = u8(lib.syn3r_raster_binning_bytes(P))
-    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-    color, depth, alpha = new(3, H, W), new(1, H, W), new(1, H, W)
-    plist = C.c_void_p(0)
-    L.check(lib.syn3r_raster_render(N, H, W, bg, L.ptr(radii), L.ptr(geom), geom.numel(), L.ptr(binning), binning.numel(), L.ptr(image),
-                                    image.numel(), P, L.ptr(color), L.ptr(depth), L.ptr(alpha), C.byref(plist), stream), "render")
-    ws = u8(lib.syn3r_raster_backward_workspace_bytes(N))
-
-    def backward(gc, gd, ga):
-        d = [new(N, 3), new(N, 3), new(N, 4), new(N), new(N, M, 3), new(N, 3), new(N)]
-        args = (N, deg, M, P, L.ptr(m3), L.ptr(s), L.ptr(q), L.ptr(o), L.ptr(sh), L.ptr(cf), 1.0, view, proj, campos, float(sc["tfx"]),
-                float(sc["tfy"]), H, W, bg, L.ptr(radii), L.ptr(geom), geom.numel(), plist.value, L.ptr(image), image.numel(),
-                L.ptr(gc), L.ptr(gd), L.ptr(ga), *[L.ptr(t) for t in d], L.ptr(ws), ws.numel())
-        if ex:
-            L.check(lib.syn3r_raster_backward_ex(*args, 0, flags, stream), "backward_ex")
-        else:
-            L.check(lib.syn3r_raster_backward(*args, stream), "backward")
-        return d
-
-    keep = (m3, s, q, o, sh, cf, geom, image, binning, ws)          # the state lives as long as the closure
-    backward.keep = keep
-    return color, depth, alpha, radii, backward
-
-
 def test_filter_off_is_the_old_entries_bit_for_bit(gpu):
     """flags = 0 through the new entries, and antialiasing=False through the Python surface, against the four old entries called
     directly: colour, depth, alpha, radii and - one live half-tile at a time (module docstring) - every gradient, bit for bit."""
@@ -221,22 +167,22 @@ def test_filter_off_is_the_old_entries_bit_for_bit(gpu):
     N, H, W, conf, deg, scale = shape
     sc = R.scene(N, H, W, conf, scale)
     lib = L.load()
-    old = _direct(lib, sc, gpu, deg, ex=False)
-    new = _direct(lib, sc, gpu, deg, ex=True, flags=0)
+    old = render_direct(lib, sc, gpu, deg, "plain")
+    new = render_direct(lib, sc, gpu, deg, "ex", flags=0)
     f = lambda t: t.float().to(gpu).contiguous()
     with torch.no_grad():
         *py, st = rasterize_forward(f(sc["m"]), f(sc["sh"]), f(sc["o"]), f(sc["s"]), f(sc["q"]), f(sc["cf"]), settings(sc, gpu, deg, False))
     for a, b, c in zip(old[:4], new[:4], (py[0], py[2], py[3], py[1])):
         assert torch.equal(a, b) and torch.equal(a, c)
-    assert int((old[3] > 0).sum()) > N // 2
+    assert int((old.radii > 0).sum()) > N // 2
     gen = torch.Generator(device="cpu").manual_seed(29)
     gc, gd, ga = (torch.randn(c, H, W, generator=gen).to(gpu) for c in (3, 1, 1))
     names = ("means3D", "scales", "rotations", "opacities", "shs", "means2D", "confidence")
     seen = torch.zeros(N, dtype=torch.bool, device=gpu)
     for m in half_tile_masks(H, W, gpu):
         g = (gc * m, gd * m, ga * m)
-        a = old[4](*g)
-        b = new[4](*g)
+        a = old.backward(*g)
+        b = new.backward(*g)
         with torch.no_grad():
             d_m3, d_m2, d_sh, d_op, d_sc, d_ro, d_cf = rasterize_backward(st, *g)
         for name, x, y, z in zip(names, a, b, (d_m3, d_sc, d_ro, d_op, d_sh, d_m2, d_cf)):
@@ -353,7 +299,7 @@ def test_unknown_flag_bits_are_rejected_before_any_launch(gpu):
     lib = L.load()
     for bad in (2, 3, 1 << 30, -2):
         with pytest.raises(L.Syn3rError, match="flag"):
-            _direct(lib, sc, gpu, deg, ex=True, flags=bad)
+            render_direct(lib, sc, gpu, deg, "ex", flags=bad)
     # nothing ran: the output buffers of a refused call keep what they held
     f = lambda t: t.float().to(gpu).contiguous()
     m3, s, q, o, sh, cf = (f(sc[k]) for k in ("m", "s", "q", "o", "sh", "cf"))
@@ -367,13 +313,13 @@ def test_unknown_flag_bits_are_rejected_before_any_launch(gpu):
     torch.cuda.synchronize()
     assert rc == -1 and b"flag" in lib.syn3r_last_error()
     assert P.value == -5 and (radii == -7).all() and int(geom.sum()) == 0
-    good = _direct(lib, sc, gpu, deg, ex=True, flags=L.RASTER_ANTIALIAS)
-    m3_, s_, q_, o_, sh_, cf_, geom_, image_, binning_, ws_ = good[4].keep
+    good = render_direct(lib, sc, gpu, deg, "ex", flags=L.RASTER_ANTIALIAS)
+    m3_, s_, q_, o_, sh_, cf_, geom_, image_, binning_, ws_ = good.backward.keep
     gc, gd, ga = torch.ones(3, H, W, device=gpu), torch.ones(1, H, W, device=gpu), torch.ones(1, H, W, device=gpu)
     d = [torch.full(shp, -7.0, device=gpu) for shp in ((N, 3), (N, 3), (N, 4), (N,), (N, sh.shape[1], 3), (N, 3), (N,))]
     rc = lib.syn3r_raster_backward_ex(N, deg, sh.shape[1], 1, L.ptr(m3_), L.ptr(s_), L.ptr(q_), L.ptr(o_), L.ptr(sh_), L.ptr(cf_), 1.0,
                                       host(sc["view"]), host(sc["proj"]), host(sc["campos"]), float(sc["tfx"]), float(sc["tfy"]), H, W,
-                                      host(sc["bg"]), L.ptr(good[3]), L.ptr(geom_), geom_.numel(), L.ptr(binning_), L.ptr(image_),
+                                      host(sc["bg"]), L.ptr(good.radii), L.ptr(geom_), geom_.numel(), L.ptr(binning_), L.ptr(image_),
                                       image_.numel(), L.ptr(gc), L.ptr(gd), L.ptr(ga), *[L.ptr(t) for t in d], L.ptr(ws_), ws_.numel(),
                                       0, 4, L.stream_ptr(gpu))
     torch.cuda.synchronize()
