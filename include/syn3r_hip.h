@@ -402,6 +402,29 @@ int syn3r_raster_backward_f3d(int N, int sh_degree, int sh_coeffs, long long P, 
                               float* dL_drotations, float* dL_dopacities, float* dL_dshs, float* dL_dmeans2D,
                               float* dL_dconfidence, void* workspace, size_t workspace_bytes, int raw, int flags,
                               const float* filter3d, void* stream);
+/*
+ * syn3r_raster_backward_f3d with the ABSOLUTE screen-space gradient of AbsGS (Ye et al., "AbsGS: Recovering Fine Details for 3D
+ * Gaussian Splatting", 2024, section 3.2; `dL_dmean2D_abs` of its released rasteriser and gsplat's `absgrad` - both RECALLED, not
+ * available to check against: UNPINNED).  Arguments as there, then `dL_dmeans2D_abs` ([N,2] device floats, 8-byte aligned, or NULL)
+ * before the stream; NULL is syn3r_raster_backward_f3d exactly (the same kernels, the same number of launches).  Per pixel p that
+ * blends Gaussian i the gradient of the loss with respect to the projected mean is g_p = (gx_p, gy_p); dL_dmeans2D[i, :2] is
+ * sum_p g_p, in which the pulls of the pixels on either side of a large Gaussian cancel, and
+ *     dL_dmeans2D_abs[i] = (sum_p |gx_p|, sum_p |gy_p|)
+ * in the same units (NDC: the factors W / 2 and H / 2 applied).  It is summed inside the blend backward (two spare slots of the
+ * gradient record: syn3r_raster_backward_workspace_bytes does not change), on both parameter routes (`raw`) and in every mode
+ * (`flags`, `filter3d`: the blend opacity carries rho and coef); culled Gaussians (radii <= 0) receive zeros.  The other outputs
+ * are those of syn3r_raster_backward_f3d up to the order of the float atomics.  One small launch more than without it.
+ */
+int syn3r_raster_backward_abs(int N, int sh_degree, int sh_coeffs, long long P, const float* means3D,
+                              const float* scales, const float* rotations, const float* opacities, const float* shs,
+                              const float* confidence, float scale_modifier, const float* viewmatrix,
+                              const float* projmatrix, const float* campos, float tanfovx, float tanfovy, int H, int W,
+                              const float* bg, const int* radii, void* geom, size_t geom_bytes,
+                              const unsigned* point_list, void* image, size_t image_bytes, const float* dL_dcolor,
+                              const float* dL_ddepth, const float* dL_dalpha, float* dL_dmeans3D, float* dL_dscales,
+                              float* dL_drotations, float* dL_dopacities, float* dL_dshs, float* dL_dmeans2D,
+                              float* dL_dconfidence, void* workspace, size_t workspace_bytes, int raw, int flags,
+                              const float* filter3d, float* dL_dmeans2D_abs, void* stream);
 
 /*
  * Stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits) — the
@@ -805,6 +828,12 @@ int syn3r_gaussian_activate_backward(int N, const float* rotations, const float*
  * denom[i] += 1, max_radii[i] = max(max_radii[i], radii[i]).  viewspace_grad [N,3] fp32; radii [N] i32; the rest [N] fp32. */
 int syn3r_densification_stats(int N, const int* radii, const float* viewspace_grad, float* grad_accum, float* denom,
                               float* max_radii, void* stream);
+/* The same (the published 3DGS add_densification_stats) and, for the same Gaussians and in the same launch, the statistic AbsGS
+ * (section 3.2; UNPINNED, see syn3r_raster_backward_abs) takes the split decision on:
+ * grad_accum_abs[i] += |abs_grad[i]|_2 (sqrt(ax*ax + ay*ay), fp32).  abs_grad [N,2] fp32 = syn3r_raster_backward_abs' dL_dmeans2D_abs;
+ * grad_accum_abs [N] fp32. */
+int syn3r_densification_stats_abs(int N, const int* radii, const float* viewspace_grad, const float* abs_grad, float* grad_accum,
+                                  float* grad_accum_abs, float* denom, float* max_radii, void* stream);
 
 /* out[i] = mean of the three smallest squared Euclidean distances from point i to the OTHER points of the cloud
  * (points [n,3] fp32, n >= 4): the quantity FSGS' GaussianModel.create_from_pcd takes from `distCUDA2` of the

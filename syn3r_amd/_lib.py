@@ -32,7 +32,7 @@ _SCENE = [c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_f, c_f, c_i, c_i] 
 _RASTER_PREPROCESS = [c_i, c_i, c_i] + _SCENE + [c_p, c_p, c_sz, C.POINTER(c_ll)]
 _RASTER_BACKWARD = ([c_i, c_i, c_i, c_ll] + _SCENE + [c_p, c_p, c_p, c_sz, c_p, c_p, c_sz]   # bg .. image_bytes
                     + [c_p] * 10 + [c_p, c_sz])                                           # 3 upstream, 7 gradients, workspace
-_STREAM, _EX, _F3D = [c_p], [c_i, c_i, c_p], [c_i, c_i, c_p, c_p]
+_STREAM, _EX, _F3D, _ABS = [c_p], [c_i, c_i, c_p], [c_i, c_i, c_p, c_p], [c_i, c_i, c_p, c_p, c_p]   # (_abs: + dL_dmeans2D_abs)
 
 # name -> (restype, argtypes); mirrors include/syn3r_hip.h declaration by declaration
 SIGNATURES = {
@@ -71,6 +71,7 @@ SIGNATURES = {
     "syn3r_raster_backward_raw": (c_i, _RASTER_BACKWARD + _STREAM),
     "syn3r_raster_backward_ex": (c_i, _RASTER_BACKWARD + _EX),
     "syn3r_raster_backward_f3d": (c_i, _RASTER_BACKWARD + _F3D),
+    "syn3r_raster_backward_abs": (c_i, _RASTER_BACKWARD + _ABS),
     "syn3r_filter3d_workspace_bytes": (c_sz, [c_i]),
     "syn3r_filter3d_compute": (c_i, [c_p, c_i, c_p, c_i, c_f, c_f, c_f, c_p, c_p, c_sz, c_p]),
     "syn3r_sort_pairs_workspace_bytes": (c_sz, [c_ll]),
@@ -78,6 +79,7 @@ SIGNATURES = {
     "syn3r_gaussian_activate": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "syn3r_gaussian_activate_backward": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "syn3r_densification_stats": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "syn3r_densification_stats_abs": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "syn3r_gemm_f16": (c_i, [c_p, c_ll, c_p, c_p, c_ll, c_p, c_p, c_ll, c_i, c_i, c_p, c_ll, c_p, c_ll, c_f, c_f, c_f,
                              c_i, c_i, c_i, c_p, c_sz, C.POINTER(c_i), c_p]),
     "syn3r_gemm_set_tile": (c_i, [c_i]),

@@ -30,6 +30,12 @@ constexpr int kGradSlots = 16;
 // slots 4-8 hold RAW moments of h = G * dL/dalpha over the splat's pixels (Sx = sum h dx, Sy, Sxx, Sxy, Syy with (dx, dy) = mean -
 // pixel); k_preprocess_bwd turns them into the gradients of the pixel mean and the conic.  Slot 9 (sum h) is dL/d(opacity x confidence).
 enum { G_R = 0, G_G, G_B, G_DEPTH, G_MX, G_MY, G_CXX, G_CXY, G_CYY, G_OP, G_USED = 10 };
+// slots 10 and 11, written by the ABS instances of k_render_bwd alone (else they keep the memset's zero): the ABSOLUTE first moments
+//     sum over the splat's pixels of |h| |cxx dx + cxy dy|   and of   |h| |cyy dy + cxy dx|
+// (AbsGS, Ye et al. 2024, section 3.2: per pixel the mean's gradient is -opacity h conic (dx, dy); its components are summed by
+// magnitude, so the pulls of the pixels on either side of a large Gaussian do not cancel).  The conic is inside the absolute value, so
+// unlike G_MX / G_MY these are formed WITH it in the visit; the opacity and the pixel -> NDC factors still wait for k_abs_means2D.
+enum { G_AMX = 10, G_AMY = 11, G_USED_ABS = 12 };
 
 // Sum the per-lane gradient terms over the 64 lanes: NV = 10 values, or 9 without a depth gradient (value 9 is the depth term).
 // Returns, on the lanes reduce_value names, a (partial) total of one value; every other lane holds a by-product.
@@ -124,7 +130,14 @@ __device__ unsigned long long g_bwd_stats[4];
 // The geometric terms are all h = G dL/da_i times powers of (dx, dy) times values uniform for the splat: the visit sums the raw
 // moments  h, h dx, h dy, h dx dx, h dx dy, h dy dy  and k_preprocess_bwd applies opacity, conic, W/2, H/2 once per Gaussian.
 // HAS_DEPTH_GRAD = false (no dL_ddepth: a colour-only loss): the depth term of d_i and the depth slot are compiled out.
-template <bool HAS_DEPTH_GRAD>
+// ABS (a caller that asked for dL_dmeans2D_abs): two more per-lane values, ax = |h0 ux0| + |h1 ux1| with ux = cxx dx + cxy dy and ay
+// likewise with uy = cyy dy + cxy dx (|h| |u| = |h u| exactly in floating point), summed over the wavefront on their own - the ten
+// values above go through reduce_lanes as in the plain instances: one half swap of the PAIR (lanes 0-31 then own ax, lanes 32-63 ay)
+// and four full-mask row rotates, after which every lane of a row holds the row's total; lane 11 of each row, the one lane with a
+// reduce_lanes by-product nobody reads, hands it to the SAME LDS atomic instruction (rows 0-1: G_AMX, rows 2-3: G_AMY; the atomic
+// adds the two rows' partials as it does for reduce_lanes' unpaired values).  A pixel that does not take the splat has h = 0 and
+// adds an exact zero; a clamped alpha keeps its gradient as the signed moments do.  ABS = false compiles to the code without it.
+template <bool HAS_DEPTH_GRAD, bool ABS>
 __global__ void __launch_bounds__(kBwdThreads) k_render_bwd(
     int H, int W, int gx, int gy, const uint2* __restrict__ ranges, const unsigned* __restrict__ point_list,
     const Splat* __restrict__ splats, float bg0, float bg1, float bg2, const unsigned* __restrict__ n_contrib,
@@ -184,6 +197,8 @@ __global__ void __launch_bounds__(kBwdThreads) k_render_bwd(
 #pragma unroll
         for (int k = 0; k < 10; ++k) rslot = rval == k ? order[k] : rslot;
     }
+    const bool abs_lane = ABS && (lane & 15) == 11;
+    if constexpr (ABS) rslot = abs_lane ? (lane < 32 ? G_AMX : G_AMY) : rslot;
     int todo = total;
     // The records of round rd + 1 are requested (list entry, then the 48-byte record: two dependent global loads)
     // BEFORE round rd is processed and land in registers meanwhile: the gather latency is off the critical path.
@@ -269,8 +284,26 @@ __global__ void __launch_bounds__(kBwdThreads) k_render_bwd(
             v[8] = Sh;
             v[9] = 0.0f;
             if constexpr (HAS_DEPTH_GRAD) { const f2 wd = wgt * gD; v[9] = wd.x + wd.y; }
-            const float s = reduce_lanes<NV>(v);
-            if (rslot >= 0) atomicAdd(&sacc[j * kGradSlots + rslot], s);   // LDS, 10 banks
+            float s = reduce_lanes<NV>(v);
+            if constexpr (ABS) {
+                const f2 ux = a.w * dy + splat2(a.z * dx), uy = b.x * dy + splat2(a.w * dx);
+                const f2 hux = h * ux, huy = h * uy;
+                const float ax = fabsf(hux.x) + fabsf(hux.y), ay = fabsf(huy.x) + fabsf(huy.y);
+                auto r = __builtin_amdgcn_permlane32_swap(__float_as_int(ax), __float_as_int(ay), false, false);
+                float t = __int_as_float(r[0]) + __int_as_float(r[1]);
+                // one block with its wait states, as in reduce_lanes: two between a VALU write of t and the DPP read of it
+                asm("s_nop 1\n\t"
+                    "v_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+                    "s_nop 1\n\t"
+                    "v_add_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
+                    "s_nop 1\n\t"
+                    "v_add_f32_dpp %0, %0, %0 row_ror:2 row_mask:0xf bank_mask:0xf\n\t"
+                    "s_nop 1\n\t"
+                    "v_add_f32_dpp %0, %0, %0 row_ror:1 row_mask:0xf bank_mask:0xf"
+                    : "+v"(t));
+                s = abs_lane ? t : s;
+            }
+            if (rslot >= 0) atomicAdd(&sacc[j * kGradSlots + rslot], s);   // LDS, 10 banks (12 with ABS)
           }
         }
         // one global atomic per (tile, splat) instead of one per (wavefront, splat): 16 lanes per record, so a
@@ -280,7 +313,7 @@ __global__ void __launch_bounds__(kBwdThreads) k_render_bwd(
             const int slot = threadIdx.x & 15;
             for (int q = threadIdx.x >> 4; q < cnt; q += kBwdThreads / 16) {
                 float val = sacc[q * kGradSlots + slot];
-                if (slot < G_USED && val != 0.0f) unsafeAtomicAdd(grad_rec + (size_t)sid[q] * kGradSlots + slot, val);
+                if (slot < (ABS ? G_USED_ABS : G_USED) && val != 0.0f) unsafeAtomicAdd(grad_rec + (size_t)sid[q] * kGradSlots + slot, val);
             }
         }
     }
@@ -598,6 +631,24 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(
     }
 }
 
+// dL_dmeans2D_abs of the `_abs` entry: the element-wise absolute counterpart of (g2x, g2y) above, from the two slots the ABS instances
+// of k_render_bwd summed.  s_op is the splat record's blend opacity, the value the blend multiplied (opacity x confidence, x rho and
+// x coef in the anti-aliased and filtered modes: non-negative); culled Gaussians write zeros.  A kernel of its own, launched only for
+// a caller that asked: k_preprocess_bwd is the same code with and without it.
+__global__ void __launch_bounds__(256) k_abs_means2D(int N, float half_w, float half_h, const int* __restrict__ radii,
+                                                     const Splat* __restrict__ splats, const float* __restrict__ grad_rec,
+                                                     float* __restrict__ abs2D) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    float2 o = make_float2(0.0f, 0.0f);
+    if (radii[i] > 0) {
+        const float s_op = splats[i].opacity;
+        const float2 m = *(const float2*)(grad_rec + (size_t)i * kGradSlots + G_AMX);
+        o = make_float2(half_w * s_op * m.x, half_h * s_op * m.y);
+    }
+    *(float2*)(abs2D + 2 * (size_t)i) = o;
+}
+
 }  // namespace
 
 extern "C" size_t syn3r_raster_backward_workspace_bytes(int N) {
@@ -608,6 +659,7 @@ extern "C" size_t syn3r_raster_backward_workspace_bytes(int N) {
 struct RasterGrads {
     const float *dL_dcolor, *dL_ddepth, *dL_dalpha;
     float *dL_dmeans3D, *dL_dscales, *dL_drotations, *dL_dopacities, *dL_dshs, *dL_dmeans2D, *dL_dconfidence;
+    float* dL_dmeans2D_abs = nullptr;   // [N,2], syn3r_raster_backward_abs alone; null: the backward of the other entries
 };
 
 static int raster_backward(const RasterScene& s, long long P, const float* bg, const int* radii, void* geom, size_t geom_bytes_,
@@ -636,14 +688,14 @@ static int raster_backward(const RasterScene& s, long long P, const float* bg, c
     if (rc) return rc;
     const unsigned tiles = (unsigned)(cam.grid_x * cam.grid_y);
     const unsigned* tile_order = raster_tiles_ordered(N, cam.grid_x, cam.grid_y) ? im.tile_order : nullptr;
-    // both instances keep the one trace name: the benchmark's per-kernel tables are keyed by it.  Without a depth gradient (a
-    // colour-only loss) slot G_DEPTH keeps the memset's zero.
+    // all four instances keep the one trace name: the benchmark's per-kernel tables are keyed by it.  Without a depth gradient (a
+    // colour-only loss) slot G_DEPTH keeps the memset's zero, without dL_dmeans2D_abs slots G_AMX and G_AMY do.
     if (P > 0)
-        with_bools([&](auto depth) {
-            SYN3R_LAUNCH_NAMED("k_render_bwd", k_render_bwd<decltype(depth)::value>, dim3(tiles), dim3(kBwdThreads), 0, stream, H, W,
-                               cam.grid_x, cam.grid_y, im.ranges, point_list, g.splats, bg[0], bg[1], bg[2], im.n_contrib, im.final_T,
-                               d.dL_dcolor, d.dL_ddepth, d.dL_dalpha, grad_rec, tile_order);
-        }, d.dL_ddepth != nullptr);
+        with_bools([&](auto depth, auto abs) {
+            SYN3R_LAUNCH_NAMED("k_render_bwd", (k_render_bwd<decltype(depth)::value, decltype(abs)::value>), dim3(tiles),
+                               dim3(kBwdThreads), 0, stream, H, W, cam.grid_x, cam.grid_y, im.ranges, point_list, g.splats, bg[0], bg[1],
+                               bg[2], im.n_contrib, im.final_T, d.dL_dcolor, d.dL_ddepth, d.dL_dalpha, grad_rec, tile_order);
+        }, d.dL_ddepth != nullptr, d.dL_dmeans2D_abs != nullptr);
     // the trace name says `staged` alone, as before the anti-aliased and filtered instances existed (the benchmark's tables again)
     const bool staged = s.sh_coeffs == 16 && ((((uintptr_t)s.shs) | ((uintptr_t)d.dL_dshs)) & 15) == 0;
     with_bools([&](auto st, auto aa, auto f3d) {
@@ -653,6 +705,9 @@ static int raster_backward(const RasterScene& s, long long P, const float* bg, c
                            s.confidence, s.scale_modifier, cam, radii, g, grad_rec, d.dL_dmeans3D, d.dL_dscales, d.dL_drotations,
                            d.dL_dopacities, d.dL_dshs, d.dL_dmeans2D, d.dL_dconfidence, s.raw, s.filter3d);
     }, staged, (s.flags & SYN3R_RASTER_ANTIALIAS) != 0, s.filter3d != nullptr);
+    if (d.dL_dmeans2D_abs)
+        SYN3R_LAUNCH(k_abs_means2D, dim3(ceil_div(N, 256)), dim3(256), 0, stream, N, 0.5f * (float)W, 0.5f * (float)H, radii, g.splats,
+                     grad_rec, d.dL_dmeans2D_abs);
     SYN3R_LAUNCH_CHECK("raster_backward launch");
     return SYN3R_OK;
 }
@@ -728,6 +783,26 @@ extern "C" int syn3r_raster_backward_f3d(int N, int sh_degree, int sh_coeffs, lo
                            P, bg, radii, geom, geom_bytes_, point_list, image, image_bytes_,
                            RasterGrads{dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacities,
                                        dL_dshs, dL_dmeans2D, dL_dconfidence},
+                           workspace, workspace_bytes, stream_);
+}
+
+extern "C" int syn3r_raster_backward_abs(int N, int sh_degree, int sh_coeffs, long long P, const float* means3D,
+                                         const float* scales, const float* rotations, const float* opacities,
+                                         const float* shs, const float* confidence, float scale_modifier,
+                                         const float* viewmatrix, const float* projmatrix, const float* campos,
+                                         float tanfovx, float tanfovy, int H, int W, const float* bg, const int* radii,
+                                         void* geom, size_t geom_bytes_, const unsigned* point_list, void* image,
+                                         size_t image_bytes_, const float* dL_dcolor, const float* dL_ddepth,
+                                         const float* dL_dalpha, float* dL_dmeans3D, float* dL_dscales,
+                                         float* dL_drotations, float* dL_dopacities, float* dL_dshs, float* dL_dmeans2D,
+                                         float* dL_dconfidence, void* workspace, size_t workspace_bytes, int raw, int flags,
+                                         const float* filter3d, float* dL_dmeans2D_abs, void* stream_) {
+    SYN3R_REQUIRE(!dL_dmeans2D_abs || ((uintptr_t)dL_dmeans2D_abs & 7) == 0, "raster_backward: dL_dmeans2D_abs must be 8-byte aligned");
+    return raster_backward(raster_scene(N, sh_degree, sh_coeffs, means3D, scales, rotations, opacities, shs, confidence,
+                                        scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, raw, flags, filter3d),
+                           P, bg, radii, geom, geom_bytes_, point_list, image, image_bytes_,
+                           RasterGrads{dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacities,
+                                       dL_dshs, dL_dmeans2D, dL_dconfidence, dL_dmeans2D_abs},
                            workspace, workspace_bytes, stream_);
 }
 

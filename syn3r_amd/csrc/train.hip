@@ -283,18 +283,35 @@ __global__ void __launch_bounds__(kThreads) k_activate_bwd(int N, const float* _
 }
 
 // GaussianModel.add_densification_stats of the published trainer for the visible Gaussians (radii > 0): torch.norm(grad[:, :2]) is
-// sqrt(gx*gx + gy*gy) in fp32 (this file compiles without fma contraction)
-__global__ void __launch_bounds__(kThreads) k_densify_stats(int N, const int* __restrict__ radii, const float* __restrict__ vgrad,
-                                                           float* __restrict__ accum, float* __restrict__ denom,
-                                                           float* __restrict__ max_radii) {
+// sqrt(gx*gx + gy*gy) in fp32 (this file compiles without fma contraction).  ABS (syn3r_densification_stats_abs): the same norm of
+// the rasteriser's absolute screen-space gradient ([N,2]) goes into a second accumulator, the statistic AbsGS splits on.
+template <bool ABS>
+__device__ __forceinline__ void densify_stats(int N, const int* __restrict__ radii, const float* __restrict__ vgrad,
+                                              const float* __restrict__ agrad, float* __restrict__ accum,
+                                              float* __restrict__ accum_abs, float* __restrict__ denom, float* __restrict__ max_radii) {
     const int i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= N) return;
     const int r = radii[i];
     if (r <= 0) return;
     const float gx = vgrad[3 * i], gy = vgrad[3 * i + 1];
     accum[i] += sqrtf(gx * gx + gy * gy);
+    if constexpr (ABS) {
+        const float ax = agrad[2 * i], ay = agrad[2 * i + 1];
+        accum_abs[i] += sqrtf(ax * ax + ay * ay);
+    }
     denom[i] += 1.0f;
     max_radii[i] = fmaxf(max_radii[i], (float)r);
+}
+__global__ void __launch_bounds__(kThreads) k_densify_stats(int N, const int* __restrict__ radii, const float* __restrict__ vgrad,
+                                                           float* __restrict__ accum, float* __restrict__ denom,
+                                                           float* __restrict__ max_radii) {
+    densify_stats<false>(N, radii, vgrad, nullptr, accum, nullptr, denom, max_radii);
+}
+__global__ void __launch_bounds__(kThreads) k_densify_stats_abs(int N, const int* __restrict__ radii, const float* __restrict__ vgrad,
+                                                               const float* __restrict__ agrad, float* __restrict__ accum,
+                                                               float* __restrict__ accum_abs, float* __restrict__ denom,
+                                                               float* __restrict__ max_radii) {
+    densify_stats<true>(N, radii, vgrad, agrad, accum, accum_abs, denom, max_radii);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -873,6 +890,17 @@ extern "C" int syn3r_densification_stats(int N, const int* radii, const float* v
     SYN3R_LAUNCH(k_densify_stats, dim3((unsigned)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream_, N, radii,
                  viewspace_grad, grad_accum, denom, max_radii);
     SYN3R_LAUNCH_CHECK("densification_stats launch");
+    return SYN3R_OK;
+}
+
+extern "C" int syn3r_densification_stats_abs(int N, const int* radii, const float* viewspace_grad, const float* abs_grad,
+                                             float* grad_accum, float* grad_accum_abs, float* denom, float* max_radii, void* stream_) {
+    SYN3R_REQUIRE(SYN3R_DIM_OK(N), "densification_stats_abs: bad N=%d", N);
+    SYN3R_REQUIRE(radii && viewspace_grad && abs_grad && grad_accum && grad_accum_abs && denom && max_radii,
+                  "densification_stats_abs: null pointer");
+    SYN3R_LAUNCH(k_densify_stats_abs, dim3((unsigned)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream_, N,
+                 radii, viewspace_grad, abs_grad, grad_accum, grad_accum_abs, denom, max_radii);
+    SYN3R_LAUNCH_CHECK("densification_stats_abs launch");
     return SYN3R_OK;
 }
 

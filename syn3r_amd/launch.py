@@ -118,6 +118,13 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                     help="1: Mip-Splatting's 3D smoothing filter in every render of the trainer (OptimizationParams.filter_3d: every "
                          "Gaussian bounded from below by the sampling rate of the training cameras; constants recalled, UNPINNED).  "
                          "The filter is stored in checkpoints.  0 (default): off")
+    ap.add_argument("--densify_abs_grad", type=int, default=0, choices=(0, 1),
+                    help="1: AbsGS' density control (OptimizationParams.densify_abs_grad): the split decision is taken on the "
+                         "accumulated ABSOLUTE screen-space gradient against --densify_abs_grad_threshold, the clone decision stays "
+                         "on the plain one against --densify_grad_threshold.  0 (default): the published 3DGS rule for both")
+    ap.add_argument("--densify_abs_grad_threshold", type=float, default=None,
+                    help="OptimizationParams.densify_abs_grad_threshold (default: the trainer's own, 0.0008 - recalled, UNPINNED, "
+                         "scene dependent)")
     ap.add_argument("--num_inference_steps", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     # FSGS' parameter groups (scripts/train.py:44-46: -s, --eval, --n_views, --resolution, --use_dust3r ... of the batch scripts)
@@ -126,8 +133,11 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     args, rest = ap.parse_known_args(given)
     # argparse takes `--percent_dens` for an abbreviation of `--percent_dense`: while that flag sat in FSGS_FLAGS the token was an
     # unknown argument, and a misspelling stays one
-    declared = ["--" + f for f, _ in TRAINER_FLAGS] + ["--gs_schedule", "--pixel_confidence", "--antialiasing", "--filter_3d"]
-    cut = [t for t in given if t.startswith("--") and any(d != t.split("=")[0] and d.startswith(t.split("=")[0]) for d in declared)]
+    declared = ["--" + f for f, _ in TRAINER_FLAGS] + ["--gs_schedule", "--pixel_confidence", "--antialiasing", "--filter_3d",
+                                                       "--densify_abs_grad", "--densify_abs_grad_threshold"]
+    # (a token that IS a declared flag is not an abbreviation of a longer one: --densify_abs_grad / --densify_abs_grad_threshold)
+    cut = [t for t in given if t.startswith("--") and t.split("=")[0] not in declared
+           and any(d.startswith(t.split("=")[0]) for d in declared)]
     if cut:
         ap.error(f"unknown argument(s): {' '.join(cut)} (the trainer's flags are not abbreviated)")
     # Only the flags of FSGS' ModelParams / OptimizationParams / PipelineParams groups that the reference's batch scripts pass
@@ -155,8 +165,8 @@ def apply_trainer_flags(opt, args):
     """-> a copy of `opt` (gs.OptimizationParams) with the TRAINER_FLAGS that were given (not None) in their fields, and with
     `--gs_schedule published` the switches of the three published optimiser rules: decay to --position_lr_final or 1.6e-6,
     spatial_lr_scale = None (the camera extent), feature_rest_lr_div = 20, sh_degree_interval = 1000.  Pure: no GPU, `opt`
-    untouched.  `--antialiasing 1` sets `antialiasing`, `--filter_3d 1` sets `filter_3d` (0, the default, leaves the field as `opt` has
-    it).  (--sh_degree
+    untouched.  `--antialiasing 1` sets `antialiasing`, `--filter_3d 1` sets `filter_3d`, `--densify_abs_grad 1` sets `densify_abs_grad`
+    (0, the default, leaves the field as `opt` has it); `--densify_abs_grad_threshold`, when given, sets its field.  (--sh_degree
     describes the model, not the optimiser: the scene factory reads it.)"""
     import dataclasses
     new = {}
@@ -172,6 +182,10 @@ def apply_trainer_flags(opt, args):
         new["antialiasing"] = True
     if getattr(args, "filter_3d", 0):
         new["filter_3d"] = True
+    if getattr(args, "densify_abs_grad", 0):
+        new["densify_abs_grad"] = True
+    if getattr(args, "densify_abs_grad_threshold", None) is not None:
+        new["densify_abs_grad_threshold"] = float(args.densify_abs_grad_threshold)
     return dataclasses.replace(opt, **new)
 
 
