@@ -210,6 +210,8 @@ int syn3r_step_replace(const void* model_output, int vdtype, const void* sample,
  * world_view_transform / full_proj_transform of FSGS cameras); campos host [3].
  * State buffers (geom, binning, image) are caller-owned byte buffers sized by
  * the *_bytes queries; they carry the forward's intermediates to the backward.
+ * They need not be initialised: stage 1 clears what the later stages accumulate
+ * into or test (the four header words of geom, whatever N is).
  * ------------------------------------------------------------------------ */
 size_t syn3r_raster_geom_bytes(int N);
 size_t syn3r_raster_image_bytes(int H, int W);

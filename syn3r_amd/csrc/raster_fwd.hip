@@ -138,8 +138,9 @@ __global__ void __launch_bounds__(256) k_preprocess(int N, int D, int M, const f
                                                     float scale_mod, Camera cam, int* __restrict__ radii,
                                                     GeomState g, int raw, const float* __restrict__ filter3d) {
     int i = blockIdx.x * 256 + threadIdx.x;
+    // pair count (written by the scan that follows), overflow flag, clipped and exact totals: cleared whatever N is (N < 4 too)
+    if (i < 4) g.header[i] = 0u;
     if (i >= N) return;
-    if (i < 4) g.header[i] = 0u;            // pair count (written by the scan that follows) and overflow flag
     radii[i] = 0;
     g.tiles_touched[i] = 0;
     g.dkeys_a[i] = 0xFFFFFFFFu;             // culled Gaussians sort behind every visible one
