@@ -427,6 +427,38 @@ int syn3r_raster_backward_abs(int N, int sh_degree, int sh_coeffs, long long P, 
                               float* dL_drotations, float* dL_dopacities, float* dL_dshs, float* dL_dmeans2D,
                               float* dL_dconfidence, void* workspace, size_t workspace_bytes, int raw, int flags,
                               const float* filter3d, float* dL_dmeans2D_abs, void* stream);
+/*
+ * syn3r_raster_backward_abs with the gradient of the loss with respect to the CAMERA: an EXTENSION with no counterpart in the
+ * reference or in the published rasteriser (gsplat's `pose_opt` and MonoGS differentiate their own parametrisations), for a trainer
+ * that refines its camera poses.  Arguments as there, then `dL_dcamera` (35 device floats, or NULL) and `accumulate` before the
+ * stream; NULL is syn3r_raster_backward_abs exactly (the same kernels, the same number of launches).  It composes with every mode
+ * (`raw`, `flags`, `filter3d`, `dL_dmeans2D_abs` given or NULL) and leaves every other output as it is.
+ * Layout: dL/dviewmatrix[16], dL/dprojmatrix[16], dL/dcampos[3], each in the storage order of its input (column-major 4 x 4, as
+ * the render reads them).  The THREE INPUTS ARE TAKEN AS INDEPENDENT, exactly as the entry takes them: that projmatrix is a
+ * projection times viewmatrix and campos the centre of viewmatrix is the caller's knowledge, and so is the chain rule through it
+ * (syn3r_amd/gs/pose.py: tangent_from_raw).  viewmatrix enters through the view-space mean (EWA Jacobian, depth output) and through
+ * its rotation part W in T = J W; projmatrix through the x, y and w rows of the clip-space mean; campos through the SH view
+ * direction.  The slots the render never reads are exact zeros: view 3, 7, 11, 15 (fourth row) and proj 2, 6, 10, 14 (clip z).
+ * Per Gaussian 27 terms are formed by a second launch of the projection backward compiled WITHOUT its stores (the per-Gaussian
+ * outputs are written by the usual instance and are bit for bit those of syn3r_raster_backward_abs), summed per block without atomics
+ * and added over the blocks in a fixed order with fp64 accumulators by a one-block kernel: the result is the same bits in every launch
+ * for the same gradient records.  Two launches more than without it.  accumulate == 0 stores
+ * it; accumulate != 0 adds it to what `dL_dcamera` holds, one fp32 add per slot (a trainer that sums several steps of one camera).
+ * The workspace must hold syn3r_raster_backward_cam_workspace_bytes(N) when dL_dcamera is given (the size of the other entries plus
+ * one 128-byte row per 256 Gaussians); with NULL syn3r_raster_backward_workspace_bytes(N) is enough.  P == 0: zeros.
+ */
+size_t syn3r_raster_backward_cam_workspace_bytes(int N);
+int syn3r_raster_backward_cam(int N, int sh_degree, int sh_coeffs, long long P, const float* means3D,
+                              const float* scales, const float* rotations, const float* opacities, const float* shs,
+                              const float* confidence, float scale_modifier, const float* viewmatrix,
+                              const float* projmatrix, const float* campos, float tanfovx, float tanfovy, int H, int W,
+                              const float* bg, const int* radii, void* geom, size_t geom_bytes,
+                              const unsigned* point_list, void* image, size_t image_bytes, const float* dL_dcolor,
+                              const float* dL_ddepth, const float* dL_dalpha, float* dL_dmeans3D, float* dL_dscales,
+                              float* dL_drotations, float* dL_dopacities, float* dL_dshs, float* dL_dmeans2D,
+                              float* dL_dconfidence, void* workspace, size_t workspace_bytes, int raw, int flags,
+                              const float* filter3d, float* dL_dmeans2D_abs, float* dL_dcamera, int accumulate,
+                              void* stream);
 
 /*
  * Stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits) — the

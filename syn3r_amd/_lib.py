@@ -33,6 +33,8 @@ _RASTER_PREPROCESS = [c_i, c_i, c_i] + _SCENE + [c_p, c_p, c_sz, C.POINTER(c_ll)
 _RASTER_BACKWARD = ([c_i, c_i, c_i, c_ll] + _SCENE + [c_p, c_p, c_p, c_sz, c_p, c_p, c_sz]   # bg .. image_bytes
                     + [c_p] * 10 + [c_p, c_sz])                                           # 3 upstream, 7 gradients, workspace
 _STREAM, _EX, _F3D, _ABS = [c_p], [c_i, c_i, c_p], [c_i, c_i, c_p, c_p], [c_i, c_i, c_p, c_p, c_p]   # (_abs: + dL_dmeans2D_abs)
+_CAM = [c_i, c_i, c_p, c_p, c_p, c_i, c_p]            # (_cam: + dL_dmeans2D_abs, dL_dcamera, accumulate)
+CAMERA_GRAD = 35                                      # floats of dL_dcamera: view[16], proj[16], campos[3]
 
 # name -> (restype, argtypes); mirrors include/syn3r_hip.h declaration by declaration
 SIGNATURES = {
@@ -72,6 +74,8 @@ SIGNATURES = {
     "syn3r_raster_backward_ex": (c_i, _RASTER_BACKWARD + _EX),
     "syn3r_raster_backward_f3d": (c_i, _RASTER_BACKWARD + _F3D),
     "syn3r_raster_backward_abs": (c_i, _RASTER_BACKWARD + _ABS),
+    "syn3r_raster_backward_cam_workspace_bytes": (c_sz, [c_i]),
+    "syn3r_raster_backward_cam": (c_i, _RASTER_BACKWARD + _CAM),
     "syn3r_filter3d_workspace_bytes": (c_sz, [c_i]),
     "syn3r_filter3d_compute": (c_i, [c_p, c_i, c_p, c_i, c_f, c_f, c_f, c_p, c_p, c_sz, c_p]),
     "syn3r_sort_pairs_workspace_bytes": (c_sz, [c_ll]),

@@ -328,7 +328,8 @@ __device__ __forceinline__ float dot(F3 a, F3 b) { return a.x * b.x + a.y * b.y 
 // SH colour backward: writes dL_dsh (M x 3) and returns dL_dmean through the view direction
 // PRELOAD (M == 16): every coefficient is read into registers before the first output is written, so `dL_dsh` may be the row
 // `sh` itself (k_preprocess_bwd's LDS-staged rows)
-template <bool PRELOAD>
+// WRITE = false: dL_dsh is not written (the camera pass of k_preprocess_bwd wants the returned direction gradient alone)
+template <bool PRELOAD, bool WRITE = true>
 __device__ __forceinline__ F3 sh_backward(int D, int M, F3 pos, const float* campos, const float* sh, unsigned clamped,
                                           F3 dL_dRGB, float* dL_dsh) {
     F3 dir_o = f3(pos.x - campos[0], pos.y - campos[1], pos.z - campos[2]);
@@ -345,6 +346,7 @@ __device__ __forceinline__ F3 sh_backward(int D, int M, F3 pos, const float* cam
     }
     auto c = [&](int k) { return PRELOAD ? f3(pre[3 * k], pre[3 * k + 1], pre[3 * k + 2]) : f3(sh[3 * k], sh[3 * k + 1], sh[3 * k + 2]); };
     auto put = [&](int k, float s) {
+        if constexpr (!WRITE) return;
         dL_dsh[3 * k] = s * dL_dRGB.x; dL_dsh[3 * k + 1] = s * dL_dRGB.y; dL_dsh[3 * k + 2] = s * dL_dRGB.z;
     };
     F3 dx = f3(0, 0, 0), dy = f3(0, 0, 0), dz = f3(0, 0, 0);
@@ -402,16 +404,67 @@ __device__ __forceinline__ F3 sh_backward(int D, int M, F3 pos, const float* cam
 // evaluated WITHOUT the division by s_i: coef / s_i = prod_{j != i} r_j / q_i on the activated route, and on the raw route the
 // chain rule's factor s_i cancels it (dL/dlog s_i = dL/dq_i r_i s_i + G op cf [rho] coef f^2 / q_i^2).  The filter gets no gradient.
 // The scales are loaded BEFORE the opacity gradient is written on the F3D path only (coef is needed there).
+// POSE (a caller that asked for dL_dcamera, syn3r_raster_backward_cam; launched AFTER the POSE = false instance of the same mode): every
+// thread forms the 27 terms its Gaussian adds to the gradients of the camera - the three inputs taken as INDEPENDENT, as the ABI takes them:
+//     view (12):  t = view [p,1], so dL/dview[c*4+r] += [p,1]_c (dtx, dty, dtz)_r; W = view[:3,:3] also enters T = J W, so dL/dW = J^T dT
+//                 with J = (J00 0 J02; 0 J11 J12) the VALUES ewa_rows used (J02 / J12 from the clamped tx / ty: inside dT they are
+//                 factors; the guard band's x_mul / y_mul are in dtx / dty already)
+//     proj (12):  ph = proj [p,1] (x, y, w read): dL/dph = (mw g2x, mw g2y, -(mul1 g2x + mul2 g2y)), outer product with [p,1]
+//     campos (3): the SH direction is p - campos: -dm_sh
+// AA and F3D add nothing: their rho / coef terms are in dL_dA/B/C and hence in dT.  A culled Gaussian and a thread past N add zeros.
+// The block's sums leave as ONE row of kPoseRow floats (pose_row_sum), without atomics; k_camera_grad_finish adds the rows.  POSE = false
+// compiles to the code without any of it.  The POSE instance is the SAME chain rule with the stores of the per-Gaussian outputs compiled
+// out (and with them whatever only they need: the scale / rotation part, the SH products): the per-Gaussian gradients of a call with
+// dL_dcamera are written by the POSE = false instance and are the bits of a call without it.  One kernel that did both was tried first:
+// the 27 extra products change which multiplications hipcc pairs into packed instructions and hence which of them it contracts with
+// an addition, and dL_dshs / dL_dmeans3D came out an ulp away from the plain instance's.
+constexpr int kPoseTerms = 27, kPoseRow = 32;
+// Sum kPoseRow per-thread values (27 terms, 5 zeros) over the block of four wavefronts and write them to `row`.  Two transposing
+// levels (reduce_lanes' half and row swaps: 32 -> 16 -> 8 live values), then four xor steps inside a 16-lane row; all through
+// compiler-visible builtins, so hipcc places the wait states.  Lane 16 q of a wavefront ends with the wavefront's totals of the
+// values k + 8 (q & 1) + 16 (q >> 1), k = 0 .. 7.  The four wavefronts meet in `lds` (an array of its own: the STAGED instances still
+// hold `shl`) and are added in a fixed order: the row is the same bits in every launch.  Every thread of the block must call this.
+__device__ __forceinline__ void pose_row_sum(float (&v)[kPoseRow], float (&lds)[4][kPoseRow], float* __restrict__ row) {
+    float a[16], b[8];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {   // the lower half owns value k, the upper k + 16
+        auto r = __builtin_amdgcn_permlane32_swap(__float_as_int(v[k]), __float_as_int(v[k + 16]), false, false);
+        a[k] = __int_as_float(r[0]) + __int_as_float(r[1]);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {    // even rows own k, odd rows k + 8
+        auto r = __builtin_amdgcn_permlane16_swap(__float_as_int(a[k]), __float_as_int(a[k + 8]), false, false);
+        b[k] = __int_as_float(r[0]) + __int_as_float(r[1]);
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) b[k] += __shfl_xor(b[k], o, 64);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4;
+    if ((lane & 15) == 0) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) lds[wave][k + 8 * (q & 1) + 16 * (q >> 1)] = b[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < kPoseRow) row[threadIdx.x] = ((lds[0][threadIdx.x] + lds[1][threadIdx.x]) + lds[2][threadIdx.x]) + lds[3][threadIdx.x];
+}
+
 constexpr int kShLd = 49;      // LDS row stride (floats): odd, so the 64 rows of a wavefront fall into 64 banks
-template <bool STAGED, bool AA, bool F3D>
+template <bool STAGED, bool AA, bool F3D, bool POSE>
 __global__ void __launch_bounds__(256) k_preprocess_bwd(
     int N, int D, int M, const float* __restrict__ means3D, const float* __restrict__ scales,
     const float* __restrict__ rots, const float* __restrict__ opacities, const float* __restrict__ shs,
     const float* __restrict__ conf, float scale_mod, Camera cam, const int* __restrict__ radii, GeomState g,
     const float* __restrict__ grad_rec, float* __restrict__ dL_dmeans3D, float* __restrict__ dL_dscales,
     float* __restrict__ dL_drots, float* __restrict__ dL_dopacity, float* __restrict__ dL_dshs,
-    float* __restrict__ dL_dmeans2D, float* __restrict__ dL_dconf, int raw, const float* __restrict__ filter3d) {
+    float* __restrict__ dL_dmeans2D, float* __restrict__ dL_dconf, int raw, const float* __restrict__ filter3d,
+    float* __restrict__ pose_rows) {
     __shared__ float shl[STAGED ? 256 * kShLd : 1];
+    float pz[POSE ? kPoseRow : 1];        // this thread's camera terms: view 0-11 (c * 3 + r), proj 12-23 (c * 3 + x/y/w), campos 24-26
+    if constexpr (POSE) {
+#pragma unroll
+        for (int k = 0; k < kPoseRow; ++k) pz[k] = 0.0f;
+    }
     const int i = blockIdx.x * 256 + threadIdx.x;
     const size_t blk0 = (size_t)blockIdx.x * 256 * 48;                // first float of the block's rows
     const int rows = min(256, N - (int)blockIdx.x * 256);
@@ -444,6 +497,7 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(
     if (i < N) do {
     float* osh = STAGED ? &shl[threadIdx.x * kShLd] : dL_dshs + (size_t)i * M * 3;
     if (radii[i] <= 0) {
+        if constexpr (POSE) break;
         for (int k = 0; k < 3; ++k) { dL_dmeans3D[3 * i + k] = 0.f; dL_dscales[3 * i + k] = 0.f; dL_dmeans2D[3 * i + k] = 0.f; }
         for (int k = 0; k < 4; ++k) dL_drots[4 * i + k] = 0.f;
         dL_dopacity[i] = 0.f;
@@ -539,12 +593,29 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(
     dmean.x += (pj[0] * mw - pj[3] * mul1) * g2x + (pj[1] * mw - pj[3] * mul2) * g2y;
     dmean.y += (pj[4] * mw - pj[7] * mul1) * g2x + (pj[5] * mw - pj[7] * mul2) * g2y;
     dmean.z += (pj[8] * mw - pj[11] * mul1) * g2x + (pj[9] * mw - pj[11] * mul2) * g2y;
-    dL_dmeans2D[3 * i] = g2x; dL_dmeans2D[3 * i + 1] = g2y; dL_dmeans2D[3 * i + 2] = 0.f;
+    if constexpr (!POSE) { dL_dmeans2D[3 * i] = g2x; dL_dmeans2D[3 * i + 1] = g2y; dL_dmeans2D[3 * i + 2] = 0.f; }
 
     // ---- colour -> SH and mean
-    F3 dm_sh = sh_backward<STAGED>(D, M, f3(p.x, p.y, p.z), cam.campos, STAGED ? (const float*)osh : shs + (size_t)i * M * 3, g.clamped[i],
+    F3 dm_sh = sh_backward<STAGED, !POSE>(D, M, f3(p.x, p.y, p.z), cam.campos, STAGED ? (const float*)osh : shs + (size_t)i * M * 3, g.clamped[i],
                                    f3(gr[G_R], gr[G_G], gr[G_B]), osh);
     dmean = dmean + dm_sh;
+    if constexpr (POSE) {
+        const float J00 = cam.focal_x * tz, J02 = -(cam.focal_x * tx) * tz2, J11 = cam.focal_y * tz, J12 = -(cam.focal_y * ty) * tz2;
+        const float pc[4] = {p.x, p.y, p.z, 1.0f};
+        const float dT0[3] = {dT00, dT01, dT02}, dT1[3] = {dT10, dT11, dT12};
+        const float dph_x = mw * g2x, dph_y = mw * g2y, dph_w = -(mul1 * g2x + mul2 * g2y);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            pz[3 * c] = pc[c] * dtx; pz[3 * c + 1] = pc[c] * dty; pz[3 * c + 2] = pc[c] * dtz;
+            pz[12 + 3 * c] = pc[c] * dph_x; pz[13 + 3 * c] = pc[c] * dph_y; pz[14 + 3 * c] = pc[c] * dph_w;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {     // dL/dW[r][c], W[r][c] = view[c * 4 + r]
+            pz[3 * c] += J00 * dT0[c]; pz[3 * c + 1] += J11 * dT1[c]; pz[3 * c + 2] += J02 * dT0[c] + J12 * dT1[c];
+        }
+        pz[24] = -dm_sh.x; pz[25] = -dm_sh.y; pz[26] = -dm_sh.z;
+        break;                            // the per-Gaussian outputs are the POSE = false instance's
+    }
     dL_dmeans3D[3 * i] = dmean.x; dL_dmeans3D[3 * i + 1] = dmean.y; dL_dmeans3D[3 * i + 2] = dmean.z;
 
     // ---- opacity / confidence (blend used opacity * confidence; cf and op_a: above the AA block)
@@ -618,7 +689,11 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(
     dL_dscales[3 * i] = ds0; dL_dscales[3 * i + 1] = ds1; dL_dscales[3 * i + 2] = ds2;
     dL_drots[4 * i] = dq.x; dL_drots[4 * i + 1] = dq.y; dL_drots[4 * i + 2] = dq.z; dL_drots[4 * i + 3] = dq.w;
     } while (0);
-    if constexpr (STAGED) {
+    if constexpr (POSE) {                 // uniform control flow: culled Gaussians, threads past N and the last block arrive with zeros
+        __shared__ float pose_lds[4][kPoseRow];
+        pose_row_sum(pz, pose_lds, pose_rows + (size_t)blockIdx.x * kPoseRow);
+    }
+    if constexpr (STAGED && !POSE) {
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < 12; ++k) {
@@ -649,10 +724,54 @@ __global__ void __launch_bounds__(256) k_abs_means2D(int N, float half_w, float 
     *(float2*)(abs2D + 2 * (size_t)i) = o;
 }
 
+// dL_dcamera of the `_cam` entry: the block rows of the POSE instances of k_preprocess_bwd, added in a fixed order (thread (g, col)
+// takes rows g, g + 32, ... of column col, then the 32 groups in order) with fp64 accumulators, rounded once to fp32 and written in
+// the storage order of the three inputs: view[16], proj[16], campos[3].  The third clip row (proj 2, 6, 10, 14) and the fourth view
+// row (view 3, 7, 11, 15) are not read by the render: exact zeros.  accumulate != 0: one fp32 add per slot onto what `out` holds.
+// One block of 1024 threads (782 rows at 200 000 Gaussians: 25 per thread, the loads of eight rows in flight at a time - with 256
+// threads and one load per dependent add the kernel took 24 us); the same bits in every launch.
+constexpr int kCameraGrad = 35, kFinishGroups = 32;
+__global__ void __launch_bounds__(kFinishGroups * kPoseRow) k_camera_grad_finish(int nrows, const float* __restrict__ rows,
+                                                                                 float* __restrict__ out, int accumulate) {
+    __shared__ double part[kFinishGroups][kPoseRow];
+    const int col = threadIdx.x & (kPoseRow - 1), grp = threadIdx.x / kPoseRow;
+    double acc = 0.0;
+    int r = grp;
+    for (; r + 7 * kFinishGroups < nrows; r += 8 * kFinishGroups) {
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = rows[(size_t)(r + k * kFinishGroups) * kPoseRow + col];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc += (double)v[k];
+    }
+    for (; r < nrows; r += kFinishGroups) acc += (double)rows[(size_t)r * kPoseRow + col];
+    part[grp][col] = acc;
+    __syncthreads();
+    const int j = threadIdx.x;
+    if (j >= kCameraGrad) return;
+    int term = -1;                        // the index into a block row, or -1: a slot the render does not read
+    if (j < 16) { const int c = j >> 2, r = j & 3; term = r < 3 ? 3 * c + r : -1; }
+    else if (j < 32) { const int c = (j - 16) >> 2, r = j & 3; term = r == 2 ? -1 : 12 + 3 * c + (r == 3 ? 2 : r); }
+    else term = 24 + (j - 32);
+    float val = 0.0f;
+    if (term >= 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int g = 0; g < kFinishGroups; ++g) t += part[g][term];
+        val = (float)t;
+    }
+    out[j] = accumulate ? out[j] + val : val;
+}
+
 }  // namespace
 
 extern "C" size_t syn3r_raster_backward_workspace_bytes(int N) {
     return N > 0 ? align256((size_t)N * kGradSlots * sizeof(float)) : 0;
+}
+
+// ... plus one row of kPoseRow floats per block of k_preprocess_bwd, behind the gradient records
+extern "C" size_t syn3r_raster_backward_cam_workspace_bytes(int N) {
+    return N > 0 ? syn3r_raster_backward_workspace_bytes(N) + align256((size_t)ceil_div(N, 256) * kPoseRow * sizeof(float)) : 0;
 }
 
 // the three upstream gradients (depth, alpha: may be null) and the seven gradient outputs (confidence: may be null)
@@ -660,6 +779,8 @@ struct RasterGrads {
     const float *dL_dcolor, *dL_ddepth, *dL_dalpha;
     float *dL_dmeans3D, *dL_dscales, *dL_drotations, *dL_dopacities, *dL_dshs, *dL_dmeans2D, *dL_dconfidence;
     float* dL_dmeans2D_abs = nullptr;   // [N,2], syn3r_raster_backward_abs alone; null: the backward of the other entries
+    float* dL_dcamera = nullptr;        // [35], syn3r_raster_backward_cam alone; null: no POSE instance, no finishing launch
+    int accumulate = 0;                 // dL_dcamera: add to what the buffer holds
 };
 
 static int raster_backward(const RasterScene& s, long long P, const float* bg, const int* radii, void* geom, size_t geom_bytes_,
@@ -672,9 +793,10 @@ static int raster_backward(const RasterScene& s, long long P, const float* bg, c
     SYN3R_REQUIRE(d.dL_dcolor && d.dL_dmeans3D && d.dL_dscales && d.dL_drotations && d.dL_dopacities && d.dL_dshs && d.dL_dmeans2D,
                   "raster_backward: null gradient buffer");
     SYN3R_REQUIRE(P == 0 || point_list, "raster_backward: point list required");
-    size_t need = syn3r_raster_backward_workspace_bytes(N);
+    const size_t need = syn3r_raster_backward_workspace_bytes(N);          // the gradient records (the memset below)
+    const size_t need_all = d.dL_dcamera ? syn3r_raster_backward_cam_workspace_bytes(N) : need;
     if (!geom || geom_bytes_ < geom_bytes(N) || !image || image_bytes_ < image_bytes(H, W) || !workspace ||
-        workspace_bytes < need) {
+        workspace_bytes < need_all) {
         set_error("raster_backward: state/workspace buffer too small");
         return SYN3R_E_WORKSPACE;
     }
@@ -684,6 +806,7 @@ static int raster_backward(const RasterScene& s, long long P, const float* bg, c
     Camera cam;
     raster_fill_camera(cam, s.viewmatrix, s.projmatrix, s.campos, s.tanfovx, s.tanfovy, H, W);
     float* grad_rec = (float*)workspace;
+    float* pose_rows = d.dL_dcamera ? (float*)((char*)workspace + need) : nullptr;   // every block writes its whole row: no memset
     int rc = check_hip(hipMemsetAsync(grad_rec, 0, need, stream), "memset grads");
     if (rc) return rc;
     const unsigned tiles = (unsigned)(cam.grid_x * cam.grid_y);
@@ -700,11 +823,22 @@ static int raster_backward(const RasterScene& s, long long P, const float* bg, c
     const bool staged = s.sh_coeffs == 16 && ((((uintptr_t)s.shs) | ((uintptr_t)d.dL_dshs)) & 15) == 0;
     with_bools([&](auto st, auto aa, auto f3d) {
         SYN3R_LAUNCH_NAMED(staged ? "k_preprocess_bwd<true>" : "k_preprocess_bwd<false>",
-                           (k_preprocess_bwd<decltype(st)::value, decltype(aa)::value, decltype(f3d)::value>), dim3(ceil_div(N, 256)),
+                           (k_preprocess_bwd<decltype(st)::value, decltype(aa)::value, decltype(f3d)::value, false>), dim3(ceil_div(N, 256)),
                            dim3(256), 0, stream, N, s.sh_degree, s.sh_coeffs, s.means3D, s.scales, s.rotations, s.opacities, s.shs,
                            s.confidence, s.scale_modifier, cam, radii, g, grad_rec, d.dL_dmeans3D, d.dL_dscales, d.dL_drotations,
-                           d.dL_dopacities, d.dL_dshs, d.dL_dmeans2D, d.dL_dconfidence, s.raw, s.filter3d);
+                           d.dL_dopacities, d.dL_dshs, d.dL_dmeans2D, d.dL_dconfidence, s.raw, s.filter3d, nullptr);
     }, staged, (s.flags & SYN3R_RASTER_ANTIALIAS) != 0, s.filter3d != nullptr);
+    if (d.dL_dcamera) {
+        // the camera pass: the same kernel without its stores (see POSE), then the sum over its block rows
+        with_bools([&](auto st, auto aa, auto f3d) {
+            SYN3R_LAUNCH_NAMED("k_preprocess_bwd_pose",
+                               (k_preprocess_bwd<decltype(st)::value, decltype(aa)::value, decltype(f3d)::value, true>), dim3(ceil_div(N, 256)),
+                               dim3(256), 0, stream, N, s.sh_degree, s.sh_coeffs, s.means3D, s.scales, s.rotations, s.opacities, s.shs,
+                               s.confidence, s.scale_modifier, cam, radii, g, grad_rec, nullptr, nullptr, nullptr, nullptr, nullptr,
+                               nullptr, nullptr, s.raw, s.filter3d, pose_rows);
+        }, s.sh_coeffs == 16 && (((uintptr_t)s.shs) & 15) == 0, (s.flags & SYN3R_RASTER_ANTIALIAS) != 0, s.filter3d != nullptr);
+        SYN3R_LAUNCH(k_camera_grad_finish, dim3(1), dim3(kFinishGroups * kPoseRow), 0, stream, ceil_div(N, 256), pose_rows, d.dL_dcamera, d.accumulate);
+    }
     if (d.dL_dmeans2D_abs)
         SYN3R_LAUNCH(k_abs_means2D, dim3(ceil_div(N, 256)), dim3(256), 0, stream, N, 0.5f * (float)W, 0.5f * (float)H, radii, g.splats,
                      grad_rec, d.dL_dmeans2D_abs);
@@ -803,6 +937,28 @@ extern "C" int syn3r_raster_backward_abs(int N, int sh_degree, int sh_coeffs, lo
                            P, bg, radii, geom, geom_bytes_, point_list, image, image_bytes_,
                            RasterGrads{dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacities,
                                        dL_dshs, dL_dmeans2D, dL_dconfidence, dL_dmeans2D_abs},
+                           workspace, workspace_bytes, stream_);
+}
+
+extern "C" int syn3r_raster_backward_cam(int N, int sh_degree, int sh_coeffs, long long P, const float* means3D,
+                                         const float* scales, const float* rotations, const float* opacities,
+                                         const float* shs, const float* confidence, float scale_modifier,
+                                         const float* viewmatrix, const float* projmatrix, const float* campos,
+                                         float tanfovx, float tanfovy, int H, int W, const float* bg, const int* radii,
+                                         void* geom, size_t geom_bytes_, const unsigned* point_list, void* image,
+                                         size_t image_bytes_, const float* dL_dcolor, const float* dL_ddepth,
+                                         const float* dL_dalpha, float* dL_dmeans3D, float* dL_dscales,
+                                         float* dL_drotations, float* dL_dopacities, float* dL_dshs, float* dL_dmeans2D,
+                                         float* dL_dconfidence, void* workspace, size_t workspace_bytes, int raw, int flags,
+                                         const float* filter3d, float* dL_dmeans2D_abs, float* dL_dcamera, int accumulate,
+                                         void* stream_) {
+    SYN3R_REQUIRE(!dL_dmeans2D_abs || ((uintptr_t)dL_dmeans2D_abs & 7) == 0, "raster_backward: dL_dmeans2D_abs must be 8-byte aligned");
+    SYN3R_REQUIRE(!dL_dcamera || ((uintptr_t)dL_dcamera & 3) == 0, "raster_backward: dL_dcamera must be 4-byte aligned");
+    return raster_backward(raster_scene(N, sh_degree, sh_coeffs, means3D, scales, rotations, opacities, shs, confidence,
+                                        scale_modifier, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, raw, flags, filter3d),
+                           P, bg, radii, geom, geom_bytes_, point_list, image, image_bytes_,
+                           RasterGrads{dL_dcolor, dL_ddepth, dL_dalpha, dL_dmeans3D, dL_dscales, dL_drotations, dL_dopacities,
+                                       dL_dshs, dL_dmeans2D, dL_dconfidence, dL_dmeans2D_abs, dL_dcamera, accumulate},
                            workspace, workspace_bytes, stream_);
 }
 

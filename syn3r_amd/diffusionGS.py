@@ -391,7 +391,7 @@ class DiffusionGS:
                 if checkpoint_path is None or not os.path.exists(checkpoint_path):
                     checkpoint_path = os.path.join(model_path, "chkpnt_latest.pth")
                 tr.load_checkpoint(checkpoint=checkpoint_path)                        # the initial GS
-        # the reference deep-copies scene.train_cameras (:1627); the camera objects are not mutated by a finetune, so
+        # the reference deep-copies scene.train_cameras (:1627); the camera objects are not replaced by a finetune (pose refinement, when on, moves them in place: kept), so
         # copying the lists is enough to restore them (:1641)
         self.original_GS_train_cameras_bak = {k: list(v) for k, v in tr.scene.train_cameras.items()}
         if confidence_maps is not None:
@@ -404,6 +404,8 @@ class DiffusionGS:
         tr.reset_gs()
         tr.finetune(0, self.refine_epoch, disable_densification=disable_densification,
                     pseudo_cam_sampling_rate=pseudo_cam_sampling_rate)
+        if hasattr(tr, "flush_pose_updates"):
+            tr.flush_pose_updates()                      # (pose refinement: what is pending belongs to the cameras of this finetune)
         tr.scene.train_cameras = self.original_GS_train_cameras_bak                   # restore the original GS cameras
         self.refine_epoch += 1
 

@@ -20,6 +20,7 @@ import torch
 
 from .. import _lib as L
 from ..raster import GaussianRasterizationSettings, GaussianRasterizer
+from . import pose as _pose
 from .train_ops import camera_table, compute_filter_3D
 from .train_ops import FusedAdam, depth_correlation_loss, image_metrics, knn3_mean_dist2, l1_loss, photometric_loss
 from .train_ops import proximity_unpool as _proximity_unpool_op
@@ -113,6 +114,18 @@ class Camera:
             cam.image_height, cam.image_width = H, W
         cam.confidence_map = cmap                      # (after the size is known)
         return cam
+
+    def set_pose(self, R, T):
+        """Move the camera (EXTENSION: pose refinement, `GSTrainer.apply_pose_updates`): `R` camera-to-world rotation, `T`
+        world-to-camera translation, as the constructor takes them.  `world_view_transform`, `full_proj_transform` and
+        `camera_center` (= -R_w2c^T T) are rebuilt as NEW tensors: the rasteriser's host copies of them are keyed by tensor identity
+        and version, so a moved camera can never be rendered from a stale matrix.  The projection does not change."""
+        self.R, self.T = np.asarray(R, np.float32).copy(), np.asarray(T, np.float32).reshape(3).copy()
+        w2c = torch.tensor(_world2view(self.R, self.T))
+        self.world_view_transform = w2c.transpose(0, 1).to(self.data_device)
+        self.full_proj_transform = self.world_view_transform @ self.projection_matrix
+        centre = -(self.R.astype(np.float64) @ self.T.astype(np.float64))
+        self.camera_center = torch.tensor(centre, dtype=torch.float32).to(self.data_device)
 
     def get_image(self):
         return self.original_image
@@ -362,6 +375,24 @@ class OptimizationParams:
     # (the statistics are not stored either).
     densify_abs_grad: bool = False
     densify_abs_grad_threshold: float = 0.0008
+    # Camera-pose refinement (EXTENSION: the reference has none; what a user of InstantSplat / gsplat's `pose_opt` / MonoGS expects of a
+    # sparse-view trainer whose input poses are estimates and whose pseudo-views sit at interpolated poses).  The rasteriser also
+    # returns the gradient with respect to the camera (`rasterize_backward(camera_grad_out=)`), the trainer sums it per camera on the
+    # device and every `pose_opt_interval` iterations (from `pose_opt_from_iter` on) takes one Adam step per camera that was
+    # trained meanwhile, on the 6-vector of a left perturbation of its world-to-camera matrix (`gs/pose.py`; `GSTrainer.
+    # apply_pose_updates`: ONE host read per update, none in a step).  `pose_opt_cameras`: "train" (the input views), "pseudo"
+    # (the views `update_cameras` registered) or "all".  The FIRST training camera never moves: it fixes the world frame (gauge).
+    # `pose_lr_rotation` is in radians; `pose_lr_translation` is multiplied by the trainer's `spatial_lr_scale` (the camera extent
+    # when `spatial_lr_scale` is None).  The two rates and the interval are CHOSEN, not taken from any source: UNPINNED and scene
+    # dependent.  Off by default: no table, no other rasteriser entry, every render, gradient and decision is what it was.  Refined
+    # poses and their Adam state ARE stored in checkpoints (written only with the option on).  `evaluate` renders the cameras it
+    # is given at THEIR poses: held-out views are not aligned to the refined frame.
+    pose_opt: bool = False
+    pose_opt_cameras: str = "all"
+    pose_lr_rotation: float = 1e-3
+    pose_lr_translation: float = 1e-3
+    pose_opt_interval: int = 10
+    pose_opt_from_iter: int = 0
 
 
 def expon_lr(step, lr_init: float, lr_final: float, lr_delay_steps: int = 0, lr_delay_mult: float = 1.0,
@@ -418,6 +449,12 @@ class GSTrainer:
         self.truncated_renders = 0        # renders whose (Gaussian, tile) pair list outgrew the async capacity (see _loop)
         self.filter_3d_computes = 0       # how often ensure_filter_3D has computed the filter
         self._f3d_cams, self._f3d_len, self._f3d_table, self._f3d_age = None, -1, None, 0
+        # pose refinement (`opt.pose_opt`): the device table [C,35] of summed camera gradients, one row per registered camera, the
+        # cameras of its rows (the list object and its members as they were when it was made) and the host count of steps per row
+        self._pose_table, self._pose_list, self._pose_cams, self._pose_counts = None, None, [], []
+        self.pose_updates = 0             # camera moves applied so far (apply_pose_updates)
+        if self.opt.pose_opt_cameras not in ("train", "pseudo", "all"):
+            raise ValueError(f"OptimizationParams.pose_opt_cameras must be 'train', 'pseudo' or 'all', got {self.opt.pose_opt_cameras!r}")
         self.background = torch.tensor(background, dtype=torch.float32, device=gaussians._xyz.device)
         self._rng = np.random.default_rng(self.opt.seed)
         self.reset_optimizers()
@@ -452,7 +489,109 @@ class GSTrainer:
         return grp["lr"]
 
     def reset_gs(self):
+        self.flush_pose_updates()
         return None
+
+    # ------------------------------------------------------------------ camera-pose refinement (EXTENSION, OptimizationParams.pose_opt)
+    def _pose_sync(self):
+        """Keep the gradient table in step with `scene.train_cameras[1.0]`: when the list is another object or has another length
+        (`update_cameras`, the orchestrator's restore) what is pending is applied to the cameras of the old rows and a fresh table is
+        made.  The Adam state lives on the camera objects, so it survives."""
+        cams = self.scene.train_cameras[1.0]
+        if self._pose_table is not None and self._pose_list is cams and len(self._pose_cams) == len(cams):
+            return
+        if self._pose_table is not None:
+            self.apply_pose_updates()
+        dev = self.gaussians._xyz.device
+        self._pose_list, self._pose_cams, self._pose_counts = cams, list(cams), [0] * len(cams)
+        self._pose_table = torch.zeros((max(len(cams), 1), L.CAMERA_GRAD), dtype=torch.float32, device=dev)
+
+    def _pose_row(self, cam: Camera) -> Optional[int]:
+        """The table row of `cam` if this step's camera gradient is wanted, else None: the option on and started, the camera registered,
+        of the chosen kind, and not the first training camera (the gauge: without a fixed camera the world frame drifts)."""
+        o = self.opt
+        if not o.pose_opt or self.iteration < int(o.pose_opt_from_iter):
+            return None
+        self._pose_sync()
+        row = next((i for i, c in enumerate(self._pose_cams) if c is cam), None)
+        if row is None:
+            return None
+        pseudo = bool(getattr(cam, "is_pseudo", False))
+        if (pseudo and o.pose_opt_cameras == "train") or (not pseudo and o.pose_opt_cameras == "pseudo"):
+            return None
+        train = self.scene.getTrainCameras()
+        if train and train[0] is cam:
+            return None
+        return row
+
+    def _pose_optimizer(self) -> "_pose.PoseOptimizer":
+        return _pose.PoseOptimizer(lr_rotation=float(self.opt.pose_lr_rotation),
+                                   lr_translation=float(self.opt.pose_lr_translation) * float(self.spatial_lr_scale))
+
+    def apply_pose_updates(self) -> int:
+        """ONE host read of the table; every camera with a non-zero count: mean raw gradient -> `pose.tangent_from_raw` -> one Adam step
+        (`pose.PoseOptimizer`, state on the camera object) -> `Camera.set_pose`.  Then the table and the counts restart and the 3D
+        filter's camera table is dropped (`ensure_filter_3D` rebuilds it from the moved poses).  Returns the number of cameras moved.
+        Independent of the density control: the camera gradient belongs to the camera, whatever happened to the Gaussians."""
+        if self._pose_table is None or not any(self._pose_counts):
+            return 0
+        host = self._pose_table.detach().cpu().double().numpy()
+        popt, moved = self._pose_optimizer(), 0
+        for row, (cam, n) in enumerate(zip(self._pose_cams, self._pose_counts)):
+            if n == 0:
+                continue
+            grad = _pose.tangent_from_raw(host[row] / float(n), cam)
+            if not np.all(np.isfinite(grad)):
+                continue                                   # (a degenerate render: leave the camera where it is)
+            state = getattr(cam, "pose_adam", None)
+            if state is None:
+                state = cam.pose_adam = popt.new_state()
+            M = popt.update(_pose.camera_w2c(cam), state, grad)
+            cam.set_pose(M[:3, :3].T, M[:3, 3])
+            moved += 1
+        self._pose_table.zero_()
+        self._pose_counts = [0] * len(self._pose_counts)
+        self._f3d_table = None
+        self.pose_updates += moved
+        return moved
+
+    def flush_pose_updates(self) -> int:
+        """Apply what is pending and start a fresh table at the next step (`update_cameras`, `reset_gs`, the orchestrator's restore of
+        the camera list).  Nothing with the option off."""
+        if self._pose_table is None:
+            return 0
+        moved = self.apply_pose_updates()
+        self._pose_table, self._pose_list, self._pose_cams, self._pose_counts = None, None, [], []
+        return moved
+
+    def _pose_capture(self) -> list:
+        """Per registered camera: index, kind, R, T and the Adam state, as tensors (the checkpoint loader reads tensors only)."""
+        out = []
+        for i, cam in enumerate(self.scene.train_cameras[1.0]):
+            st = getattr(cam, "pose_adam", None)
+            e = {"index": i, "is_pseudo": int(bool(getattr(cam, "is_pseudo", False))), "R": torch.from_numpy(np.array(cam.R, np.float32)),
+                 "T": torch.from_numpy(np.array(cam.T, np.float32))}
+            if st is not None:
+                e.update(m=torch.from_numpy(np.array(st["m"], np.float64)), v=torch.from_numpy(np.array(st["v"], np.float64)), t=int(st["t"]))
+            out.append(e)
+        return out
+
+    def _pose_restore(self, entries: list):
+        """Entry i goes to registered camera i when there is one of the same kind (a checkpoint written with pseudo-views registered
+        may be loaded after the list was restored: their entries are skipped)."""
+        cams = self.scene.train_cameras[1.0]
+        for e in entries:
+            i = int(e["index"])
+            if i >= len(cams) or int(bool(getattr(cams[i], "is_pseudo", False))) != int(e["is_pseudo"]):
+                continue
+            cams[i].set_pose(e["R"].cpu().numpy(), e["T"].cpu().numpy())
+            if "m" in e:
+                cams[i].pose_adam = {"m": e["m"].cpu().double().numpy().copy(), "v": e["v"].cpu().double().numpy().copy(), "t": int(e["t"])}
+            elif hasattr(cams[i], "pose_adam"):
+                del cams[i].pose_adam
+        # gradients summed at the poses just replaced are dropped, not applied
+        self._pose_table, self._pose_list, self._pose_cams, self._pose_counts = None, None, [], []
+        self._f3d_table = None
 
     @property
     def pseudo_cameras(self) -> List[Camera]:
@@ -463,6 +602,7 @@ class GSTrainer:
         `scene.train_cameras` (appended, as the reference; the orchestrator restores the list after the finetune).
         `confidence_maps` (EXTENSION; default None): one per-pixel map ([H,W], see `Camera.confidence_map`) or None per view, a
         list of the length of `views`."""
+        self.flush_pose_updates()                      # (pose refinement: what is pending belongs to the cameras registered so far)
         if np.isscalar(cam_confidences):
             cam_confidences = [float(cam_confidences)] * len(views)
         if confidence_maps is None:
@@ -491,7 +631,12 @@ class GSTrainer:
         name = "chkpnt_latest.pth" if latest else (f"chkpnt{iteration}.pth" if refine_epoch is None
                                                    else f"refine_{refine_epoch}_chkpnt{iteration}.pth")
         path = os.path.join(self._ckpt_dir(), name)
-        torch.save((self.gaussians.capture(), int(iteration)), path)
+        state = self.gaussians.capture()
+        if self.opt.pose_opt:
+            # refined poses and their Adam state, per registered camera (key absent with the option off: the file it always was).  What
+            # is pending in the gradient table is NOT applied here: saving must not change the run
+            state["camera_poses"] = self._pose_capture()
+        torch.save((state, int(iteration)), path)
         return path
 
     def load_checkpoint(self, checkpoint: str):
@@ -503,6 +648,8 @@ class GSTrainer:
         state, it = torch.load(checkpoint, map_location=self.gaussians._xyz.device, weights_only=True)
         self.gaussians.restore(state)
         self.iteration = int(it)
+        if "camera_poses" in state:                    # (written with `opt.pose_opt`; an older file has no such key and loads as before)
+            self._pose_restore(state["camera_poses"])
         self.reset_optimizers()
 
     def reset_gaussians_from_pcd(self, pcd, append_to_old_gaussians: bool = False):
@@ -563,7 +710,10 @@ class GSTrainer:
         """PSNR / SSIM of the current Gaussians over held-out (or the training) cameras, computed on the device
         (`train_ops.image_metrics`): the psnr / ssim columns of the per-scene record (SURVEY.md §8e;
         scripts/summarize_dl3dv.py:11-80 tabulates them).  LPIPS is reported when the trainer holds an `lpips` model
-        (weights supplied by the caller), NaN otherwise."""
+        (weights supplied by the caller), NaN otherwise.
+        The cameras are rendered at the poses THEY hold.  With `opt.pose_opt` the training cameras have moved and with them, slightly,
+        the frame the Gaussians live in; held-out test poses are NOT aligned to that refined frame (test-time pose alignment, as
+        pose-refining papers evaluate, is out of scope), so their metrics carry the residual misalignment."""
         cams = list(cams) if cams is not None else self.scene.getTrainCameras()
         ps, ss, ls = [], [], []
         with torch.no_grad():
@@ -771,8 +921,9 @@ class GSTrainer:
             self.filter_3d_computes += 1
         return g.filter_3D
 
-    def render_view(self, cam: Camera, scaling_modifier: float = 1.0):
-        """-> {'render' [3,H,W], 'depth' [1,H,W], 'alpha' [1,H,W], ...} (diffusionGS.py:154-172)."""
+    def render_view(self, cam: Camera, scaling_modifier: float = 1.0, _pose_row: Optional[int] = None):
+        """-> {'render' [3,H,W], 'depth' [1,H,W], 'alpha' [1,H,W], ...} (diffusionGS.py:154-172).
+        `_pose_row` (train_step alone, `opt.pose_opt`): the backward of this render ADDS its camera gradient to that row of the table."""
         g = self.gaussians
         f3 = self.ensure_filter_3D()
         st = GaussianRasterizationSettings(
@@ -781,6 +932,19 @@ class GSTrainer:
             viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform, sh_degree=g.active_sh_degree,
             campos=cam.camera_center, prefiltered=False, debug=False, antialiasing=bool(self.opt.antialiasing))
         means2D = torch.zeros_like(g.get_xyz, requires_grad=True)
+        if _pose_row is not None:
+            abs2D = None
+            if self.opt.densify_abs_grad:
+                abs2D = torch.zeros((g.get_xyz.shape[0], 2), dtype=torch.float32, device=g.get_xyz.device)
+            color, radii, depth, alpha = GaussianRasterizer(st)(g.get_xyz, means2D, g.get_opacity, shs=g.get_features,
+                                                                scales=g.get_scaling, rotations=g.get_rotation,
+                                                                confidence=g.confidence, filter_3D=f3, means2D_abs=abs2D,
+                                                                camera_grad=self._pose_table[_pose_row], camera_grad_accumulate=True)
+            out = {"render": color, "depth": depth, "alpha": alpha, "viewspace_points": means2D,
+                   "visibility_filter": radii > 0, "radii": radii}
+            if abs2D is not None:
+                out["viewspace_abs_grad"] = abs2D
+            return out
         if not self.opt.densify_abs_grad:
             color, radii, depth, alpha = GaussianRasterizer(st)(g.get_xyz, means2D, g.get_opacity, shs=g.get_features,
                                                                 scales=g.get_scaling, rotations=g.get_rotation,
@@ -852,7 +1016,15 @@ class GSTrainer:
                 d_loss, d_depth = depth_correlation_loss_step(depth, prior, self.opt.depth_weight, self.opt.depth_offset)
                 loss = loss + d_loss
             abs2D = None
-            if self.opt.densify_abs_grad:
+            pose_row = self._pose_row(cam)
+            if pose_row is not None:                 # the camera gradient of this step is ADDED to the camera's row: no host read here
+                if self.opt.densify_abs_grad:
+                    abs2D = torch.empty((g._xyz.shape[0], 2), dtype=torch.float32, device=g._xyz.device)
+                d_m3, d_m2, d_sh, d_lg, d_ls, d_rr, _ = rasterize_backward(rstate, d_color, d_depth, abs_grad_out=abs2D,
+                                                                           camera_grad_out=self._pose_table[pose_row],
+                                                                           camera_grad_accumulate=True)
+                self._pose_counts[pose_row] += 1
+            elif self.opt.densify_abs_grad:
                 abs2D = torch.empty((g._xyz.shape[0], 2), dtype=torch.float32, device=g._xyz.device)
                 d_m3, d_m2, d_sh, d_lg, d_ls, d_rr, _ = rasterize_backward(rstate, d_color, d_depth, abs_grad_out=abs2D)
             else:
@@ -896,7 +1068,8 @@ class GSTrainer:
                 raise ValueError("train_step(explicit=True) has no LPIPS term: the perceptual loss runs through autograd")
             loss, out = self._explicit_step(cam)
         else:
-            out = self.render_view(cam)
+            pose_row = self._pose_row(cam)
+            out = self.render_view(cam) if pose_row is None else self.render_view(cam, _pose_row=pose_row)
             wmap = getattr(cam, "confidence_map", None)
             if self.opt.lambda_dssim > 0.0:
                 loss = photometric_loss(out["render"], cam.original_image, self.opt.lambda_dssim, float(cam.cam_confidence),
@@ -913,6 +1086,8 @@ class GSTrainer:
                 loss = loss + depth_correlation_loss(out["depth"], prior, self.opt.depth_weight, self.opt.depth_offset)
             self.optimizer.zero_grad(set_to_none=True)
             loss.backward()
+            if pose_row is not None:
+                self._pose_counts[pose_row] += 1
         changed = False
         if self.densify:
             n0 = self.gaussians._xyz.shape[0]
@@ -923,6 +1098,9 @@ class GSTrainer:
             self.optimizer.step()
         self.iteration += 1
         self._f3d_age += 1                    # (ensure_filter_3D: steps since the filter was computed)
+        o = self.opt
+        if o.pose_opt and self.iteration >= int(o.pose_opt_from_iter) and self.iteration % max(int(o.pose_opt_interval), 1) == 0:
+            self.apply_pose_updates()         # (whether or not the density control changed the set: the gradient belongs to the camera)
         if self.opt.sh_degree_interval > 0 and self.iteration % self.opt.sh_degree_interval == 0:
             self.gaussians.oneupSHdegree()
         return loss.detach()

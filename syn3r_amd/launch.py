@@ -125,6 +125,19 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--densify_abs_grad_threshold", type=float, default=None,
                     help="OptimizationParams.densify_abs_grad_threshold (default: the trainer's own, 0.0008 - recalled, UNPINNED, "
                          "scene dependent)")
+    ap.add_argument("--pose_opt", type=int, default=0, choices=(0, 1),
+                    help="1: EXTENSION (not in the reference) - camera-pose refinement (OptimizationParams.pose_opt): the rasteriser also "
+                         "returns the gradient with respect to the camera and the trainer takes an Adam step on the poses of "
+                         "--pose_opt_cameras every --pose_opt_interval iterations; the first training camera stays fixed.  evaluate() "
+                         "does not align held-out poses to the refined frame.  0 (default): cameras never move")
+    ap.add_argument("--pose_opt_cameras", type=str, default=None, choices=("train", "pseudo", "all"),
+                    help="OptimizationParams.pose_opt_cameras: the input views, the diffusion pseudo-views, or both (default: the trainer's own, all)")
+    ap.add_argument("--pose_lr_rotation", type=float, default=None,
+                    help="OptimizationParams.pose_lr_rotation, radians (default: the trainer's own, 1e-3 - chosen, UNPINNED, scene dependent)")
+    ap.add_argument("--pose_lr_translation", type=float, default=None,
+                    help="OptimizationParams.pose_lr_translation, times the spatial scale (default: the trainer's own, 1e-3 - chosen, UNPINNED)")
+    ap.add_argument("--pose_opt_interval", type=int, default=None,
+                    help="OptimizationParams.pose_opt_interval: iterations between pose updates (default: the trainer's own, 10 - chosen, UNPINNED)")
     ap.add_argument("--num_inference_steps", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     # FSGS' parameter groups (scripts/train.py:44-46: -s, --eval, --n_views, --resolution, --use_dust3r ... of the batch scripts)
@@ -134,7 +147,9 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     # argparse takes `--percent_dens` for an abbreviation of `--percent_dense`: while that flag sat in FSGS_FLAGS the token was an
     # unknown argument, and a misspelling stays one
     declared = ["--" + f for f, _ in TRAINER_FLAGS] + ["--gs_schedule", "--pixel_confidence", "--antialiasing", "--filter_3d",
-                                                       "--densify_abs_grad", "--densify_abs_grad_threshold"]
+                                                       "--densify_abs_grad", "--densify_abs_grad_threshold", "--pose_opt",
+                                                       "--pose_opt_cameras", "--pose_lr_rotation", "--pose_lr_translation",
+                                                       "--pose_opt_interval"]
     # (a token that IS a declared flag is not an abbreviation of a longer one: --densify_abs_grad / --densify_abs_grad_threshold)
     cut = [t for t in given if t.startswith("--") and t.split("=")[0] not in declared
            and any(d.startswith(t.split("=")[0]) for d in declared)]
@@ -166,7 +181,8 @@ def apply_trainer_flags(opt, args):
     `--gs_schedule published` the switches of the three published optimiser rules: decay to --position_lr_final or 1.6e-6,
     spatial_lr_scale = None (the camera extent), feature_rest_lr_div = 20, sh_degree_interval = 1000.  Pure: no GPU, `opt`
     untouched.  `--antialiasing 1` sets `antialiasing`, `--filter_3d 1` sets `filter_3d`, `--densify_abs_grad 1` sets `densify_abs_grad`
-    (0, the default, leaves the field as `opt` has it); `--densify_abs_grad_threshold`, when given, sets its field.  (--sh_degree
+    (0, the default, leaves the field as `opt` has it); `--densify_abs_grad_threshold`, when given, sets its field.  `--pose_opt 1`
+    sets `pose_opt`; `--pose_opt_cameras`, `--pose_lr_rotation`, `--pose_lr_translation` and `--pose_opt_interval`, when given, set theirs.  (--sh_degree
     describes the model, not the optimiser: the scene factory reads it.)"""
     import dataclasses
     new = {}
@@ -186,6 +202,11 @@ def apply_trainer_flags(opt, args):
         new["densify_abs_grad"] = True
     if getattr(args, "densify_abs_grad_threshold", None) is not None:
         new["densify_abs_grad_threshold"] = float(args.densify_abs_grad_threshold)
+    if getattr(args, "pose_opt", 0):
+        new["pose_opt"] = True
+    for flag, typ in (("pose_opt_cameras", str), ("pose_lr_rotation", float), ("pose_lr_translation", float), ("pose_opt_interval", int)):
+        if getattr(args, flag, None) is not None:
+            new[flag] = typ(getattr(args, flag))
     return dataclasses.replace(opt, **new)
 
 

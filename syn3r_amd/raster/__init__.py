@@ -235,13 +235,18 @@ def rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, se
     return color, radii, depth, alpha, st
 
 
-def rasterize_backward(st: RasterState, g_color, g_depth=None, g_alpha=None, abs_grad_out: Optional[torch.Tensor] = None):
+def rasterize_backward(st: RasterState, g_color, g_depth=None, g_alpha=None, abs_grad_out: Optional[torch.Tensor] = None,
+                       camera_grad_out: Optional[torch.Tensor] = None, camera_grad_accumulate: bool = False):
     """Backward of both stages (`syn3r_raster_backward_f3d`, in the forward's mode and with the forward's `filter_3D`): (d_means3D, d_means2D, d_shs, d_opacities, d_scales, d_rotations,
     d_confidence or None) - with `raw_params` the gradients of the log-scales / raw quaternions / logits.
     `abs_grad_out` (default None: the call above): a contiguous [N,2] fp32 tensor on the state's device that
     `syn3r_raster_backward_abs` fills with AbsGS' absolute screen-space gradient, per Gaussian the sum over its pixels of the
     component-wise |d loss / d projected mean| in the units of d_means2D[:, :2] (zeros for culled Gaussians).  The returned tuple is
-    the same either way."""
+    the same either way.
+    `camera_grad_out` (EXTENSION, default None: the calls above): a contiguous [35] fp32 tensor on the state's device that
+    `syn3r_raster_backward_cam` fills with the gradient with respect to the camera - d loss / d viewmatrix [16], / d projmatrix [16],
+    / d campos [3], each in its tensor's storage order, the three taken as INDEPENDENT inputs (`syn3r_amd.gs.pose.tangent_from_raw`
+    turns them into the gradient of a pose); with `camera_grad_accumulate` it is ADDED to what the tensor holds.  Same tuple again."""
     radii, geom, binning, image = st.tensors[6:]
     if tuple(L.ptr(t) for t in st.tensors[:5]) != st.scene[3:8]:     # (`scene` holds the addresses the forward was given)
         raise L.Syn3rError("rasterize_backward: the state's tensors are not the ones rasterize_forward stored")
@@ -256,16 +261,24 @@ def rasterize_backward(st: RasterState, g_color, g_depth=None, g_alpha=None, abs
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
     d_m3, d_sc, d_ro, d_op, d_sh, d_m2 = new(N, 3), new(N, 3), new(N, 4), new(N), new(N, M, 3), new(N, 3)
     d_cf = new(N) if st.has_conf else None
-    ws = L.workspace(dev, lib.syn3r_raster_backward_workspace_bytes(N), "raster_bwd")
+    ws_bytes = (lib.syn3r_raster_backward_workspace_bytes if camera_grad_out is None else lib.syn3r_raster_backward_cam_workspace_bytes)(N)
+    ws = L.workspace(dev, ws_bytes, "raster_bwd")
     args = (*st.scene[:3], st.P, *st.scene[3:], st.bg, L.ptr(radii), L.ptr(geom), geom.numel(), st.plist, L.ptr(image), image.numel(),
             L.ptr(gc), L.ptr(gd), L.ptr(ga), L.ptr(d_m3), L.ptr(d_sc), L.ptr(d_ro), L.ptr(d_op), L.ptr(d_sh),
             L.ptr(d_m2), L.ptr(d_cf), L.ptr(ws), ws.numel(), int(st.raw_params), _flags(s), L.ptr(st.filter_3D))
-    if abs_grad_out is None:
-        L.check(lib.syn3r_raster_backward_f3d(*args, L.stream_ptr(dev)), "syn3r_raster_backward_f3d")
-    else:
+    if abs_grad_out is not None:
         if (abs_grad_out.device != dev or abs_grad_out.dtype != torch.float32 or tuple(abs_grad_out.shape) != (N, 2)
                 or not abs_grad_out.is_contiguous()):
             raise ValueError(f"rasterize_backward: abs_grad_out must be a contiguous [{N}, 2] float32 tensor on {dev}")
+    if camera_grad_out is not None:
+        if (camera_grad_out.device != dev or camera_grad_out.dtype != torch.float32 or tuple(camera_grad_out.shape) != (L.CAMERA_GRAD,)
+                or not camera_grad_out.is_contiguous()):
+            raise ValueError(f"rasterize_backward: camera_grad_out must be a contiguous [{L.CAMERA_GRAD}] float32 tensor on {dev}")
+        L.check(lib.syn3r_raster_backward_cam(*args, L.ptr(abs_grad_out), L.ptr(camera_grad_out), int(bool(camera_grad_accumulate)),
+                                              L.stream_ptr(dev)), "syn3r_raster_backward_cam")
+    elif abs_grad_out is None:
+        L.check(lib.syn3r_raster_backward_f3d(*args, L.stream_ptr(dev)), "syn3r_raster_backward_f3d")
+    else:
         L.check(lib.syn3r_raster_backward_abs(*args, L.ptr(abs_grad_out), L.stream_ptr(dev)), "syn3r_raster_backward_abs")
     return d_m3, d_m2, d_sh, d_op.reshape(st.opacity_shape), d_sc, d_ro, d_cf
 
@@ -275,10 +288,12 @@ class _Rasterize(torch.autograd.Function):
     debug_state = None
 
     @staticmethod
-    def forward(ctx, means3D, means2D, shs, opacities, scales, rotations, confidence, settings, filter_3D=None, means2D_abs=None):
+    def forward(ctx, means3D, means2D, shs, opacities, scales, rotations, confidence, settings, filter_3D=None, means2D_abs=None,
+                camera_grad=None, camera_grad_accumulate=False):
         color, radii, depth, alpha, st = rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, settings,
                                                            filter_3D=filter_3D)
         ctx.means2D_abs = means2D_abs        # a buffer the backward fills (`GaussianRasterizer.forward`), not an input of the render
+        ctx.camera_grad, ctx.camera_grad_accumulate = camera_grad, bool(camera_grad_accumulate)      # likewise
         ctx.save_for_backward(*st.tensors)
         st.tensors = None
         ctx.state = st
@@ -292,10 +307,17 @@ class _Rasterize(torch.autograd.Function):
         st = ctx.state
         st.tensors = ctx.saved_tensors
         try:
-            d_m3, d_m2, d_sh, d_op, d_sc, d_ro, d_cf = rasterize_backward(st, g_color, g_depth, g_alpha, abs_grad_out=ctx.means2D_abs)
+            if ctx.camera_grad is None:
+                d_m3, d_m2, d_sh, d_op, d_sc, d_ro, d_cf = rasterize_backward(st, g_color, g_depth, g_alpha, abs_grad_out=ctx.means2D_abs)
+            else:
+                d_m3, d_m2, d_sh, d_op, d_sc, d_ro, d_cf = rasterize_backward(
+                    st, g_color, g_depth, g_alpha, abs_grad_out=ctx.means2D_abs, camera_grad_out=ctx.camera_grad,
+                    camera_grad_accumulate=ctx.camera_grad_accumulate)
         finally:
             st.tensors = None
         grads = (d_m3, d_m2, d_sh, d_op, d_sc, d_ro, d_cf, None, None)
+        if ctx.camera_grad is not None:
+            return grads + (None, None, None)                             # (means2D_abs, camera_grad, camera_grad_accumulate)
         return grads if ctx.means2D_abs is None else grads + (None,)      # (one per argument `apply` was given)
 
 
@@ -306,8 +328,12 @@ class GaussianRasterizer(torch.nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, confidence: Optional[torch.Tensor] = None, filter_3D: Optional[torch.Tensor] = None,
-                means2D_abs: Optional[torch.Tensor] = None):
-        """`means2D_abs` (default None): an [N,2] fp32 buffer on the Gaussians' device that the autograd backward of this render
+                means2D_abs: Optional[torch.Tensor] = None, camera_grad: Optional[torch.Tensor] = None,
+                camera_grad_accumulate: bool = False):
+        """`camera_grad` (EXTENSION, default None): a [35] fp32 buffer on the Gaussians' device that the autograd backward of this
+        render fills with (or, with `camera_grad_accumulate`, adds to it) the gradient with respect to the camera
+        (`rasterize_backward(camera_grad_out=)`).  Handled like `means2D_abs`: data, not an input of the render.
+        `means2D_abs` (default None): an [N,2] fp32 buffer on the Gaussians' device that the autograd backward of this render
         FILLS with AbsGS' absolute screen-space gradient (`rasterize_backward(abs_grad_out=)`).  It is data: no gradient flows into
         it or out of it, and the render does not read it."""
         if (shs is None) == (colors_precomp is None):
@@ -318,10 +344,15 @@ class GaussianRasterizer(torch.nn.Module):
             raise Exception("Please provide scales and rotations")
         if filter_3D is not None:
             filter_3D = filter_3D.detach()       # data (Mip-Splatting's 3D smoothing filter, `rasterize_forward`): no gradient
+        if means2D_abs is not None and means2D_abs.requires_grad:
+            raise ValueError("GaussianRasterizer: means2D_abs is a buffer the backward fills, not a tensor that requires grad")
+        if camera_grad is not None:
+            if camera_grad.requires_grad:
+                raise ValueError("GaussianRasterizer: camera_grad is a buffer the backward fills, not a tensor that requires grad")
+            return _Rasterize.apply(means3D, means2D, shs, opacities, scales, rotations, confidence, self.raster_settings, filter_3D,
+                                    means2D_abs, camera_grad, bool(camera_grad_accumulate))
         if means2D_abs is None:
             return _Rasterize.apply(means3D, means2D, shs, opacities, scales, rotations, confidence, self.raster_settings, filter_3D)
-        if means2D_abs.requires_grad:
-            raise ValueError("GaussianRasterizer: means2D_abs is a buffer the backward fills, not a tensor that requires grad")
         return _Rasterize.apply(means3D, means2D, shs, opacities, scales, rotations, confidence, self.raster_settings, filter_3D,
                                 means2D_abs)
 
