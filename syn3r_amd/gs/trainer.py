@@ -451,7 +451,7 @@ class GSTrainer:
         self._f3d_cams, self._f3d_len, self._f3d_table, self._f3d_age = None, -1, None, 0
         # pose refinement (`opt.pose_opt`): the device table [C,35] of summed camera gradients, one row per registered camera, the
         # cameras of its rows (the list object and its members as they were when it was made) and the host count of steps per row
-        self._pose_table, self._pose_list, self._pose_cams, self._pose_counts = None, None, [], []
+        self._pose_drop()
         self.pose_updates = 0             # camera moves applied so far (apply_pose_updates)
         if self.opt.pose_opt_cameras not in ("train", "pseudo", "all"):
             raise ValueError(f"OptimizationParams.pose_opt_cameras must be 'train', 'pseudo' or 'all', got {self.opt.pose_opt_cameras!r}")
@@ -493,6 +493,10 @@ class GSTrainer:
         return None
 
     # ------------------------------------------------------------------ camera-pose refinement (EXTENSION, OptimizationParams.pose_opt)
+    def _pose_drop(self):
+        """No table (the state with the option off); `_pose_sync` makes a fresh one at the next step that wants a camera gradient."""
+        self._pose_table, self._pose_list, self._pose_cams, self._pose_counts = None, None, [], []
+
     def _pose_sync(self):
         """Keep the gradient table in step with `scene.train_cameras[1.0]`: when the list is another object or has another length
         (`update_cameras`, the orchestrator's restore) what is pending is applied to the cameras of the old rows and a fresh table is
@@ -561,7 +565,7 @@ class GSTrainer:
         if self._pose_table is None:
             return 0
         moved = self.apply_pose_updates()
-        self._pose_table, self._pose_list, self._pose_cams, self._pose_counts = None, None, [], []
+        self._pose_drop()
         return moved
 
     def _pose_capture(self) -> list:
@@ -589,8 +593,7 @@ class GSTrainer:
                 cams[i].pose_adam = {"m": e["m"].cpu().double().numpy().copy(), "v": e["v"].cpu().double().numpy().copy(), "t": int(e["t"])}
             elif hasattr(cams[i], "pose_adam"):
                 del cams[i].pose_adam
-        # gradients summed at the poses just replaced are dropped, not applied
-        self._pose_table, self._pose_list, self._pose_cams, self._pose_counts = None, None, [], []
+        self._pose_drop()                              # gradients summed at the poses just replaced are dropped, not applied
         self._f3d_table = None
 
     @property
@@ -882,10 +885,7 @@ class GSTrainer:
             return
         vis = out["visibility_filter"]
         vgrad = out["viewspace_grad"] if "viewspace_grad" in out else out["viewspace_points"].grad
-        if o.densify_abs_grad:
-            g.add_densification_stats(vgrad, vis, out["radii"], abs_grad=out["viewspace_abs_grad"])
-        else:
-            g.add_densification_stats(vgrad, vis, out["radii"])
+        g.add_densification_stats(vgrad, vis, out["radii"], abs_grad=out.get("viewspace_abs_grad") if o.densify_abs_grad else None)
         if it > o.densify_from_iter and it % o.densification_interval == 0:
             size = o.prune_screen_size if it > o.opacity_reset_interval else None
             self.densify_and_prune(o.densify_grad_threshold, o.prune_min_opacity, self.cameras_extent(), size)
@@ -921,43 +921,29 @@ class GSTrainer:
             self.filter_3d_computes += 1
         return g.filter_3D
 
+    def _raster_settings(self, cam: Camera, scale_modifier: float) -> GaussianRasterizationSettings:
+        return GaussianRasterizationSettings(
+            image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
+            tanfovy=math.tan(cam.FoVy * 0.5), bg=self.background, scale_modifier=scale_modifier,
+            viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform, sh_degree=self.gaussians.active_sh_degree,
+            campos=cam.camera_center, prefiltered=False, debug=False, antialiasing=bool(self.opt.antialiasing))
+
     def render_view(self, cam: Camera, scaling_modifier: float = 1.0, _pose_row: Optional[int] = None):
         """-> {'render' [3,H,W], 'depth' [1,H,W], 'alpha' [1,H,W], ...} (diffusionGS.py:154-172).
         `_pose_row` (train_step alone, `opt.pose_opt`): the backward of this render ADDS its camera gradient to that row of the table."""
         g = self.gaussians
         f3 = self.ensure_filter_3D()
-        st = GaussianRasterizationSettings(
-            image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
-            tanfovy=math.tan(cam.FoVy * 0.5), bg=self.background, scale_modifier=scaling_modifier,
-            viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform, sh_degree=g.active_sh_degree,
-            campos=cam.camera_center, prefiltered=False, debug=False, antialiasing=bool(self.opt.antialiasing))
         means2D = torch.zeros_like(g.get_xyz, requires_grad=True)
-        if _pose_row is not None:
-            abs2D = None
-            if self.opt.densify_abs_grad:
-                abs2D = torch.zeros((g.get_xyz.shape[0], 2), dtype=torch.float32, device=g.get_xyz.device)
-            color, radii, depth, alpha = GaussianRasterizer(st)(g.get_xyz, means2D, g.get_opacity, shs=g.get_features,
-                                                                scales=g.get_scaling, rotations=g.get_rotation,
-                                                                confidence=g.confidence, filter_3D=f3, means2D_abs=abs2D,
-                                                                camera_grad=self._pose_table[_pose_row], camera_grad_accumulate=True)
-            out = {"render": color, "depth": depth, "alpha": alpha, "viewspace_points": means2D,
-                   "visibility_filter": radii > 0, "radii": radii}
-            if abs2D is not None:
-                out["viewspace_abs_grad"] = abs2D
-            return out
-        if not self.opt.densify_abs_grad:
-            color, radii, depth, alpha = GaussianRasterizer(st)(g.get_xyz, means2D, g.get_opacity, shs=g.get_features,
-                                                                scales=g.get_scaling, rotations=g.get_rotation,
-                                                                confidence=g.confidence, filter_3D=f3)
-            return {"render": color, "depth": depth, "alpha": alpha, "viewspace_points": means2D,
-                    "visibility_filter": radii > 0, "radii": radii}
-        # AbsGS: the backward of this render fills the buffer (zeros until then, and for a render that is never differentiated)
-        abs2D = torch.zeros((g.get_xyz.shape[0], 2), dtype=torch.float32, device=g.get_xyz.device)
-        color, radii, depth, alpha = GaussianRasterizer(st)(g.get_xyz, means2D, g.get_opacity, shs=g.get_features,
-                                                            scales=g.get_scaling, rotations=g.get_rotation,
-                                                            confidence=g.confidence, filter_3D=f3, means2D_abs=abs2D)
-        return {"render": color, "depth": depth, "alpha": alpha, "viewspace_points": means2D,
-                "visibility_filter": radii > 0, "radii": radii, "viewspace_abs_grad": abs2D}
+        extra = {}
+        if self.opt.densify_abs_grad:
+            # AbsGS: the backward of this render fills the buffer (zeros until then, and for a render that is never differentiated)
+            extra["viewspace_abs_grad"] = torch.zeros((g.get_xyz.shape[0], 2), dtype=torch.float32, device=g.get_xyz.device)
+        color, radii, depth, alpha = GaussianRasterizer(self._raster_settings(cam, scaling_modifier))(
+            g.get_xyz, means2D, g.get_opacity, shs=g.get_features, scales=g.get_scaling, rotations=g.get_rotation,
+            confidence=g.confidence, filter_3D=f3, means2D_abs=extra.get("viewspace_abs_grad"),
+            camera_grad=None if _pose_row is None else self._pose_table[_pose_row], camera_grad_accumulate=True)
+        return {"render": color, "depth": depth, "alpha": alpha, "viewspace_points": means2D, "visibility_filter": radii > 0,
+                "radii": radii, **extra}
 
     def _pick_camera(self) -> Camera:
         pseudo = self.scene.getPseudoCameras()
@@ -998,14 +984,10 @@ class GSTrainer:
         prior = self._depth_term_prior(cam)
         f3 = self.ensure_filter_3D()
         with torch.no_grad():
-            st = GaussianRasterizationSettings(
-                image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
-                tanfovy=math.tan(cam.FoVy * 0.5), bg=self.background, scale_modifier=1.0,
-                viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform, sh_degree=g.active_sh_degree,
-                campos=cam.camera_center, prefiltered=False, debug=False, antialiasing=bool(self.opt.antialiasing))
             # log-scales / raw quaternions / logits in, THEIR gradients out (syn3r_raster_*_raw)
             color, radii, depth, alpha, rstate = rasterize_forward(g._xyz, g._features, g._opacity, g._scaling, g._rotation,
-                                                                   g.confidence, st, raw_params=True, filter_3D=f3)
+                                                                   g.confidence, self._raster_settings(cam, 1.0), raw_params=True,
+                                                                   filter_3D=f3)
             w, wmap = float(cam.cam_confidence), getattr(cam, "confidence_map", None)
             if self.opt.lambda_dssim > 0.0:
                 loss, _, d_color = photometric_loss_step(color, cam.original_image, self.opt.lambda_dssim, w, weight_map=wmap)
@@ -1015,25 +997,18 @@ class GSTrainer:
             if prior is not None:
                 d_loss, d_depth = depth_correlation_loss_step(depth, prior, self.opt.depth_weight, self.opt.depth_offset)
                 loss = loss + d_loss
-            abs2D = None
-            pose_row = self._pose_row(cam)
-            if pose_row is not None:                 # the camera gradient of this step is ADDED to the camera's row: no host read here
-                if self.opt.densify_abs_grad:
-                    abs2D = torch.empty((g._xyz.shape[0], 2), dtype=torch.float32, device=g._xyz.device)
-                d_m3, d_m2, d_sh, d_lg, d_ls, d_rr, _ = rasterize_backward(rstate, d_color, d_depth, abs_grad_out=abs2D,
-                                                                           camera_grad_out=self._pose_table[pose_row],
-                                                                           camera_grad_accumulate=True)
+            extra = {}
+            if self.opt.densify_abs_grad:             # (uninitialised: the backward writes every row)
+                extra["viewspace_abs_grad"] = torch.empty((g._xyz.shape[0], 2), dtype=torch.float32, device=g._xyz.device)
+            pose_row = self._pose_row(cam)            # the camera gradient of this step is ADDED to the camera's row: no host read here
+            d_m3, d_m2, d_sh, d_lg, d_ls, d_rr, _ = rasterize_backward(
+                rstate, d_color, d_depth, abs_grad_out=extra.get("viewspace_abs_grad"),
+                camera_grad_out=None if pose_row is None else self._pose_table[pose_row], camera_grad_accumulate=True)
+            if pose_row is not None:
                 self._pose_counts[pose_row] += 1
-            elif self.opt.densify_abs_grad:
-                abs2D = torch.empty((g._xyz.shape[0], 2), dtype=torch.float32, device=g._xyz.device)
-                d_m3, d_m2, d_sh, d_lg, d_ls, d_rr, _ = rasterize_backward(rstate, d_color, d_depth, abs_grad_out=abs2D)
-            else:
-                d_m3, d_m2, d_sh, d_lg, d_ls, d_rr, _ = rasterize_backward(rstate, d_color, d_depth)
             g._xyz.grad, g._features.grad, g._opacity.grad, g._scaling.grad, g._rotation.grad = d_m3, d_sh, d_lg.reshape(g._opacity.shape), d_ls, d_rr
         out = {"render": color, "depth": depth, "alpha": alpha, "viewspace_grad": d_m2, "visibility_filter": None,      # visible = radii > 0: add_densification_stats takes it from `radii` on the device
-               "radii": radii}
-        if abs2D is not None:
-            out["viewspace_abs_grad"] = abs2D
+               "radii": radii, **extra}
         return loss, out
 
     def _one(self, dev) -> torch.Tensor:
@@ -1069,7 +1044,7 @@ class GSTrainer:
             loss, out = self._explicit_step(cam)
         else:
             pose_row = self._pose_row(cam)
-            out = self.render_view(cam) if pose_row is None else self.render_view(cam, _pose_row=pose_row)
+            out = self.render_view(cam, _pose_row=pose_row)
             wmap = getattr(cam, "confidence_map", None)
             if self.opt.lambda_dssim > 0.0:
                 loss = photometric_loss(out["render"], cam.original_image, self.opt.lambda_dssim, float(cam.cam_confidence),
@@ -1166,6 +1141,12 @@ class GSTrainer:
             raster.set_pair_count_mode(prev)
         return float(last) if last is not None else 0.0     # ONE synchronisation, at the end of the loop
 
+    def _run(self, first_iter: int, iterations: Optional[int], disable_densification: bool) -> Tuple[int, float]:
+        """The common head of `training` and `finetune`: -> (the iteration the loop ran to, its last loss)"""
+        n = iterations if iterations is not None else self.opt.iterations
+        self.densify = not disable_densification
+        return n, self._loop(first_iter, n)
+
     def training(self, first_iter: int = 0, epoch_indicator: int = 0, iterations: Optional[int] = None,
                  disable_densification: bool = False):
         """HOT LOOP A (diffusionGS.py:139): `opt.iterations` optimisation steps with the published adaptive density
@@ -1173,9 +1154,7 @@ class GSTrainer:
         reset every `opacity_reset_interval`), then the checkpoints the orchestrator's refine_GS looks for
         (`chkpnt{N}.pth` for the configured checkpoint iterations, else `chkpnt_latest.pth`, diffusionGS.py:1620-1624)
         when `scene.model_path` is set."""
-        n = iterations if iterations is not None else self.opt.iterations
-        self.densify = not disable_densification
-        last = self._loop(first_iter, n)
+        n, last = self._run(first_iter, iterations, disable_densification)
         if self.scene.model_path:
             if n in self.checkpoint_iterations:
                 self.save_checkpoint(n)
@@ -1189,9 +1168,7 @@ class GSTrainer:
         `refine_{epoch}_chkpnt{N}.pth` (the file the next cycle's refine_GS reloads, :1611-1618)."""
         if pseudo_cam_sampling_rate is not None:
             self.opt.pseudo_cam_sampling_rate = pseudo_cam_sampling_rate
-        n = iterations if iterations is not None else self.opt.iterations
-        self.densify = not disable_densification
-        last = self._loop(first_iter, n)
+        n, last = self._run(first_iter, iterations, disable_densification)
         if self.scene.model_path:
             self.save_checkpoint(n, refine_epoch=refine_epoch)
         return last

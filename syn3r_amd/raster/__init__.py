@@ -133,17 +133,22 @@ def capacity_key(dev: torch.device, N: int, H: int, W: int):
 
 
 def _flags(s: GaussianRasterizationSettings) -> int:
-    """the `flags` of syn3r_raster_preprocess_ex / syn3r_raster_backward_ex for these settings"""
+    """the `flags` of syn3r_raster_preprocess_f3d / syn3r_raster_backward_f3d (and _abs, _cam) for these settings"""
     return L.RASTER_ANTIALIAS if s.antialiasing else 0
 
 
 class RasterState:
     """What `rasterize_forward` leaves for `rasterize_backward`: the (detached, contiguous fp32) inputs, the device state of the two
-    forward stages and the host-side constants.  `scene` is the argument prefix the projection and the backward entries share (N,
-    sh_degree, sh_coeffs, the six tensors of `tensors` by address, scale_modifier, the camera by value, H, W): built once, so the
-    backward cannot describe another scene than the forward did.  A plain object: the autograd Function stores its tensors through
-    `save_for_backward`, a caller that drives the two passes itself (`GSTrainer._explicit_step`) just keeps it."""
-    __slots__ = ("settings", "scene", "bg", "P", "plist", "has_conf", "opacity_shape", "raw_params", "tensors", "filter_3D")
+    forward stages and the host-side constants.  `scene` is the argument prefix of the projection entry (N, sh_degree, sh_coeffs (`M`),
+    the six input tensors by address, scale_modifier, the camera by value, H, W) and `bwd_scene` the same with `P` after `M`, the
+    prefix of the backward entries: both built once, so the backward cannot describe another scene than the forward did;
+    `addresses` are those of the five Gaussian tensors.  `tensors` holds the ten device tensors in the order of the names below,
+    which read it.  A plain object: the autograd Function stores `tensors` through `save_for_backward`, a caller that drives the two
+    passes itself (`GSTrainer._explicit_step`) just keeps it."""
+    __slots__ = ("settings", "N", "M", "H", "W", "scene", "bwd_scene", "addresses", "bg", "P", "plist", "has_conf", "opacity_shape",
+                 "raw_params", "tensors", "filter_3D")
+    means3D, scales, rotations, opacities, shs, confidence, radii, geom, binning, image = (
+        property(lambda st, i=i: st.tensors[i]) for i in range(10))
 
 
 def rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, settings: GaussianRasterizationSettings,
@@ -151,7 +156,7 @@ def rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, se
     """Both forward stages (`syn3r_raster_preprocess_f3d`, `syn3r_raster_render`); returns (color, radii, depth, alpha, state).
     `raw_params`: `scales`, `rotations`, `opacities` are the trainer's PARAMETERS (log-scales, unnormalised quaternions, logits);
     the published activations run inside the projection kernel and `rasterize_backward` returns the gradients of the parameters
-    (`syn3r_raster_backward_ex` with raw = 1).  `settings.antialiasing` goes to both passes as SYN3R_RASTER_ANTIALIAS: the state
+    (`syn3r_raster_backward_f3d` with raw = 1).  `settings.antialiasing` goes to both passes as SYN3R_RASTER_ANTIALIAS: the state
     keeps the settings, so `rasterize_backward` cannot be given another mode than the forward.
     `filter_3D` ([N] fp32, default None = the unfiltered render, bit for bit): Mip-Splatting's 3D smoothing filter
     (`train_ops.compute_filter_3D`), applied to the scales and the opacity inside the projection kernel; the state remembers it for
@@ -176,8 +181,10 @@ def rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, se
     if m3.shape != (N, 3) or sc.shape != (N, 3) or ro.shape != (N, 4) or op.shape != (N,) or sh.shape != (N, M, 3):
         raise ValueError("rasteriser: inconsistent Gaussian tensor shapes")
     bg = _host_floats(s.bg)
-    scene = (N, int(s.sh_degree), M, L.ptr(m3), L.ptr(sc), L.ptr(ro), L.ptr(op), L.ptr(sh), L.ptr(cf), float(s.scale_modifier),
-             _host_floats(s.viewmatrix), _host_floats(s.projmatrix), _host_floats(s.campos), float(s.tanfovx), float(s.tanfovy), H, W)
+    dims, addresses = (N, int(s.sh_degree), M), (L.ptr(m3), L.ptr(sc), L.ptr(ro), L.ptr(op), L.ptr(sh))
+    rest = (*addresses, L.ptr(cf), float(s.scale_modifier), _host_floats(s.viewmatrix), _host_floats(s.projmatrix),
+            _host_floats(s.campos), float(s.tanfovx), float(s.tanfovy), H, W)
+    scene = (*dims, *rest)
     stream = L.stream_ptr(dev)
 
     geom = torch.empty(lib.syn3r_raster_geom_bytes(N), dtype=torch.uint8, device=dev)
@@ -228,58 +235,58 @@ def rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, se
             depths=geom[256:256 + 4 * N].view(torch.float32).clone(),
         )
     st = RasterState()
-    st.settings, st.scene, st.bg, st.P, st.plist = s, scene, bg, P, plist.value
+    st.settings, st.scene, st.bwd_scene, st.addresses, st.bg, st.P, st.plist = s, scene, (*dims, P, *rest), addresses, bg, P, plist.value
+    st.N, st.M, st.H, st.W = N, M, H, W
     st.has_conf, st.opacity_shape, st.raw_params = cf is not None, opacities.shape, bool(raw_params)
     st.filter_3D = f3
     st.tensors = (m3, sc, ro, op, sh, cf if cf is not None else torch.empty(0, device=dev), radii, geom, binning, image)
     return color, radii, depth, alpha, st
 
 
+def _out_buffer(name: str, t: torch.Tensor, shape: tuple, dev: torch.device) -> int:
+    """the address of an output buffer of `rasterize_backward`: a contiguous fp32 tensor of `shape` on the state's device"""
+    if t.device != dev or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+        raise ValueError(f"rasterize_backward: {name} must be a contiguous {list(shape)} float32 tensor on {dev}")
+    return L.ptr(t)
+
+
 def rasterize_backward(st: RasterState, g_color, g_depth=None, g_alpha=None, abs_grad_out: Optional[torch.Tensor] = None,
                        camera_grad_out: Optional[torch.Tensor] = None, camera_grad_accumulate: bool = False):
-    """Backward of both stages (`syn3r_raster_backward_f3d`, in the forward's mode and with the forward's `filter_3D`): (d_means3D, d_means2D, d_shs, d_opacities, d_scales, d_rotations,
-    d_confidence or None) - with `raw_params` the gradients of the log-scales / raw quaternions / logits.
-    `abs_grad_out` (default None: the call above): a contiguous [N,2] fp32 tensor on the state's device that
-    `syn3r_raster_backward_abs` fills with AbsGS' absolute screen-space gradient, per Gaussian the sum over its pixels of the
-    component-wise |d loss / d projected mean| in the units of d_means2D[:, :2] (zeros for culled Gaussians).  The returned tuple is
-    the same either way.
-    `camera_grad_out` (EXTENSION, default None: the calls above): a contiguous [35] fp32 tensor on the state's device that
+    """Backward of both stages (`syn3r_raster_backward_f3d`, in the forward's mode and with the forward's `filter_3D`): (d_means3D,
+    d_means2D, d_shs, d_opacities, d_scales, d_rotations, d_confidence or None) - with `raw_params` the gradients of the log-scales /
+    raw quaternions / logits.  The entry is chosen HERE and nowhere else, from the two optional output buffers.
+    `abs_grad_out` (default None: that entry): a contiguous [N,2] fp32 tensor on the state's device that `syn3r_raster_backward_abs`
+    fills with AbsGS' absolute screen-space gradient, per Gaussian the sum over its pixels of the component-wise |d loss / d projected
+    mean| in the units of d_means2D[:, :2] (zeros for culled Gaussians).  The returned tuple is the same either way.
+    `camera_grad_out` (EXTENSION, default None: one of the two entries above): a contiguous [35] fp32 tensor on the state's device that
     `syn3r_raster_backward_cam` fills with the gradient with respect to the camera - d loss / d viewmatrix [16], / d projmatrix [16],
     / d campos [3], each in its tensor's storage order, the three taken as INDEPENDENT inputs (`syn3r_amd.gs.pose.tangent_from_raw`
     turns them into the gradient of a pose); with `camera_grad_accumulate` it is ADDED to what the tensor holds.  Same tuple again."""
-    radii, geom, binning, image = st.tensors[6:]
-    if tuple(L.ptr(t) for t in st.tensors[:5]) != st.scene[3:8]:     # (`scene` holds the addresses the forward was given)
+    if (L.ptr(st.means3D), L.ptr(st.scales), L.ptr(st.rotations), L.ptr(st.opacities), L.ptr(st.shs)) != st.addresses:
         raise L.Syn3rError("rasterize_backward: the state's tensors are not the ones rasterize_forward stored")
-    s = st.settings
     lib = L.load()
-    dev = radii.device
-    N, _, M = st.scene[:3]
-    H, W = st.scene[-2:]
-    gc = g_color.detach().to(torch.float32).contiguous() if g_color is not None else torch.zeros((3, H, W), device=dev)
+    radii, geom, image = st.radii, st.geom, st.image
+    dev, N, M = radii.device, st.N, st.M
+    # the entry and what it takes after the common arguments; with neither buffer the call is the one made before they existed
+    entry, ws_bytes, extra = "syn3r_raster_backward_f3d", lib.syn3r_raster_backward_workspace_bytes, ()
+    if abs_grad_out is not None:
+        entry, extra = "syn3r_raster_backward_abs", (_out_buffer("abs_grad_out", abs_grad_out, (N, 2), dev),)
+    if camera_grad_out is not None:
+        entry, ws_bytes = "syn3r_raster_backward_cam", lib.syn3r_raster_backward_cam_workspace_bytes
+        extra = (L.ptr(abs_grad_out), _out_buffer("camera_grad_out", camera_grad_out, (L.CAMERA_GRAD,), dev),
+                 int(bool(camera_grad_accumulate)))
+    gc = g_color.detach().to(torch.float32).contiguous() if g_color is not None else torch.zeros((3, st.H, st.W), device=dev)
     gd = g_depth.detach().to(torch.float32).contiguous() if g_depth is not None else None
     ga = g_alpha.detach().to(torch.float32).contiguous() if g_alpha is not None else None
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
     d_m3, d_sc, d_ro, d_op, d_sh, d_m2 = new(N, 3), new(N, 3), new(N, 4), new(N), new(N, M, 3), new(N, 3)
     d_cf = new(N) if st.has_conf else None
-    ws_bytes = (lib.syn3r_raster_backward_workspace_bytes if camera_grad_out is None else lib.syn3r_raster_backward_cam_workspace_bytes)(N)
-    ws = L.workspace(dev, ws_bytes, "raster_bwd")
-    args = (*st.scene[:3], st.P, *st.scene[3:], st.bg, L.ptr(radii), L.ptr(geom), geom.numel(), st.plist, L.ptr(image), image.numel(),
-            L.ptr(gc), L.ptr(gd), L.ptr(ga), L.ptr(d_m3), L.ptr(d_sc), L.ptr(d_ro), L.ptr(d_op), L.ptr(d_sh),
-            L.ptr(d_m2), L.ptr(d_cf), L.ptr(ws), ws.numel(), int(st.raw_params), _flags(s), L.ptr(st.filter_3D))
-    if abs_grad_out is not None:
-        if (abs_grad_out.device != dev or abs_grad_out.dtype != torch.float32 or tuple(abs_grad_out.shape) != (N, 2)
-                or not abs_grad_out.is_contiguous()):
-            raise ValueError(f"rasterize_backward: abs_grad_out must be a contiguous [{N}, 2] float32 tensor on {dev}")
-    if camera_grad_out is not None:
-        if (camera_grad_out.device != dev or camera_grad_out.dtype != torch.float32 or tuple(camera_grad_out.shape) != (L.CAMERA_GRAD,)
-                or not camera_grad_out.is_contiguous()):
-            raise ValueError(f"rasterize_backward: camera_grad_out must be a contiguous [{L.CAMERA_GRAD}] float32 tensor on {dev}")
-        L.check(lib.syn3r_raster_backward_cam(*args, L.ptr(abs_grad_out), L.ptr(camera_grad_out), int(bool(camera_grad_accumulate)),
-                                              L.stream_ptr(dev)), "syn3r_raster_backward_cam")
-    elif abs_grad_out is None:
-        L.check(lib.syn3r_raster_backward_f3d(*args, L.stream_ptr(dev)), "syn3r_raster_backward_f3d")
-    else:
-        L.check(lib.syn3r_raster_backward_abs(*args, L.ptr(abs_grad_out), L.stream_ptr(dev)), "syn3r_raster_backward_abs")
+    ws = L.workspace(dev, ws_bytes(N), "raster_bwd")
+    rc = getattr(lib, entry)(*st.bwd_scene, st.bg, L.ptr(radii), L.ptr(geom), geom.numel(), st.plist, L.ptr(image), image.numel(),
+                             L.ptr(gc), L.ptr(gd), L.ptr(ga), L.ptr(d_m3), L.ptr(d_sc), L.ptr(d_ro), L.ptr(d_op), L.ptr(d_sh),
+                             L.ptr(d_m2), L.ptr(d_cf), L.ptr(ws), ws.numel(), int(st.raw_params), _flags(st.settings),
+                             L.ptr(st.filter_3D), *extra, L.stream_ptr(dev))
+    L.check(rc, entry)
     return d_m3, d_m2, d_sh, d_op.reshape(st.opacity_shape), d_sc, d_ro, d_cf
 
 
@@ -288,8 +295,8 @@ class _Rasterize(torch.autograd.Function):
     debug_state = None
 
     @staticmethod
-    def forward(ctx, means3D, means2D, shs, opacities, scales, rotations, confidence, settings, filter_3D=None, means2D_abs=None,
-                camera_grad=None, camera_grad_accumulate=False):
+    def forward(ctx, means3D, means2D, shs, opacities, scales, rotations, confidence, settings, filter_3D, means2D_abs, camera_grad,
+                camera_grad_accumulate):
         color, radii, depth, alpha, st = rasterize_forward(means3D, shs, opacities, scales, rotations, confidence, settings,
                                                            filter_3D=filter_3D)
         ctx.means2D_abs = means2D_abs        # a buffer the backward fills (`GaussianRasterizer.forward`), not an input of the render
@@ -307,18 +314,13 @@ class _Rasterize(torch.autograd.Function):
         st = ctx.state
         st.tensors = ctx.saved_tensors
         try:
-            if ctx.camera_grad is None:
-                d_m3, d_m2, d_sh, d_op, d_sc, d_ro, d_cf = rasterize_backward(st, g_color, g_depth, g_alpha, abs_grad_out=ctx.means2D_abs)
-            else:
-                d_m3, d_m2, d_sh, d_op, d_sc, d_ro, d_cf = rasterize_backward(
-                    st, g_color, g_depth, g_alpha, abs_grad_out=ctx.means2D_abs, camera_grad_out=ctx.camera_grad,
-                    camera_grad_accumulate=ctx.camera_grad_accumulate)
+            d_m3, d_m2, d_sh, d_op, d_sc, d_ro, d_cf = rasterize_backward(
+                st, g_color, g_depth, g_alpha, abs_grad_out=ctx.means2D_abs, camera_grad_out=ctx.camera_grad,
+                camera_grad_accumulate=ctx.camera_grad_accumulate)
         finally:
             st.tensors = None
-        grads = (d_m3, d_m2, d_sh, d_op, d_sc, d_ro, d_cf, None, None)
-        if ctx.camera_grad is not None:
-            return grads + (None, None, None)                             # (means2D_abs, camera_grad, camera_grad_accumulate)
-        return grads if ctx.means2D_abs is None else grads + (None,)      # (one per argument `apply` was given)
+        # one per argument of `forward`: settings, filter_3D, means2D_abs, camera_grad and camera_grad_accumulate have no gradient
+        return d_m3, d_m2, d_sh, d_op, d_sc, d_ro, d_cf, None, None, None, None, None
 
 
 class GaussianRasterizer(torch.nn.Module):
@@ -346,15 +348,10 @@ class GaussianRasterizer(torch.nn.Module):
             filter_3D = filter_3D.detach()       # data (Mip-Splatting's 3D smoothing filter, `rasterize_forward`): no gradient
         if means2D_abs is not None and means2D_abs.requires_grad:
             raise ValueError("GaussianRasterizer: means2D_abs is a buffer the backward fills, not a tensor that requires grad")
-        if camera_grad is not None:
-            if camera_grad.requires_grad:
-                raise ValueError("GaussianRasterizer: camera_grad is a buffer the backward fills, not a tensor that requires grad")
-            return _Rasterize.apply(means3D, means2D, shs, opacities, scales, rotations, confidence, self.raster_settings, filter_3D,
-                                    means2D_abs, camera_grad, bool(camera_grad_accumulate))
-        if means2D_abs is None:
-            return _Rasterize.apply(means3D, means2D, shs, opacities, scales, rotations, confidence, self.raster_settings, filter_3D)
+        if camera_grad is not None and camera_grad.requires_grad:
+            raise ValueError("GaussianRasterizer: camera_grad is a buffer the backward fills, not a tensor that requires grad")
         return _Rasterize.apply(means3D, means2D, shs, opacities, scales, rotations, confidence, self.raster_settings, filter_3D,
-                                means2D_abs)
+                                means2D_abs, camera_grad, bool(camera_grad_accumulate))
 
 
 def sort_pairs(keys: torch.Tensor, vals: torch.Tensor, nbits: int = 64):

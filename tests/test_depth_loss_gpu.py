@@ -289,9 +289,9 @@ def test_default_leaves_the_step_unchanged(gpu, monkeypatch):
     seen = []
     real_bwd = raster.rasterize_backward
 
-    def spy(st, g_color, g_depth=None, g_alpha=None):
+    def spy(st, g_color, g_depth=None, g_alpha=None, **kw):
         seen.append((g_color.clone(), None if g_depth is None else g_depth.clone()))
-        return real_bwd(st, g_color, g_depth, g_alpha)
+        return real_bwd(st, g_color, g_depth, g_alpha, **kw)
     monkeypatch.setattr(raster, "rasterize_backward", spy)
     N, H, W = 2000, 48, 64
     target = torch.rand(3, H, W, generator=torch.Generator().manual_seed(2))

@@ -328,9 +328,9 @@ def test_split_decision_on_the_abs_statistic(gpu):
 
 def test_option_off_is_the_old_call_path(gpu, monkeypatch):
     """Option off: a 20-step run with density control on ends with parameters bit-equal to the same run, same seed, made through
-    the pre-existing call path - `rasterize_backward` and `add_densification_stats` behind wrappers with the signatures they had
-    before the option existed (an `abs_grad_out` / `abs_grad` argument would be a TypeError there), the backward wrapper calling
-    syn3r_raster_backward_f3d itself.  The loss is the L1 term under a `confidence_map` that is non-zero on one half-tile, so that
+    the pre-existing call path - `rasterize_backward` and `add_densification_stats` behind wrappers that do what they did before the
+    option existed (an `abs_grad_out` / `camera_grad_out` / `abs_grad` argument that is not None fails their assertion), the backward
+    wrapper calling syn3r_raster_backward_f3d itself.  The loss is the L1 term under a `confidence_map` that is non-zero on one half-tile, so that
     the gradients are the same bits in every launch (tests/test_raster_aa_gpu.py's module docstring)."""
     from syn3r_amd import _lib as L
     from syn3r_amd import raster
@@ -339,7 +339,8 @@ def test_option_off_is_the_old_call_path(gpu, monkeypatch):
     w2c = np.eye(4, dtype=np.float32)
     calls = {"bwd": 0, "stats": 0}
 
-    def old_backward(st, g_color, g_depth=None, g_alpha=None):
+    def old_backward(st, g_color, g_depth=None, g_alpha=None, **kw):
+        assert kw.get("abs_grad_out") is None and kw.get("camera_grad_out") is None      # option off: no buffer is ever handed over
         calls["bwd"] += 1
         radii, geom, binning, image = st.tensors[6:]
         lib, dev = L.load(), radii.device
@@ -360,7 +361,8 @@ def test_option_off_is_the_old_call_path(gpu, monkeypatch):
 
     new_stats = GaussianModel.add_densification_stats
 
-    def old_stats(self, viewspace_grad, update_filter, radii=None):
+    def old_stats(self, viewspace_grad, update_filter, radii=None, abs_grad=None):
+        assert abs_grad is None
         calls["stats"] += 1
         return new_stats(self, viewspace_grad, update_filter, radii)
 
