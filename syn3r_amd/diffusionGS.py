@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import orchestrator as O
-from .gs.trainer import Camera
+from .gs.camera import Camera
 from .pipeline.svd_2pass import StableVideoDiffusionPipeline
 from .schedulers.scheduling_euler_discrete import SVD_XT_SCHEDULER_CONFIG, EulerDiscreteScheduler
 

@@ -2,8 +2,8 @@
 
 The rasteriser returns the gradient of the loss with respect to its three camera inputs taken as INDEPENDENT
 (`rasterize_backward(camera_grad_out=)`, syn3r_raster_backward_cam: view[16], proj[16], campos[3] in storage order).  This module
-turns those 35 numbers into the gradient of a 6-vector on the pose and applies an Adam step to it.  All of it is float64 numpy: a
-few dozen flops per camera and update.
+turns those 35 numbers into the gradient of a 6-vector on the pose and applies an Adam step to it.  The maths is float64 numpy: a
+few dozen flops per camera and update.  `PoseTable` is what the trainer holds: the device table the rasteriser sums into.
 
 Convention: world-to-camera M = [R | t] (4 x 4, bottom row 0 0 0 1), twist xi = (rho, phi) with the TRANSLATION FIRST, LEFT
 perturbation M' = Exp(xi) M.  A `Camera` stores R as camera-to-world (R_c2w = R^T) and T = t, the published 3DGS convention.
@@ -13,6 +13,9 @@ from __future__ import annotations
 from typing import Optional, Tuple
 
 import numpy as np
+import torch
+
+from .. import _lib as L
 
 _SMALL = 1e-4        # below it the series of the three coefficients (relative error ~ theta^4 / 20160 and smaller: < 1e-20)
 
@@ -117,3 +120,121 @@ class PoseOptimizer:
         out = np.eye(4, dtype=np.float64)
         out[:3, :3], out[:3, 3] = R, M[:3, 3]
         return out
+
+
+class PoseTable:
+    """The trainer's side of `OptimizationParams.pose_opt`: the device table [C,35] of summed camera gradients, one row per registered
+    camera, the cameras of its rows (the list object and its members as they were when it was made) and the host count of steps per
+    row.  It reads the trainer's `opt`, `scene`, `iteration`, `gaussians` (for the device) and `spatial_lr_scale` when it needs them,
+    and tells the trainer's 3D-filter cache (`filter3d.invalidate_cameras`) when cameras have moved."""
+
+    def __init__(self, trainer):
+        self.trainer = trainer
+        self.updates = 0                  # camera moves applied so far (`apply`)
+        self.drop()
+
+    def drop(self):
+        """No table (the state with the option off); `sync` makes a fresh one at the next step that wants a camera gradient."""
+        self.table, self.list, self.cams, self.counts = None, None, [], []
+
+    def sync(self):
+        """Keep the gradient table in step with `scene.train_cameras[1.0]`: when the list is another object or has another length
+        (`update_cameras`, the orchestrator's restore) what is pending is applied to the cameras of the old rows and a fresh table is
+        made.  The Adam state lives on the camera objects, so it survives."""
+        cams = self.trainer.scene.train_cameras[1.0]
+        if self.table is not None and self.list is cams and len(self.cams) == len(cams):
+            return
+        if self.table is not None:
+            self.apply()
+        dev = self.trainer.gaussians._xyz.device
+        self.list, self.cams, self.counts = cams, list(cams), [0] * len(cams)
+        self.table = torch.zeros((max(len(cams), 1), L.CAMERA_GRAD), dtype=torch.float32, device=dev)
+
+    def row(self, cam) -> Optional[int]:
+        """The table row of `cam` if this step's camera gradient is wanted, else None: the option on and started, the camera registered,
+        of the chosen kind, and not the first training camera (the gauge: without a fixed camera the world frame drifts)."""
+        o = self.trainer.opt
+        if not o.pose_opt or self.trainer.iteration < int(o.pose_opt_from_iter):
+            return None
+        self.sync()
+        row = next((i for i, c in enumerate(self.cams) if c is cam), None)
+        if row is None:
+            return None
+        pseudo = bool(getattr(cam, "is_pseudo", False))
+        if (pseudo and o.pose_opt_cameras == "train") or (not pseudo and o.pose_opt_cameras == "pseudo"):
+            return None
+        train = self.trainer.scene.getTrainCameras()
+        if train and train[0] is cam:
+            return None
+        return row
+
+    def count(self, row: Optional[int]):
+        """One more step's camera gradient has been ADDED to `row` (None: this step wanted none)."""
+        if row is not None:
+            self.counts[row] += 1
+
+    def apply(self) -> int:
+        """ONE host read of the table; every camera with a non-zero count: mean raw gradient -> `tangent_from_raw` -> one Adam step
+        (`PoseOptimizer`, state on the camera object) -> `Camera.set_pose`.  Then the table and the counts restart and the 3D
+        filter's camera table is dropped (`ensure_filter_3D` rebuilds it from the moved poses).  Returns the number of cameras moved.
+        Independent of the density control: the camera gradient belongs to the camera, whatever happened to the Gaussians."""
+        if self.table is None or not any(self.counts):
+            return 0
+        host = self.table.detach().cpu().double().numpy()
+        o = self.trainer.opt
+        popt, moved = PoseOptimizer(lr_rotation=float(o.pose_lr_rotation),
+                                    lr_translation=float(o.pose_lr_translation) * float(self.trainer.spatial_lr_scale)), 0
+        for row, (cam, n) in enumerate(zip(self.cams, self.counts)):
+            if n == 0:
+                continue
+            grad = tangent_from_raw(host[row] / float(n), cam)
+            if not np.all(np.isfinite(grad)):
+                continue                                   # (a degenerate render: leave the camera where it is)
+            state = getattr(cam, "pose_adam", None)
+            if state is None:
+                state = cam.pose_adam = popt.new_state()
+            M = popt.update(camera_w2c(cam), state, grad)
+            cam.set_pose(M[:3, :3].T, M[:3, 3])
+            moved += 1
+        self.table.zero_()
+        self.counts = [0] * len(self.counts)
+        self.trainer.filter3d.invalidate_cameras()
+        self.updates += moved
+        return moved
+
+    def flush(self) -> int:
+        """Apply what is pending and start a fresh table at the next step (`update_cameras`, `reset_gs`, the orchestrator's restore of
+        the camera list).  Nothing with the option off."""
+        if self.table is None:
+            return 0
+        moved = self.apply()
+        self.drop()
+        return moved
+
+    def capture(self) -> list:
+        """Per registered camera: index, kind, R, T and the Adam state, as tensors (the checkpoint loader reads tensors only)."""
+        out = []
+        for i, cam in enumerate(self.trainer.scene.train_cameras[1.0]):
+            st = getattr(cam, "pose_adam", None)
+            e = {"index": i, "is_pseudo": int(bool(getattr(cam, "is_pseudo", False))), "R": torch.from_numpy(np.array(cam.R, np.float32)),
+                 "T": torch.from_numpy(np.array(cam.T, np.float32))}
+            if st is not None:
+                e.update(m=torch.from_numpy(np.array(st["m"], np.float64)), v=torch.from_numpy(np.array(st["v"], np.float64)), t=int(st["t"]))
+            out.append(e)
+        return out
+
+    def restore(self, entries: list):
+        """Entry i goes to registered camera i when there is one of the same kind (a checkpoint written with pseudo-views registered
+        may be loaded after the list was restored: their entries are skipped)."""
+        cams = self.trainer.scene.train_cameras[1.0]
+        for e in entries:
+            i = int(e["index"])
+            if i >= len(cams) or int(bool(getattr(cams[i], "is_pseudo", False))) != int(e["is_pseudo"]):
+                continue
+            cams[i].set_pose(e["R"].cpu().numpy(), e["T"].cpu().numpy())
+            if "m" in e:
+                cams[i].pose_adam = {"m": e["m"].cpu().double().numpy().copy(), "v": e["v"].cpu().double().numpy().copy(), "t": int(e["t"])}
+            elif hasattr(cams[i], "pose_adam"):
+                del cams[i].pose_adam
+        self.drop()                                    # gradients summed at the poses just replaced are dropped, not applied
+        self.trainer.filter3d.invalidate_cameras()

@@ -30,6 +30,14 @@ def _map_arg(who: str, weight_map: Optional[torch.Tensor], image: torch.Tensor) 
     return m.contiguous()
 
 
+def _l1_entries(lib, wm: Optional[torch.Tensor]):
+    """The ONE place that knows the L1 loss has `_map` entries: -> (forward entry, backward entry, their name for `L.check`, and
+    what a map adds to their argument lists: its pointer after `target`, its length after `n`; two empty tuples without one)"""
+    if wm is None:
+        return lib.syn3r_l1_loss, lib.syn3r_l1_loss_backward, "l1_loss", (), ()
+    return lib.syn3r_l1_loss_map, lib.syn3r_l1_loss_map_backward, "l1_loss_map", (L.ptr(wm),), (wm.numel(),)
+
+
 def _l1_forward(image: torch.Tensor, target: torch.Tensor, weight: float, weight_map: Optional[torch.Tensor] = None):
     L.require_gpu(image, target)
     if image.shape != target.shape or image.dtype != torch.float32 or target.dtype != torch.float32:
@@ -40,24 +48,18 @@ def _l1_forward(image: torch.Tensor, target: torch.Tensor, weight: float, weight
     n = image.numel()
     loss = torch.empty((), dtype=torch.float32, device=image.device)
     ws = L.workspace(image.device, lib.syn3r_l1_loss_workspace_bytes(n), "l1")
-    if wm is None:
-        L.check(lib.syn3r_l1_loss(L.ptr(image), L.ptr(target), n, float(weight), L.ptr(loss), L.ptr(ws), ws.numel(),
-                                  L.stream_ptr(image.device)), "l1_loss")
-    else:
-        L.check(lib.syn3r_l1_loss_map(L.ptr(image), L.ptr(target), L.ptr(wm), n, wm.numel(), float(weight), L.ptr(loss), L.ptr(ws),
-                                      ws.numel(), L.stream_ptr(image.device)), "l1_loss_map")
+    forward, _, name, map_ptr, map_len = _l1_entries(lib, wm)
+    L.check(forward(L.ptr(image), L.ptr(target), *map_ptr, n, *map_len, float(weight), L.ptr(loss), L.ptr(ws), ws.numel(),
+                    L.stream_ptr(image.device)), name)
     return loss, image, target, wm
 
 
 def _l1_backward(image: torch.Tensor, target: torch.Tensor, weight: float, grad_loss, wm: Optional[torch.Tensor] = None):
     go = grad_loss.to(torch.float32).contiguous() if grad_loss is not None else None      # device scalar; None = 1
     grad = torch.empty_like(image)
-    if wm is None:
-        L.check(L.load().syn3r_l1_loss_backward(L.ptr(image), L.ptr(target), image.numel(), float(weight), L.ptr(go),
-                                                L.ptr(grad), L.stream_ptr(image.device)), "l1_loss_backward")
-    else:
-        L.check(L.load().syn3r_l1_loss_map_backward(L.ptr(image), L.ptr(target), L.ptr(wm), image.numel(), wm.numel(), float(weight),
-                                                    L.ptr(go), L.ptr(grad), L.stream_ptr(image.device)), "l1_loss_map_backward")
+    _, backward, name, map_ptr, map_len = _l1_entries(L.load(), wm)
+    L.check(backward(L.ptr(image), L.ptr(target), *map_ptr, image.numel(), *map_len, float(weight), L.ptr(go), L.ptr(grad),
+                     L.stream_ptr(image.device)), name + "_backward")
     return grad
 
 
@@ -100,6 +102,17 @@ def _photo_args(who: str, image: torch.Tensor, target: torch.Tensor, weight_map:
     return dev, _map_arg(who, weight_map, image)
 
 
+def _photo_entries(lib, wm: Optional[torch.Tensor]):
+    """The ONE place that knows the photometric loss has `_map` entries: -> (forward, backward and step entry, the workspace-size
+    function, the length of `parts` (3: [loss, L1, SSIM]; 4 with a map: + mean(m)), their name for `L.check`, and what a map adds to
+    their argument lists: its pointer after `target`; an empty tuple without one)"""
+    if wm is None:
+        return (lib.syn3r_photo_loss, lib.syn3r_photo_loss_backward, lib.syn3r_photo_loss_step, lib.syn3r_photo_loss_workspace_bytes,
+                3, "photo_loss", ())
+    return (lib.syn3r_photo_loss_map, lib.syn3r_photo_loss_map_backward, lib.syn3r_photo_loss_map_step,
+            lib.syn3r_photo_loss_map_workspace_bytes, 4, "photo_loss_map", (L.ptr(wm),))
+
+
 class _PhotoLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image: torch.Tensor, target: torch.Tensor, lambda_dssim: float, weight: float,
@@ -108,17 +121,12 @@ class _PhotoLoss(torch.autograd.Function):
         image, target = image.contiguous(), target.contiguous()
         lib = L.load()
         C_, H_, W_ = image.shape
+        forward, _, _, workspace_bytes, n_parts, name, map_ptr = _photo_entries(lib, wm)
         # own buffer, not the shared workspace cache: the derivative maps must survive until backward
-        if wm is None:
-            ws = torch.empty(lib.syn3r_photo_loss_workspace_bytes(C_, H_, W_), dtype=torch.uint8, device=image.device)
-            out = torch.empty(3, dtype=torch.float32, device=image.device)
-            L.check(lib.syn3r_photo_loss(L.ptr(image), L.ptr(target), C_, H_, W_, float(lambda_dssim), float(weight),
-                                         L.ptr(out), L.ptr(ws), ws.numel(), L.stream_ptr(image.device)), "photo_loss")
-        else:
-            ws = torch.empty(lib.syn3r_photo_loss_map_workspace_bytes(C_, H_, W_), dtype=torch.uint8, device=image.device)
-            out = torch.empty(4, dtype=torch.float32, device=image.device)
-            L.check(lib.syn3r_photo_loss_map(L.ptr(image), L.ptr(target), L.ptr(wm), C_, H_, W_, float(lambda_dssim), float(weight),
-                                             L.ptr(out), L.ptr(ws), ws.numel(), L.stream_ptr(image.device)), "photo_loss_map")
+        ws = torch.empty(workspace_bytes(C_, H_, W_), dtype=torch.uint8, device=image.device)
+        out = torch.empty(n_parts, dtype=torch.float32, device=image.device)
+        L.check(forward(L.ptr(image), L.ptr(target), *map_ptr, C_, H_, W_, float(lambda_dssim), float(weight), L.ptr(out), L.ptr(ws),
+                        ws.numel(), L.stream_ptr(image.device)), name)
         ctx.save_for_backward(image, target, ws)
         ctx.args = (float(lambda_dssim), float(weight))
         ctx.wm = wm                                   # data without a gradient: kept beside the saved tensors
@@ -134,14 +142,9 @@ class _PhotoLoss(torch.autograd.Function):
         C_, H_, W_ = image.shape
         go = grad_loss.to(torch.float32).contiguous()
         grad = torch.empty_like(image)
-        if ctx.wm is None:
-            L.check(L.load().syn3r_photo_loss_backward(L.ptr(image), L.ptr(target), C_, H_, W_, lam, weight, L.ptr(go),
-                                                       L.ptr(ws), L.ptr(grad), L.stream_ptr(image.device)),
-                    "photo_loss_backward")
-        else:
-            L.check(L.load().syn3r_photo_loss_map_backward(L.ptr(image), L.ptr(target), L.ptr(ctx.wm), C_, H_, W_, lam, weight,
-                                                           L.ptr(go), L.ptr(ws), L.ptr(grad), L.stream_ptr(image.device)),
-                    "photo_loss_map_backward")
+        _, backward, _, _, _, name, map_ptr = _photo_entries(L.load(), ctx.wm)
+        L.check(backward(L.ptr(image), L.ptr(target), *map_ptr, C_, H_, W_, lam, weight, L.ptr(go), L.ptr(ws), L.ptr(grad),
+                         L.stream_ptr(image.device)), name + "_backward")
         return grad, None, None, None, None
 
 
@@ -172,17 +175,11 @@ def photometric_loss_step(image: torch.Tensor, target: torch.Tensor, lambda_dssi
     C_, H_, W_ = image.shape
     grad = torch.empty_like(image)
     go = grad_loss.to(torch.float32).contiguous() if grad_loss is not None else None
-    if wm is None:
-        ws = L.workspace(dev, lib.syn3r_photo_loss_workspace_bytes(C_, H_, W_), "photo_step")     # the maps die with the call
-        parts = torch.empty(3, dtype=torch.float32, device=dev)
-        L.check(lib.syn3r_photo_loss_step(L.ptr(image), L.ptr(target), C_, H_, W_, float(lambda_dssim), float(weight), L.ptr(go),
-                                          L.ptr(parts), L.ptr(grad), L.ptr(ws), ws.numel(), L.stream_ptr(dev)), "photo_loss_step")
-    else:
-        ws = L.workspace(dev, lib.syn3r_photo_loss_map_workspace_bytes(C_, H_, W_), "photo_step")
-        parts = torch.empty(4, dtype=torch.float32, device=dev)
-        L.check(lib.syn3r_photo_loss_map_step(L.ptr(image), L.ptr(target), L.ptr(wm), C_, H_, W_, float(lambda_dssim), float(weight),
-                                              L.ptr(go), L.ptr(parts), L.ptr(grad), L.ptr(ws), ws.numel(), L.stream_ptr(dev)),
-                "photo_loss_map_step")
+    _, _, step, workspace_bytes, n_parts, name, map_ptr = _photo_entries(lib, wm)
+    ws = L.workspace(dev, workspace_bytes(C_, H_, W_), "photo_step")                              # the maps die with the call
+    parts = torch.empty(n_parts, dtype=torch.float32, device=dev)
+    L.check(step(L.ptr(image), L.ptr(target), *map_ptr, C_, H_, W_, float(lambda_dssim), float(weight), L.ptr(go), L.ptr(parts),
+                 L.ptr(grad), L.ptr(ws), ws.numel(), L.stream_ptr(dev)), name + "_step")
     return parts[0], parts, grad
 
 

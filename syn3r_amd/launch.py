@@ -109,7 +109,7 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                     help="published: the three rules of the published 3DGS optimiser - position rate decaying log-linearly to "
                          "--position_lr_final (default 1.6e-6) over --position_lr_max_steps, times the camera extent; SH rows 1.. at "
                          "feature_lr / 20; SH degree from 0, one up every 1000 iterations (values recalled, UNPINNED: "
-                         "gs/trainer.py OptimizationParams).  constant (default): none of them")
+                         "gs/params.py OptimizationParams).  constant (default): none of them")
     ap.add_argument("--antialiasing", type=int, default=0, choices=(0, 1),
                     help="1: anti-aliased splatting in every render of the trainer (OptimizationParams.antialiasing: the published 3DGS "
                          "switch = Mip-Splatting's 2D Mip filter; constants recalled, UNPINNED).  Not stored in checkpoints: a model "

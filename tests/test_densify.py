@@ -47,7 +47,7 @@ def test_densify_and_prune_matches_oracle():
         z = torch.from_numpy(np.random.default_rng(99).normal(size=(k, 3)).astype(np.float32))
         drawn.append(z.numpy())
         return z
-    tr._split_noise = noise
+    tr.density._split_noise = noise
     n_clone, n_split, n_prune = tr.densify_and_prune(max_grad, min_op, extent, screen)
     assert n_clone > 20 and n_split > 20 and n_prune > 20          # every rule is exercised
     exp, prov = DO.densify_and_prune(before, accum, denom, radii, drawn[0], max_grad=max_grad, min_opacity=min_op, extent=extent,
@@ -87,7 +87,7 @@ def test_reset_opacity_matches_oracle():
 
 
 def test_density_control_schedule():
-    """_density_control: statistics every iteration, densify on the interval after densify_from_iter (screen-size pruning
+    """DensityControl.control: statistics every iteration, densify on the interval after densify_from_iter (screen-size pruning
     only after the first opacity reset), opacity reset on its interval, nothing after densify_until_iter."""
     from syn3r_amd.gs.trainer import GSTrainer, OptimizationParams
     gm, _ = _model(50, 7)
@@ -100,7 +100,7 @@ def test_density_control_schedule():
         tr.iteration = it
         mp = torch.zeros(50, 3, requires_grad=True)
         mp.grad = torch.ones(50, 3)
-        tr._density_control({"visibility_filter": torch.ones(50, dtype=torch.bool), "viewspace_points": mp,
-                             "radii": torch.full((50,), 3)})
+        tr.density.control({"visibility_filter": torch.ones(50, dtype=torch.bool), "viewspace_points": mp,
+                            "radii": torch.full((50,), 3)})
     assert calls == [("densify", 6, None), ("reset", 7), ("densify", 9, 20.0)]
     assert float(gm.denom[0]) == 11.0 and float(gm.max_radii2D[0]) == 3.0      # iterations 1..11 accumulate

@@ -182,7 +182,7 @@ def test_option_off_touches_nothing_and_on_has_no_cpu_fallback():
     assert f is tr.gaussians.filter_3D and f.tolist() == [0.0] * 12 and tr.filter_3d_computes == 1
     assert tr.ensure_filter_3D() is f and tr.filter_3d_computes == 1
     # density control changes the set: the filter is dropped with it (a prune after a clone may give the old N back)
-    tr._keep_gaussians(torch.ones(12, dtype=torch.bool))
+    tr.density._keep_gaussians(torch.ones(12, dtype=torch.bool))
     assert tr.gaussians.filter_3D is None
 
 

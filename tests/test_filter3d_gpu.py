@@ -355,7 +355,7 @@ def test_trainer_bookkeeping(gpu):
     tr.update_cameras([view], [_w2c(0.1, -0.1, 0.5)], K, 0.05)
     with torch.no_grad():
         tr.render_view(cams[1])
-    assert tr.filter_3d_computes == 3 and tr._f3d_table.shape == (4, 16) and len(tr.scene.train_cameras[1.0]) == 4
+    assert tr.filter_3d_computes == 3 and tr.filter3d.table.shape == (4, 16) and len(tr.scene.train_cameras[1.0]) == 4
     np.testing.assert_allclose(gm.filter_3D.cpu().numpy(), _reference_filter(tr).numpy(), rtol=1e-5)
     with torch.no_grad():
         tr.render_view(cams[2])
@@ -364,7 +364,7 @@ def test_trainer_bookkeeping(gpu):
     tr.scene.train_cameras = {1.0: list(cams)}
     with torch.no_grad():
         tr.render_view(cams[1])
-    assert tr.filter_3d_computes == 4 and tr._f3d_table.shape == (3, 16)
+    assert tr.filter_3d_computes == 4 and tr.filter3d.table.shape == (3, 16)
     # density control changes N
     gm.ensure_stats()
     gm.xyz_gradient_accum[:40] = 1.0
@@ -387,7 +387,9 @@ def test_filter_is_computed_without_a_host_round_trip(gpu):
     src = inspect.getsource(train_ops.compute_filter_3D)
     for word in (".item(", "nonzero", ".cpu(", ".tolist(", "synchronize", ".numpy(", "float(xyz", "int(xyz"):
         assert word not in src, word
-    src = inspect.getsource(GSTrainer.ensure_filter_3D)
+    from syn3r_amd.gs.filter3d import Filter3DCache
+    src = inspect.getsource(GSTrainer.ensure_filter_3D) + inspect.getsource(Filter3DCache.ensure)    # the delegation and what it calls
+    assert "compute_filter_3D(" in src
     for word in (".item(", "nonzero", ".cpu(", ".tolist(", "synchronize", ".numpy(", ".any(", ".all(", ".max("):
         assert word not in src, word
     hip = (ROOT / "syn3r_amd" / "csrc" / "filter3d.hip").read_text()

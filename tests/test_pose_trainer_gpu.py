@@ -109,7 +109,7 @@ def test_off_is_the_old_path(gpu, monkeypatch):
     for explicit in (True, False):
         for c in cams:
             tr.train_step(c, explicit=explicit)
-    assert calls["n"] == 0 and tr._pose_table is None and tr.pose_updates == 0
+    assert calls["n"] == 0 and tr.pose.table is None and tr.pose_updates == 0
     for c, (R, T, v) in zip(cams, poses):
         assert np.array_equal(c.R, R) and np.array_equal(c.T, T) and c.world_view_transform is v
     tr, cams, truth = make_trainer(gpu, dict(pose_opt=True, pose_opt_cameras="pseudo", pose_opt_interval=1), n=300)
@@ -135,16 +135,16 @@ def test_camera_list_change_applies_what_is_pending(gpu):
     assert tr.pose_updates == 1 and cams[1].pose_adam["t"] == 1
     tr.train_step(cams[1])
     tr.train_step(cams[2])
-    assert tr._pose_counts == [0, 1, 1] and tr.pose_updates == 1
+    assert tr.pose.counts == [0, 1, 1] and tr.pose_updates == 1
     R1, state1 = cams[1].R.copy(), cams[1].pose_adam
     assert not hasattr(cams[2], "pose_adam")
     tr.update_cameras([cams[2].original_image], [truth[2]], intrinsics(), 0.5, append=True)
-    assert tr.pose_updates == 3 and tr._pose_table is None
+    assert tr.pose_updates == 3 and tr.pose.table is None
     assert cams[1].pose_adam is state1 and state1["t"] == 2 and cams[2].pose_adam["t"] == 1 and not np.array_equal(cams[1].R, R1)
     tr.train_step(tr.pseudo_cameras[0])
-    assert tuple(tr._pose_table.shape) == (4, 35) and tr._pose_counts == [0, 0, 0, 1]
+    assert tuple(tr.pose.table.shape) == (4, 35) and tr.pose.counts == [0, 0, 0, 1]
     tr.reset_gs()
-    assert tr.pose_updates == 4 and tr._pose_table is None and tr.pseudo_cameras[0].pose_adam["t"] == 1
+    assert tr.pose_updates == 4 and tr.pose.table is None and tr.pseudo_cameras[0].pose_adam["t"] == 1
 
 
 def test_checkpoint_round_trip(gpu, tmp_path):
@@ -198,7 +198,7 @@ def test_pose_update_renews_the_filter(gpu):
     tr.train_step(cams[1])
     n0 = tr.filter_3d_computes
     tr.train_step(cams[1])                       # the update happens at the end of this step
-    assert tr.filter_3d_computes == n0 and tr.pose_updates == 1 and tr._f3d_table is None
+    assert tr.filter_3d_computes == n0 and tr.pose_updates == 1 and tr.filter3d.table is None
     tr.train_step(cams[0])
     assert tr.filter_3d_computes == n0 + 1
     tr.train_step(cams[0])                       # nothing pending for an eligible camera: no update, no new filter

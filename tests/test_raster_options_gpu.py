@@ -137,16 +137,16 @@ def make_trainer(dev, **opt_kw):
 @pytest.mark.parametrize("abs_on,pose_on", COMBOS)
 def test_trainer_steps_take_the_table_s_entry(abs_on, pose_on, gpu, entry_calls):
     """densify_abs_grad x pose_opt: one explicit and one autograd step on the camera that is not the fixed first one, density
-    control on.  Which entry ran; `viewspace_abs_grad` reaches `_density_control` exactly with the option on; no pose table with
+    control on.  Which entry ran; `viewspace_abs_grad` reaches `DensityControl.control` exactly with the option on; no pose table with
     `pose_opt` off, one count per step with it on."""
     tr, cams = make_trainer(gpu, densify_abs_grad=abs_on, pose_opt=pose_on, pose_opt_interval=1000)
     tr.densify = True
-    outs, control = [], tr._density_control
+    outs, control = [], tr.density.control
 
     def spy(out):
         outs.append(out)
         return control(out)
-    tr._density_control = spy
+    tr.density.control = spy
     for k, explicit in enumerate((True, False)):
         tr.train_step(cams[1], explicit=explicit)
         assert took(entry_calls) == {expected_entry(abs_on, pose_on): 1}, explicit
@@ -156,6 +156,6 @@ def test_trainer_steps_take_the_table_s_entry(abs_on, pose_on, gpu, entry_calls)
     torch.cuda.synchronize()
     assert (tr.gaussians.xyz_gradient_accum_abs is not None) == abs_on
     if pose_on:
-        assert tuple(tr._pose_table.shape) == (2, 35) and tr._pose_counts == [0, 2] and float(tr._pose_table[1].abs().max()) > 0
+        assert tuple(tr.pose.table.shape) == (2, 35) and tr.pose.counts == [0, 2] and float(tr.pose.table[1].abs().max()) > 0
     else:
-        assert tr._pose_table is None and tr._pose_counts == []
+        assert tr.pose.table is None and tr.pose.counts == []

@@ -279,7 +279,7 @@ def test_trainer_proximity_unpool_appends_the_restated_rows(gpu):
     n, extent = 600, 2.0
     tr = _gpu_trainer(n, 5, gpu)
     gm = tr.gaussians
-    before = {a: _np(getattr(gm, a)).copy() for a in tr._PARAM_ATTRS}
+    before = {a: _np(getattr(gm, a)).copy() for a in tr.density._PARAM_ATTRS}
     conf0 = _np(gm.confidence).copy()
     dist, idx = graph_bruteforce(before["_xyz"])
     q = float(np.quantile(_score(dist), 0.8))
