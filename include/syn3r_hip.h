@@ -821,6 +821,27 @@ int syn3r_depth_corr_loss_backward(const float* depth, const float* prior, long 
 int syn3r_depth_corr_loss_step(const float* depth, const float* prior, long long n, float weight, float offset, int mode,
                                const float* grad_loss, float* parts, float* grad_depth, void* ws, size_t ws_bytes, void* stream);
 
+/* Per-camera affine exposure compensation (EXTENSION: the reference has none; the published 3DGS code base has since grown a
+ * per-image exposure model, gsplat an appearance optimisation).  A is 3 x 4 fp32, row-major, 12 floats in DEVICE memory; image,
+ * out, grad_out and grad_image are [3,H,W] fp32 planes:
+ *   out_c(p)        = A[c][0] image_0(p) + A[c][1] image_1(p) + A[c][2] image_2(p) + A[c][3]     (added left to right, no clamp)
+ *   grad_image_k(p) = sum_c A[c][k] grad_out_c(p)
+ *   grad_A[c][k]    = sum_p grad_out_c(p) image_k(p)        grad_A[c][3] = sum_p grad_out_c(p)
+ * The convention is this library's own: a 3 x 3 block times the colour as a COLUMN, then the offset.  The published code multiplies
+ * a row vector by the transposed 3 x 3 block - recalled, not available to check against: UNPINNED.
+ * syn3r_exposure_apply is one launch.  syn3r_exposure_backward is two: a pass over the six input planes that writes grad_image and
+ * leaves one row of 12 fp32 partial sums per block in ws (per-thread running sums, added over the wave, then over the block's waves
+ * in a fixed order), and a one-block kernel that adds the rows in a fixed order in fp64 and stores grad_A (accumulate == 0) or adds
+ * to it (accumulate != 0).  No atomics, the grid depends on H * W alone: bitwise repeatable for a given shape.  Planes whose
+ * pointers are 16-byte aligned with H * W % 4 == 0 go through 16-byte accesses, anything else (4-byte aligned) through scalar ones.
+ * ws: syn3r_exposure_backward_workspace_bytes(H, W) bytes (0 for H or W outside [1, 2^15]), 16-byte aligned.
+ * Rejections before any HIP call: null pointers, H or W outside [1, 2^15], misaligned pointers, out / grad_image overlapping an
+ * input (SYN3R_E_INVALID), a short workspace (SYN3R_E_WORKSPACE).  The parameter update is syn3r_adam_step on the 12 floats. */
+int syn3r_exposure_apply(const float* image, const float* A, int H, int W, float* out, void* stream);
+size_t syn3r_exposure_backward_workspace_bytes(int H, int W);
+int syn3r_exposure_backward(const float* image, const float* A, const float* grad_out, int H, int W, float* grad_image, float* grad_A,
+                            int accumulate, void* ws, size_t ws_bytes, void* stream);
+
 /* One torch.optim.Adam update (no weight decay, no amsgrad) of n fp32 parameters in place, in torch's
  * operation order: exp_avg.lerp_(g, 1-beta1); exp_avg_sq = beta2*exp_avg_sq + (1-beta2)*g*g;
  * param -= lr/(1-beta1^step) * exp_avg / (sqrt(exp_avg_sq)/sqrt(1-beta2^step) + eps).  step is 1-based. */

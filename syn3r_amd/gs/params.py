@@ -99,6 +99,25 @@ class OptimizationParams:
     pose_lr_translation: float = 1e-3
     pose_opt_interval: int = 10
     pose_opt_from_iter: int = 0
+    # Per-camera affine exposure compensation (EXTENSION: the reference has none; what a user of the published 3DGS code base's
+    # per-image exposure model or of gsplat's appearance optimisation expects of a trainer that refines against generated frames,
+    # whose brightness, white balance and contrast drift).  An eligible camera holds A (3 x 4, initialised to [I | 0]) and its loss
+    # compares E(render), E_c = A[c][0] I_0 + A[c][1] I_1 + A[c][2] I_2 + A[c][3], with the camera's target: the photometric term (L1,
+    # D-SSIM, with or without `confidence_map`) and the LPIPS term see E(render); the depth-correlation term, `render_view`,
+    # `evaluate`, the capacity-seeding renders and the orchestrator's render_GS see the scene colour (`gs/exposure.py`,
+    # csrc/exposure.hip; four more launches per step on an eligible camera, no host read).  `exposure_cameras`: "pseudo" (the views
+    # `update_cameras` registered), "train" (the input views) or "all"; for "train" and "all" the FIRST training camera keeps the
+    # identity forever (gauge: otherwise a global colour change is free).  A takes one Adam step (betas 0.9 / 0.999, eps 1e-15) per
+    # step on its camera at `exposure_lr`, constant unless `exposure_lr_final` is set: then expon_lr(iteration + 1, exposure_lr,
+    # exposure_lr_final, max_steps=exposure_lr_max_steps).  Rate 0.01 (to 0.001 over 30 000 steps in the released arguments) and the
+    # Adam constants are RECALLED from the released 3DGS arguments, which are not available to check against: UNPINNED and scene
+    # dependent.  Off by default: every render, gradient, launch, checkpoint file and decision is what it was.  A and its Adam state
+    # ARE stored in checkpoints (written only with the option on).  No regulariser on A, no exposure for held-out cameras.
+    exposure_opt: bool = False
+    exposure_cameras: str = "pseudo"
+    exposure_lr: float = 0.01
+    exposure_lr_final: Optional[float] = None
+    exposure_lr_max_steps: int = 30_000
 
 
 def expon_lr(step, lr_init: float, lr_final: float, lr_delay_steps: int = 0, lr_delay_mult: float = 1.0,

@@ -9,9 +9,9 @@ heuristics (out of scope).
 
 `GSTrainer` holds construction, the optimiser and its learning rate, camera registration, checkpoints, the two step routes and
 the loop.  What it is made of lives beside it and is re-exported here: the cameras and their registry (`camera.py`), the Gaussians
-(`gaussian_model.py`), the options and `expon_lr` (`params.py`); and three objects it owns, each with the state of one concern:
-adaptive density control (`density.DensityControl`), the camera-gradient table of pose refinement (`pose.PoseTable`) and the
-3D filter's camera table (`filter3d.Filter3DCache`).
+(`gaussian_model.py`), the options and `expon_lr` (`params.py`); and four objects it owns, each with the state of one concern:
+adaptive density control (`density.DensityControl`), the camera-gradient table of pose refinement (`pose.PoseTable`), the
+3D filter's camera table (`filter3d.Filter3DCache`) and the per-camera exposure (`exposure.ExposureControl`).
 """
 from __future__ import annotations
 
@@ -27,12 +27,14 @@ from .. import raster
 from ..raster import GaussianRasterizationSettings, GaussianRasterizer
 from .camera import Camera, _projection, _Scene, _world2view  # noqa: F401  (re-exported: callers import them from here)
 from .density import DensityControl
+from .exposure import CAMERA_KINDS as EXPOSURE_CAMERA_KINDS
+from .exposure import ExposureControl
 from .filter3d import Filter3DCache
 from .gaussian_model import SH_C0, GaussianModel, build_rotation  # noqa: F401
 from .params import OptimizationParams, expon_lr
 from .pose import PoseTable
 from .train_ops import FusedAdam, depth_correlation_loss, image_metrics, l1_loss, photometric_loss
-from .train_ops import depth_correlation_loss_step, l1_loss_step, photometric_loss_step
+from .train_ops import depth_correlation_loss_step, exposure_apply, exposure_apply_step, l1_loss_step, photometric_loss_step
 
 
 class GSTrainer:
@@ -52,19 +54,23 @@ class GSTrainer:
         self._ck_tag, self._ck_keys = None, []        # _capacity_keys
         if self.opt.pose_opt_cameras not in ("train", "pseudo", "all"):
             raise ValueError(f"OptimizationParams.pose_opt_cameras must be 'train', 'pseudo' or 'all', got {self.opt.pose_opt_cameras!r}")
+        if self.opt.exposure_cameras not in EXPOSURE_CAMERA_KINDS:
+            raise ValueError(f"OptimizationParams.exposure_cameras must be 'pseudo', 'train' or 'all', got {self.opt.exposure_cameras!r}")
         self.density = DensityControl(self)           # adaptive density control: every change of the set of Gaussians
         self.filter3d = Filter3DCache()               # `opt.filter_3d`: the camera table and the age of `gaussians.filter_3D`
         self.pose = PoseTable(self)                   # `opt.pose_opt`: the camera-gradient table and its counts
+        self.exposure = ExposureControl(self)         # `opt.exposure_opt`: which cameras have an exposure, its gradient and its Adam step
         self.background = torch.tensor(background, dtype=torch.float32, device=gaussians._xyz.device)
         self._rng = np.random.default_rng(self.opt.seed)
         self.reset_optimizers()
 
-    # ------------------------------------------------------------------ public names of what the three owned objects keep and do
+    # ------------------------------------------------------------------ public names of what the four owned objects keep and do
     # (the docstrings are at the implementations)
     last_unpooled = property(lambda self: self.density.last_unpooled, doc="Gaussians the proximity unpooling added in the last "
                              "densify_and_prune call")
     filter_3d_computes = property(lambda self: self.filter3d.computes, doc="how often ensure_filter_3D has computed the filter")
     pose_updates = property(lambda self: self.pose.updates, doc="camera moves applied so far (apply_pose_updates)")
+    exposure_updates = property(lambda self: self.exposure.updates, doc="exposure (Adam) steps taken so far")
 
     def densify_and_prune(self, max_grad: float, min_opacity: float, extent: float, max_screen_size: Optional[float]):
         return self.density.densify_and_prune(max_grad, min_opacity, extent, max_screen_size)
@@ -83,6 +89,11 @@ class GSTrainer:
 
     def flush_pose_updates(self) -> int:
         return self.pose.flush()
+
+    def exposed(self, image: torch.Tensor, cam: Camera) -> torch.Tensor:
+        """What the loss of a step on `cam` compares with the camera's target: E(image) for a camera that has an exposure
+        (`opt.exposure_opt`, `gs/exposure.py`), else `image` itself.  Every render the trainer RETURNS is the scene colour."""
+        return self.exposure.exposed(image, cam)
 
     # ------------------------------------------------------------------ surface used by DiffusionGS
     def reset_optimizers(self):
@@ -160,6 +171,9 @@ class GSTrainer:
             # refined poses and their Adam state, per registered camera (key absent with the option off: the file it always was).  What
             # is pending in the gradient table is NOT applied here: saving must not change the run
             state["camera_poses"] = self.pose.capture()
+        if self.opt.exposure_opt:
+            # the exposures and their Adam state, per registered camera that has any (key absent with the option off)
+            state["camera_exposures"] = self.exposure.capture()
         torch.save((state, int(iteration)), path)
         return path
 
@@ -174,6 +188,8 @@ class GSTrainer:
         self.iteration = int(it)
         if "camera_poses" in state:                    # (written with `opt.pose_opt`; an older file has no such key and loads as before)
             self.pose.restore(state["camera_poses"])
+        if "camera_exposures" in state and self.opt.exposure_opt:      # (a trainer with the option off leaves the key alone)
+            self.exposure.restore(state["camera_exposures"])
         self.reset_optimizers()
 
     def reset_gaussians_from_pcd(self, pcd, append_to_old_gaussians: bool = False):
@@ -340,7 +356,11 @@ class GSTrainer:
             color, radii, depth, alpha, rstate = raster.rasterize_forward(g._xyz, g._features, g._opacity, g._scaling, g._rotation,
                                                                           g.confidence, self._raster_settings(cam, 1.0), raw_params=True,
                                                                           filter_3D=f3)
-            loss, d_color = self._photo_loss(color, cam, True)
+            A = self.exposure.state(cam)              # None: a camera without an exposure runs the plain step, launch for launch
+            loss, d_color = self._photo_loss(color if A is None else exposure_apply_step(color, A), cam, True)
+            if A is not None:                         # d loss / d E(color) -> d loss / d color; d loss / d A into the control's buffer,
+                d_color = self.exposure.backward(color, cam, d_color)       # then ITS Adam step (no host read)
+                self.exposure.step(cam)
             d_depth = None
             if prior is not None:
                 d_loss, d_depth = depth_correlation_loss_step(depth, prior, self.opt.depth_weight, self.opt.depth_offset)
@@ -364,18 +384,24 @@ class GSTrainer:
         `visibility_filter` and the gradient on `viewspace_points` are what the density control reads on this route."""
         pose_row = self.pose.row(cam)
         out = self.render_view(cam, _pose_row=pose_row)
-        loss, _ = self._photo_loss(out["render"], cam, False)
+        A = self.exposure.state(cam)                  # None: a camera without an exposure
+        if A is not None:
+            A = A.detach().requires_grad_(True)       # (a leaf over `cam.exposure`'s memory; its gradient goes to `exposure.step` below)
+        image = out["render"] if A is None else exposure_apply(out["render"], A)       # the photometric and LPIPS terms see E(render)
+        loss, _ = self._photo_loss(image, cam, False)
         if lpips_on:
             # the perceptual term of the refine stage (diffusionGS.py:1690,1697; `--lpips_weight`): published LPIPS-VGG on the
             # whole render, weighted like the photometric term by the camera confidence.  How FSGS applies it is not visible
             # (un-vendored): UNPINNED.
-            loss = loss + (self.opt.lpips_weight * float(cam.cam_confidence)) * self.lpips(out["render"].clamp(0, 1), cam.original_image)
+            loss = loss + (self.opt.lpips_weight * float(cam.cam_confidence)) * self.lpips(image.clamp(0, 1), cam.original_image)
         prior = self._depth_term_prior(cam)
         if prior is not None:
             loss = loss + depth_correlation_loss(out["depth"], prior, self.opt.depth_weight, self.opt.depth_offset)
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         self.pose.count(pose_row)
+        if A is not None:
+            self.exposure.step(cam, A.grad)
         return loss, out
 
     def train_step(self, cam: Optional[Camera] = None, explicit: Optional[bool] = None) -> torch.Tensor:
@@ -391,6 +417,10 @@ class GSTrainer:
         `cam.confidence_map` (EXTENSION, default None: the scalar-only, reference-shaped loss): a per-pixel weight on the photometric
         term (L1 and D-SSIM, `train_ops.photometric_loss(weight_map=)`) on top of the scalar `cam.cam_confidence`, on both the
         explicit and the autograd path.  The depth-correlation and LPIPS terms are NOT touched by the map.
+        `opt.exposure_opt` (EXTENSION, default off: every launch is what it was): a camera of `opt.exposure_cameras` holds an affine
+        colour transform `cam.exposure` (`gs/exposure.py`); the photometric and LPIPS terms compare E(render) with its target and the
+        transform takes one Adam step per step on its camera, on both routes (four more launches: apply, the backward's two, Adam).
+        The depth-correlation term and every render the trainer returns keep the scene colour; `exposed` shows what the loss saw.
         `explicit` (default: whenever the LPIPS term is off): the step without autograd (`_explicit_step`).
         The published schedule, when switched on (`OptimizationParams`): `update_learning_rate(iteration + 1)` before the optimiser
         step, `oneupSHdegree()` after every `sh_degree_interval`-th step (the published loop raises it at the top of the next

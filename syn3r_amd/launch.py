@@ -138,6 +138,19 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                     help="OptimizationParams.pose_lr_translation, times the spatial scale (default: the trainer's own, 1e-3 - chosen, UNPINNED)")
     ap.add_argument("--pose_opt_interval", type=int, default=None,
                     help="OptimizationParams.pose_opt_interval: iterations between pose updates (default: the trainer's own, 10 - chosen, UNPINNED)")
+    ap.add_argument("--exposure_opt", type=int, default=0, choices=(0, 1),
+                    help="1: EXTENSION (not in the reference) - per-camera affine exposure compensation (OptimizationParams.exposure_opt): "
+                         "a camera of --exposure_cameras holds a 3 x 4 colour transform between its render and the photometric / LPIPS "
+                         "terms, with an Adam step of its own per step on that camera; the first training camera keeps the identity.  "
+                         "Renders, evaluate() and the depth term keep the scene colour.  0 (default): no camera has one")
+    ap.add_argument("--exposure_cameras", type=str, default=None, choices=("pseudo", "train", "all"),
+                    help="OptimizationParams.exposure_cameras: the diffusion pseudo-views, the input views, or both (default: the "
+                         "trainer's own, pseudo)")
+    ap.add_argument("--exposure_lr", type=float, default=None,
+                    help="OptimizationParams.exposure_lr (default: the trainer's own, 0.01 - recalled, UNPINNED, scene dependent)")
+    ap.add_argument("--exposure_lr_final", type=float, default=None,
+                    help="OptimizationParams.exposure_lr_final: the rate decays log-linearly to it over exposure_lr_max_steps (default: "
+                         "the trainer's own, None = constant)")
     ap.add_argument("--num_inference_steps", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     # FSGS' parameter groups (scripts/train.py:44-46: -s, --eval, --n_views, --resolution, --use_dust3r ... of the batch scripts)
@@ -149,7 +162,8 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     declared = ["--" + f for f, _ in TRAINER_FLAGS] + ["--gs_schedule", "--pixel_confidence", "--antialiasing", "--filter_3d",
                                                        "--densify_abs_grad", "--densify_abs_grad_threshold", "--pose_opt",
                                                        "--pose_opt_cameras", "--pose_lr_rotation", "--pose_lr_translation",
-                                                       "--pose_opt_interval"]
+                                                       "--pose_opt_interval", "--exposure_opt", "--exposure_cameras", "--exposure_lr",
+                                                       "--exposure_lr_final"]
     # (a token that IS a declared flag is not an abbreviation of a longer one: --densify_abs_grad / --densify_abs_grad_threshold)
     cut = [t for t in given if t.startswith("--") and t.split("=")[0] not in declared
            and any(d.startswith(t.split("=")[0]) for d in declared)]
@@ -182,7 +196,8 @@ def apply_trainer_flags(opt, args):
     spatial_lr_scale = None (the camera extent), feature_rest_lr_div = 20, sh_degree_interval = 1000.  Pure: no GPU, `opt`
     untouched.  `--antialiasing 1` sets `antialiasing`, `--filter_3d 1` sets `filter_3d`, `--densify_abs_grad 1` sets `densify_abs_grad`
     (0, the default, leaves the field as `opt` has it); `--densify_abs_grad_threshold`, when given, sets its field.  `--pose_opt 1`
-    sets `pose_opt`; `--pose_opt_cameras`, `--pose_lr_rotation`, `--pose_lr_translation` and `--pose_opt_interval`, when given, set theirs.  (--sh_degree
+    sets `pose_opt`; `--pose_opt_cameras`, `--pose_lr_rotation`, `--pose_lr_translation` and `--pose_opt_interval`, when given, set theirs.
+    `--exposure_opt 1` sets `exposure_opt`; `--exposure_cameras`, `--exposure_lr` and `--exposure_lr_final`, when given, set theirs.  (--sh_degree
     describes the model, not the optimiser: the scene factory reads it.)"""
     import dataclasses
     new = {}
@@ -205,6 +220,11 @@ def apply_trainer_flags(opt, args):
     if getattr(args, "pose_opt", 0):
         new["pose_opt"] = True
     for flag, typ in (("pose_opt_cameras", str), ("pose_lr_rotation", float), ("pose_lr_translation", float), ("pose_opt_interval", int)):
+        if getattr(args, flag, None) is not None:
+            new[flag] = typ(getattr(args, flag))
+    if getattr(args, "exposure_opt", 0):
+        new["exposure_opt"] = True
+    for flag, typ in (("exposure_cameras", str), ("exposure_lr", float), ("exposure_lr_final", float)):
         if getattr(args, flag, None) is not None:
             new[flag] = typ(getattr(args, flag))
     return dataclasses.replace(opt, **new)
