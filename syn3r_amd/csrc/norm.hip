@@ -27,6 +27,25 @@ __device__ __forceinline__ const __half* gn_src(const __half* x, const __half* x
     return x2 + sample_rows * (size_t)(C - C1) + (size_t)(cv * 8 - C1);
 }
 
+// Statistics pass.  The one-pass variance E[x^2] - mean^2 loses (mean / std)^2 of its fp32 precision to the cancellation: 12 of
+// the 24 bits at mean / std = 64, which activations with a channel offset reach (rstd off by 3e-4: whole fp16 ulps of the
+// output).  So every thread sums, per channel, x and the squares of x - K with K = ITS OWN first value, and turns them into
+// the sum of squared deviations from its own mean, M2 = sum (x - K)^2 - n (mean - K)^2.  K is one of the thread's n values, so
+// (mean - K)^2 <= M2 and the cancellation costs at most a factor n (the thread's rows: tens) whatever the data - an outlier
+// in K included.  (count, sum, M2) are then merged pairwise, M2 += M2b + (mean_b - mean_a)^2 na nb / (na + nb) (Chan et al.),
+// which has no cancellation: over the thread-channels of a group here, over the chunks in k_gn_finalize, always in the same
+// order (bitwise reproducible, no atomics).  The mean is the plain sum of x over the group.
+struct GnAcc {
+    float n, s, m2;
+    __device__ __forceinline__ void merge(float nb, float sb, float m2b) {      // nb > 0
+        const float tot = n + nb;
+        const float delta = sb / nb - (n > 0.f ? s / n : 0.f);
+        m2 += m2b + delta * delta * (n * (nb / tot));
+        s += sb;
+        n = tot;
+    }
+};
+
 __global__ void k_gn_stats(const __half* __restrict__ x, const __half* __restrict__ x2, int C1, int R, int C, int rows_per_block,
                            float* __restrict__ stats) {
     extern __shared__ float red[];   // [threads][16]
@@ -38,13 +57,19 @@ __global__ void k_gn_stats(const __half* __restrict__ x, const __half* __restric
     const int r_end = min(R, r_begin + rows_per_block);
     int stride;
     const __half* base = gn_src(x, x2, C, C1, cv, (size_t)sample * R, stride);
-    float s[8], q[8];
+    float s[8], q[8], sh[8];
+    int r = r_begin + rl;
+    // rows of this thread: r, r + rpb, ... < r_end
+    const int nrows = r < r_end ? (r_end - r + rpb - 1) / rpb : 0;
+    {
+        half8 first = {};
+        if (nrows > 0) first = *(const half8*)(base + (size_t)r * stride);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; }
+        for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; sh[e] = (float)first[e]; }
+    }
     // four rows of a thread are requested together (one load per trip left the pass waiting out a memory latency per row); the
     // sums take the rows in the same order
     constexpr int UN = 4;
-    int r = r_begin + rl;
     for (; r + (UN - 1) * rpb < r_end; r += UN * rpb) {
         half8 v[UN];
 #pragma unroll
@@ -53,9 +78,9 @@ __global__ void k_gn_stats(const __half* __restrict__ x, const __half* __restric
         for (int u = 0; u < UN; ++u) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                float f = (float)v[u][e];
+                const float f = (float)v[u][e], d = f - sh[e];
                 s[e] += f;
-                q[e] += f * f;
+                q[e] += d * d;
             }
         }
     }
@@ -63,57 +88,69 @@ __global__ void k_gn_stats(const __half* __restrict__ x, const __half* __restric
         half8 v = *(const half8*)(base + (size_t)r * stride);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            float f = (float)v[e];
+            const float f = (float)v[e], d = f - sh[e];
             s[e] += f;
-            q[e] += f * f;
+            q[e] += d * d;
         }
     }
     float* my = red + threadIdx.x * 16;
+    const float nt = (float)nrows, inv_nt = nrows > 0 ? 1.0f / nt : 0.f;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { my[e] = s[e]; my[8 + e] = q[e]; }
+    for (int e = 0; e < 8; ++e) {
+        const float dm = s[e] * inv_nt - sh[e];
+        my[e] = s[e];
+        my[8 + e] = fmaxf(q[e] - nt * dm * dm, 0.f);
+    }
     __syncthreads();
-    // threads 0..31: one group each; sum its channels over the rpb row-lanes
+    // threads 0..31: one group each; merge its channels over the rpb row-lanes
     if (threadIdx.x < 32) {
         const int g = threadIdx.x, cpg = C / 32;
-        float gs = 0.f, gq = 0.f;
-        for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
-            int v = c >> 3, e = c & 7;
-            for (int k = 0; k < rpb; ++k) {
-                const float* o = red + (k * cvec + v) * 16;
-                gs += o[e];
-                gq += o[8 + e];
+        // GnAcc::merge with a running mean and reciprocals (v_rcp_f32, 1 ulp: the weights only scale the small between-thread
+        // term): the thread-channels of a row-lane share their count, and this loop is the serial tail of every block
+        float n = 0.f, gs = 0.f, gm = 0.f, gm2 = 0.f;
+        for (int k = 0; k < rpb; ++k) {
+            const int rows_k = r_begin + k < r_end ? (r_end - r_begin - k + rpb - 1) / rpb : 0;
+            if (rows_k == 0) break;
+            const float nb = (float)rows_k, inv_nb = __builtin_amdgcn_rcpf(nb);
+            for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
+                const float* o = red + (k * cvec + (c >> 3)) * 16;
+                const float sb = o[c & 7];
+                const float w = nb * __builtin_amdgcn_rcpf(n + nb);
+                const float delta = sb * inv_nb - gm;
+                gm2 += o[8 + (c & 7)] + delta * delta * (n * w);
+                gm += delta * w;
+                gs += sb;
+                n += nb;
             }
         }
-        // per-chunk partial (summed in a fixed order by k_gn_apply: bitwise reproducible, no atomics)
+        // per-chunk partial (sum of x, M2; the count follows from the chunk's rows), merged in a fixed order by k_gn_finalize
         float* dst = stats + (((size_t)sample * gridDim.x + blockIdx.x) * 32 + g) * 2;
         dst[0] = gs;
-        dst[1] = gq;
+        dst[1] = gm2;
     }
 }
 
-// Fixed-order reduction of the per-chunk partials -> (mean, rstd) per (sample, group).
+// Fixed-order merge of the per-chunk partials (sum of x, M2) -> (mean, rstd) per (sample, group).
 // One 1024-thread block per sample: 32 threads per group stride over the chunks, then a fixed
 // 5-step shuffle tree (bitwise reproducible).
 __global__ void __launch_bounds__(1024) k_gn_finalize(const float* __restrict__ partial, int chunks, float inv_n, float eps,
-                                                     float* __restrict__ mr) {
+                                                     int R, int rows_per_block, int cpg, float* __restrict__ mr) {
     const int sample = blockIdx.x;
     const int g = threadIdx.x >> 5, sub = threadIdx.x & 31;
-    float s1 = 0.f, s2 = 0.f;
+    GnAcc acc = {0.f, 0.f, 0.f};
     for (int ch = sub; ch < chunks; ch += 32) {
         const float* st = partial + (((size_t)sample * chunks + ch) * 32 + g) * 2;
-        s1 += st[0];
-        s2 += st[1];
+        const int rows = min(R, (ch + 1) * rows_per_block) - ch * rows_per_block;
+        acc.merge((float)rows * (float)cpg, st[0], st[1]);
     }
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) {
-        s1 += __shfl_down(s1, o, 32);
-        s2 += __shfl_down(s2, o, 32);
+        const float nb = __shfl_down(acc.n, o, 32), sb = __shfl_down(acc.s, o, 32), m2b = __shfl_down(acc.m2, o, 32);
+        if (nb > 0.f) acc.merge(nb, sb, m2b);
     }
     if (sub == 0) {
-        float mean = s1 * inv_n;
-        float var = fmaxf(s2 * inv_n - mean * mean, 0.0f);
-        mr[((size_t)sample * 32 + g) * 2] = mean;
-        mr[((size_t)sample * 32 + g) * 2 + 1] = rsqrtf(var + eps);
+        mr[((size_t)sample * 32 + g) * 2] = acc.s * inv_n;
+        mr[((size_t)sample * 32 + g) * 2 + 1] = rsqrtf(fmaxf(acc.m2 * inv_n, 0.0f) + eps);
     }
 }
 
@@ -387,7 +424,7 @@ int groupnorm_launch(const void* x, const void* x2, int C1, void* y, int samples
         SYN3R_LAUNCH(k_gn_stats, grid, dim3(threads), lds, stream, (const __half*)x, (const __half*)x2, C1, rows, C, rows_per_block,
                      partial);
         SYN3R_LAUNCH(k_gn_finalize, dim3(samples), dim3(1024), 0, stream, (const float*)partial, chunks,
-                     1.0f / ((float)rows * (float)(C / 32)), eps, meanrstd);
+                     1.0f / ((float)rows * (float)(C / 32)), eps, rows, rows_per_block, C / 32, meanrstd);
     }
     if (silu)
         SYN3R_LAUNCH(k_gn_apply<true>, grid, dim3(threads), 0, stream, (const __half*)x, (const __half*)x2, C1, (__half*)y, rows,
