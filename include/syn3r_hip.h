@@ -637,6 +637,31 @@ int syn3r_conv2d3x3_f16(const void* X, const void* W, void* out, long long ldc, 
                         int pad_lo, void* gn_partials, size_t gn_partials_bytes, int* gn_written, void* stream);
 
 /*
+ * The same nearest-2x upsample + 3x3 convolution (upsampling.py:172-183) as FOUR 2x2 convolutions at input resolution, one per
+ * output parity: after the upsample the 3x3 window of output pixel (2i + py, 2j + px) covers input pixels
+ * (i + py - 1 + a, j + px - 1 + b), a, b in {0, 1}, and the nine taps collapse onto them with summed weights - K = 4 Cin instead
+ * of 9 Cin.  The zero padding of the upsampled image falls on input row / column -1 or Hi / Wi: borders need no special weights.
+ *
+ * syn3r_pack_upsample4_f16 (pure host code, no GPU call; once per loaded model): w [Cout, 3, 3, Cin] fp16 (OHWI, as
+ * syn3r_conv2d3x3_f16 takes it) -> w4 [4][Cout][2][2][Cin] fp16, phase p = 2 py + px.  Filter rows ty fall on block row a as
+ * py = 0: {0} | {1, 2}, py = 1: {0, 1} | {2} (columns the same with px); a folded weight is the sum of its 1, 2 or 4 source taps
+ * in fp32, in ascending (ty, tx) order, rounded once to fp16 (nearest even).  The result differs from the 9-tap form by that one
+ * rounding of the weights (about 2e-4 relative rms of the output at UNet widths, under half an fp16 output step).
+ *
+ * syn3r_conv2d3x3_up4_f16: X [NB, Hi, Wi, Cin], w4 as packed, bias [Cout] or NULL -> out [NB, 2 Hi, 2 Wi, Cout] (dense rows of
+ * Cout).  Accumulation in fp32 with k = (channel chunk of 64, tap) ascending, bias added, one rounding to fp16.  No row vector,
+ * residual or aux: `residual` must be NULL (the 9-tap entry has the general epilogue).  Refused with SYN3R_E_INVALID and a
+ * message: Cin % 64 != 0 (a k-tile is 64 channels of one tap; in particular every Cin % 16 != 0), Cout % 8 != 0,
+ * NB Hi Wi >= 2^24, a non-NULL residual.  gn_partials / gn_partials_bytes / gn_written: as for syn3r_gemm_f16 with
+ * M = 4 NB Hi Wi, N = Cout, written when also Hi Wi % 32 == 0; the 32-row block lb of phase p of image n is slot
+ * (4 n + p) (Hi Wi / 32) + lb of the buffer - its rows are 32 pixels of ONE phase, not 32 consecutive output rows: every image
+ * still owns 4 Hi Wi / 32 consecutive slots, which is all syn3r_groupnorm_pre_f16 (samples = images) relies on.
+ */
+int syn3r_pack_upsample4_f16(const void* w, void* w4, int Cout, int Cin);
+int syn3r_conv2d3x3_up4_f16(const void* X, const void* w4, void* out, const void* bias, const void* residual, int NB, int Hi, int Wi,
+                            int Cin, int Cout, void* gn_partials, size_t gn_partials_bytes, int* gn_written, void* stream);
+
+/*
  * (3,1,1) Conv3d over frames, padding (1,0,0) (resnet.py:571-597) on [B,F,HW,Cin] fp16.
  * W [Cout, 3, Cin] (= the Conv3d weight [Cout,Cin,3,1,1] permuted), Cin % 64 == 0.
  * gn_partials / gn_partials_bytes / gn_written: as for syn3r_gemm_f16 (M = B*F*HW, N = Cout).

@@ -103,6 +103,8 @@ SIGNATURES = {
     "syn3r_layernorm_linear320_f16": (c_i, [c_p, c_ll, c_p, c_p, c_f, c_p, c_p, c_ll, c_i, c_i, c_i, c_p]),
     "syn3r_conv2d3x3_f16": (c_i, [c_p, c_p, c_p, c_ll, c_p, c_p, c_ll, c_i, c_p, c_ll, c_f, c_f,
                                   c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_sz, C.POINTER(c_i), c_p]),
+    "syn3r_pack_upsample4_f16": (c_i, [c_p, c_p, c_i, c_i]),
+    "syn3r_conv2d3x3_up4_f16": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_sz, C.POINTER(c_i), c_p]),
     "syn3r_tconv3_f16": (c_i, [c_p, c_p, c_p, c_ll, c_p, c_p, c_ll, c_i, c_p, c_ll, c_f, c_f,
                                c_i, c_i, c_i, c_i, c_i, c_p, c_sz, C.POINTER(c_i), c_p]),
     "syn3r_attention_f16": (c_i, [c_p, c_p, c_p, c_ll, c_p, c_ll, c_i, c_i, c_i, c_p]),

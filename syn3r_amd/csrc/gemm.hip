@@ -17,7 +17,9 @@
 // per shape by launch_dma (DESIGN.md section 4 has the measurements behind every rule):
 //   k_gemm_widep   persistent 256 x 320 tile (dense contractions whose tiles fill the CUs): LDS-DMA 2-stage ring,
 //                  cross-tile prefetch, scalar addressing, lean epilogue, GEGLU gate in registers, two-source A
-//   k_gemm_z       the same tile with a software-pipelined main loop (gemm_z.h): gated projections, 3x3 convolutions
+//   k_gemm_z       the same tile with a software-pipelined main loop (gemm_z.h): gated projections, 3x3 convolutions; its UP4
+//                  mode is the nearest-2x upsample + 3x3 convolution as four 2x2 phase convolutions on folded weights
+//                  (syn3r_conv2d3x3_up4_f16: chosen by the caller, not by launch_dma)
 //   k_ffn320r      FeedForward (GEGLU) for C = 320 in one kernel, hidden activation never leaves the CU
 //   k_lnlin320     LayerNorm + stacked q / k / v projection for C = 320 in one kernel
 //   k_gemm_dma     BM x 160 tile, LDS-DMA 3-stage ring (BM = 256, wavefronts 4-7 staggered; every convolution /
@@ -157,6 +159,16 @@ int launch_z(const GemmParams& p, hipStream_t stream, int* gn_written) {
         if (p.ups) return launch_tiles<k_gemm_z<false, MODE_CONV2D, true>>("gemm_z", Z_LDS, blocks, 512, stream, q, gn_written, "k_gemm_z<%d>", MODE);
     }
     return launch_tiles<k_gemm_z<false, MODE>>("gemm_z", Z_LDS, blocks, 512, stream, q, gn_written, "k_gemm_z<%d>", MODE);
+}
+
+// The four-phase upsampling convolution (k_gemm_z<false, MODE_CONV2D, false, true>, gemm_z.h): p.M / p.K are ONE phase's rows and
+// 4 Cin; the tile list holds the four phases one after the other.
+int launch_z_up4(const GemmParams& p, hipStream_t stream, int* gn_written) {
+    const long long blocks = std::min<long long>(4 * wide_tiles(p), persistent_blocks());
+    GemmParams q = p;
+    q.band = band_width(p);
+    q.a_bytes = (unsigned)((long long)p.M * p.Cin * 2);
+    return launch_tiles<k_gemm_z<false, MODE_CONV2D, false, true>>("gemm_z", Z_LDS, blocks, 512, stream, q, gn_written, "k_gemm_z<%d>/up4", MODE_CONV2D);
 }
 
 // Kernel family forced by the CALLING THREAD (syn3r_gemm_set_tile; tests and tuning tools): 0 = by shape, 128 / 256 = the
@@ -663,6 +675,34 @@ extern "C" int syn3r_conv2d3x3_f16(const void* X, const void* W, void* out, long
     rc = check_common(p, "conv2d3x3");
     if (rc) return rc;
     return launch_dma<MODE_CONV2D>(p, (hipStream_t)stream, gn_written);
+}
+
+extern "C" int syn3r_conv2d3x3_up4_f16(const void* X, const void* W4, void* out, const void* bias, const void* residual, int NB, int Hi,
+                                       int Wi, int Cin, int Cout, void* gn_partials, size_t gn_partials_bytes, int* gn_written,
+                                       void* stream) {
+    if (gn_written) *gn_written = 0;
+    SYN3R_REQUIRE(X && W4 && out, "conv2d3x3_up4: null operand");
+    SYN3R_REQUIRE(!residual, "conv2d3x3_up4: the phase form takes no residual (use syn3r_conv2d3x3_f16 with upsample = 1)");
+    SYN3R_REQUIRE(SYN3R_DIM_OK(NB) && SYN3R_SIDE_OK(Hi) && SYN3R_SIDE_OK(Wi) && SYN3R_DIM_OK(Cin) && SYN3R_DIM_OK(Cout), "conv2d3x3_up4: bad sizes");
+    // (K = 4 Cin in whole k-tiles would ask for Cin % 16 == 0 only; a k-tile of the gather is 64 channels of ONE tap)
+    SYN3R_REQUIRE(Cin % BK == 0, "conv2d3x3_up4: Cin=%d must be a multiple of %d (a k-tile is %d channels of one tap)", Cin, BK, BK);
+    SYN3R_REQUIRE(Cout % 8 == 0, "conv2d3x3_up4: Cout=%d must be a multiple of 8", Cout);
+    const long long M4 = (long long)NB * Hi * Wi;
+    SYN3R_REQUIRE(M4 < (1ll << 24), "conv2d3x3_up4: %lld input pixels (the phase form takes fewer than 2^24)", M4);
+    SYN3R_REQUIRE(M4 * Cin * 2 < (1ll << 32) - (1 << 20) && (long long)Cout * 4 * Cin < (1ll << 29), "conv2d3x3_up4: operand too large");
+    SYN3R_REQUIRE(((uintptr_t)X | (uintptr_t)W4 | (uintptr_t)out | (uintptr_t)bias) % 16 == 0, "conv2d3x3_up4: operands must be 16-byte aligned");
+    SYN3R_REQUIRE((gn_partials == nullptr) == (gn_partials_bytes == 0), "conv2d3x3_up4: gn_partials pointer and size must both be given or both be zero");
+    SYN3R_REQUIRE(((uintptr_t)gn_partials % 16) == 0, "conv2d3x3_up4: the gn_partials buffer must be 16-byte aligned");
+    GemmParams p{};
+    p.A = (const __half*)X; p.W = (const __half*)W4; p.out = (__half*)out; p.ldc = Cout; p.bias = (const __half*)bias;
+    p.s_acc = 1.0f; p.s_res = 0.f; p.s_aux = 0.f;
+    p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.stride = 1; p.ups = 0; p.pad = 1; p.Ho = Hi; p.Wo = Wi;
+    p.M = (int)M4; p.N = Cout; p.K = 4 * Cin;
+    // partial sums: whole 32-row blocks per image and phase (the slot order of gn_tile_stats<.., UP4>), else "not written"
+    if (gn_partials && ((long long)Hi * Wi) % 32 == 0 && Cout % 80 == 0 && gn_partials_bytes >= ::gn_partials_bytes(4 * M4, Cout)) {
+        p.gn_part = (float*)gn_partials; p.gn_units = Cout / 10; p.up4_bpi = Hi * Wi / 32;
+    }
+    return launch_z_up4(p, (hipStream_t)stream, gn_written);
 }
 
 extern "C" int syn3r_conv2d3x3_act_f16(const void* X, const void* W, void* out, const void* bias, int relu, const void* relu_mask,

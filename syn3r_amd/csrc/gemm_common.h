@@ -82,6 +82,8 @@ struct GemmParams {
     // k_gemm_z convolution modes (round 6): bytes of the input tensor, the extent of the buffer resource the A pieces are fetched
     // through - a padded chunk is an out-of-range offset and the LDS-DMA writes zeros (tools/ubench/buffer_lds_oob.hip)
     unsigned a_bytes;
+    // k_gemm_z<.., UP4> (the four-phase upsampling convolution): 32-row blocks per image and phase (Hi Wi / 32) when gn_part is set
+    int up4_bpi;
 };
 
 // element offset of (row m, column d) in the A-tiled layout of a matrix with D columns

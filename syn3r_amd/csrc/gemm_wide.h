@@ -46,8 +46,10 @@ __device__ unsigned long long g_wide_timing[64];
 // belongs to (compile-time: pair p of the 40 pairs of a row is unit p / 5), then the 32 lanes of a half are folded: one
 // v_permlane16_swap + add per unit leaves the sums of x on the even 16-lane rows and the sums of x^2 on the odd ones, four DPP
 // row rotations finish each.  Fixed order throughout: bitwise reproducible.  ~140 (NI = 4) / ~70 vector instructions per call.
-template <int NI>
-__device__ __forceinline__ void gn_tile_stats(const GemmParams& p, const __half* st, int lane, int gm0, int gn0, int N) {
+// UP4 (k_gemm_z's four-phase upsampling convolution): m counts the rows of phase `ph`, whose 32-row block lb of image n is slot
+// (4 n + ph) * up4_bpi + lb - an image's slots stay contiguous and a slot's rows lie in one image, which is all the consumer needs.
+template <int NI, bool UP4 = false>
+__device__ __forceinline__ void gn_tile_stats(const GemmParams& p, const __half* st, int lane, int gm0, int gn0, int N, int ph = 0) {
     typedef _Float16 half2e __attribute__((ext_vector_type(2)));
     constexpr int NU = NI == 4 ? 8 : 4, NC = NI == 4 ? 10 : 5;
     const int row = NI == 4 ? lane : (lane & 31);
@@ -82,16 +84,22 @@ __device__ __forceinline__ void gn_tile_stats(const GemmParams& p, const __half*
         const int m = gm0 + (NI == 4 ? 32 * (rowp >> 1) : 0);
         const int n = gn0 + (NI == 4 ? 0 : 40 * (rowp >> 1));
         if (m < p.M && n < N) {
-            float* dst = p.gn_part + ((size_t)(m >> 5) * 2 + (rowp & 1)) * (size_t)p.gn_units + n / 10;
+            int slot = m >> 5;
+            if constexpr (UP4) { const int img = slot / p.up4_bpi; slot += (3 * img + ph) * p.up4_bpi; }
+            float* dst = p.gn_part + ((size_t)slot * 2 + (rowp & 1)) * (size_t)p.gn_units + n / 10;
 #pragma unroll
             for (int u = 0; u < NU; u += 4) *(float4v*)(dst + u) = (float4v){w[u], w[u + 1], w[u + 2], w[u + 3]};
         }
     }
 }
 
-template <int NI, bool HOIST = false>
+// UP4 (no residual / aux): row m of the tile is stored to output row `orow` of lane m - gm0 (k_gemm_z's four-phase upsampling
+// convolution, NI = 4: one lane per row of the wavefront's tile)
+template <int NI, bool HOIST = false, bool UP4 = false>
 __device__ __forceinline__ void lean_store(const GemmParams& p, float4v (*acc)[TN], __half* st, int lane, int gm0,
-                                           int gn0, int N, const __half* bias, const __half* residual, const __half* aux, bool full) {
+                                           int gn0, int N, const __half* bias, const __half* residual, const __half* aux, bool full,
+                                           int orow = 0, int ph = 0) {
+    static_assert(!UP4 || NI == 4, "UP4: one lane per row of the tile");
     typedef _Float16 half4e __attribute__((ext_vector_type(4)));
     const int fr = lane & 15, fq = lane >> 4;
     // per-sample row vector (time embedding / folded cross-attention): row m takes rowvec[m / rows_per_vec] (or
@@ -167,10 +175,10 @@ __device__ __forceinline__ void lean_store(const GemmParams& p, float4v (*acc)[T
     __builtin_amdgcn_wave_barrier();      // the staging area is the wavefront's own: program order is enough
     static_assert(NI % 2 == 0, "lean_store: an even number of row tiles");
     constexpr int NQ = NI * 16 * (WN / 8) / 64;   // 10 (NI = 4) or 5 (NI = 2) chunks of 16 bytes per lane
-    auto put = [&](int m, int n, const half8& v) {
+    auto put = [&](int m, int n, const half8& v, int mo = -1) {       // mo: the output row where it is not m (UP4)
         if (!(full || (m < p.M && n < N))) return;
         if (p.out_tiled) OUT_STORE((half8*)(p.out + tiled_off(m, n, N)), v);
-        else OUT_STORE((half8*)(p.out + (long long)m * p.ldc + n), v);
+        else OUT_STORE((half8*)(p.out + (long long)(UP4 ? mo : m) * p.ldc + n), v);
     };
     if (residual && aux) {                // (temporal blend: out = s_acc * y + s_res * residual + s_aux * aux)
         constexpr int RB = 5;             // rounds of five chunks: 2 x 20 registers of prefetched operands
@@ -223,19 +231,22 @@ __device__ __forceinline__ void lean_store(const GemmParams& p, float4v (*acc)[T
         for (int it = 0; it < NQ; ++it) {
             const int q = lane + it * 64, row = q / (WN / 8), ch = q - row * (WN / 8);
             const half8 v = *(const half8*)(st + row * EPI_LD + ch * 8);
-            put(gm0 + row, gn0 + ch * 8, v);
+            if constexpr (UP4) put(gm0 + row, gn0 + ch * 8, v, __builtin_amdgcn_ds_bpermute(row << 2, orow));      // (every lane is active here)
+            else put(gm0 + row, gn0 + ch * 8, v);
         }
     }
     __builtin_amdgcn_wave_barrier();
     if (p.gn_part) {                      // (wave-uniform)
-        gn_tile_stats<NI>(p, st, lane, gm0, gn0, N);
+        gn_tile_stats<NI, UP4>(p, st, lane, gm0, gn0, N, ph);
         __builtin_amdgcn_wave_barrier();
     }
 }
 
+template <bool UP4 = false>
 __device__ __forceinline__ void widep_store(const GemmParams& p, float4v (&acc)[TM][TN], char* epi, int lane, int wv, int gm0,
-                                            int gn0, int N, const __half* bias, const __half* residual, const __half* aux, bool full) {
-    lean_store<TM>(p, acc, (__half*)epi + wv * (WM * EPI_LD), lane, gm0, gn0, N, bias, residual, aux, full);
+                                            int gn0, int N, const __half* bias, const __half* residual, const __half* aux, bool full,
+                                            int orow = 0, int ph = 0) {
+    lean_store<TM, false, UP4>(p, acc, (__half*)epi + wv * (WM * EPI_LD), lane, gm0, gn0, N, bias, residual, aux, full, orow, ph);
 }
 
 __global__ void __launch_bounds__(512, 2) k_gemm_widep(GemmParams p) {

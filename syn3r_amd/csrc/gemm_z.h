@@ -72,16 +72,24 @@ __device__ __forceinline__ void z_wait(half8 (&af)[NAF][TM], half8 (&bf)[RB]) {
 // further - taps 0 and 2 move by 0 / 1 for every pixel, the middle tap by 1 only for EVEN output rows / columns.  So the
 // k-tile offset stays wave-uniform except for two lane-dependent additions, steered by two parity bits per piece that share
 // the validity register (4 x 6 validity bits + 4 x 2 parity bits = 32).
-template <bool TWOSRC, int MODE, bool UPS = false>
+// UP4 (MODE_CONV2D only): the same nearest-2x upsample + 3 x 3 convolution as FOUR 2 x 2 convolutions at input resolution, one per
+// output parity (py, px) = phase ph = 2 py + px, on weights folded at load (syn3r_pack_upsample4_f16: W is [4][N][2][2][Cin],
+// K = 4 Cin instead of 9 Cin).  p.M is the row count of ONE phase (NB Hi Wi, p.Ho = p.Hi, p.Wo = p.Wi); the tile list is
+// (phase, m-tile, n-tile) with the phase outermost.  Logical row r = input pixel (n, i, j); tap (a, b) reads input pixel
+// (i + py - 1 + a, j + px - 1 + b) - the plain gather below with a 2 x 2 window and a per-tile padding of 1 - py / 1 - px - and the
+// epilogue stores the row to output pixel (n, 2 i + py, 2 j + px).
+template <bool TWOSRC, int MODE, bool UPS = false, bool UP4 = false>
 __global__ void __launch_bounds__(512, 2) k_gemm_z(GemmParams p) {
     static_assert(!UPS || MODE == MODE_CONV2D, "UPS is a conv2d option");
+    static_assert(!UP4 || (MODE == MODE_CONV2D && !UPS), "UP4 is a conv2d option of its own");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wv >> 1, wn = wv & 1;
     const int tiles_n = (p.N + WBN - 1) / WBN;
     const int tiles_m = (p.M + WBM - 1) / WBM;
-    const unsigned nblk = (unsigned)(tiles_m * tiles_n);
+    const unsigned per_ph = (unsigned)(tiles_m * tiles_n);     // tiles of one phase (UP4) / of the launch
+    const unsigned nblk = UP4 ? 4u * per_ph : per_ph;
     const XcdTiles tiles = xcd_tiles(nblk);
     const int nkt = p.K / BK;
     // tile order: bands of 4 tile columns, row-major inside a band (as k_gemm_widep: the 32 tiles an XCD holds at a time are
@@ -89,7 +97,9 @@ __global__ void __launch_bounds__(512, 2) k_gemm_z(GemmParams p) {
     const unsigned bw0 = p.band > 0 ? (unsigned)p.band : 4u;
     const unsigned bw = (unsigned)tiles_n >= bw0 ? bw0 : (unsigned)tiles_n;
     const unsigned band_sz = (unsigned)tiles_m * bw, full_bands = (unsigned)tiles_n / bw;
-    auto tile_origin = [&](unsigned tile, int& m0, int& n0, int& tn) {
+    auto tile_origin = [&](unsigned tile, int& m0, int& n0, int& tn, int& ph) {
+        ph = 0;
+        if constexpr (UP4) { const unsigned q = tile / per_ph; ph = (int)q; tile -= q * per_ph; }
         unsigned b = tile / band_sz, w = bw, t2 = tile - b * band_sz;
         if (b >= full_bands) { b = full_bands; t2 = tile - full_bands * band_sz; w = (unsigned)tiles_n - full_bands * bw; }
         tn = (int)(b * bw + t2 % w);
@@ -105,7 +115,7 @@ __global__ void __launch_bounds__(512, 2) k_gemm_z(GemmParams p) {
     const char* abase = (const char*)p.A;
     const int kt_switch = TWOSRC ? p.K1 / BK : 0x7fffffff;
     unsigned c_tl = blockIdx.x / 8;                            // cursor: position in the tile list ...
-    int c_ks = 0, c_m0 = 0;                                    // ... k-tile inside that tile, its row origin
+    int c_ks = 0, c_m0 = 0, c_ph = 0;                          // ... k-tile inside that tile, its row origin (UP4: and phase)
     unsigned c_slot = 0;                                       // ring slot (byte offset) of the stage being requested
     unsigned voff_a, voff_a2 = 0, voff_b;                      // per-lane byte offset inside a piece
     {
@@ -163,7 +173,15 @@ __global__ void __launch_bounds__(512, 2) k_gemm_z(GemmParams p) {
                 unsigned r, x;
                 const unsigned n = udiv(m, d_hw, r_hw, r), y = udiv(r, d_w, r_w, x);
                 unsigned f = 0;
-                if constexpr (UPS) {
+                if constexpr (UP4) {
+                    const int y0 = (int)y + (c_ph >> 1) - 1, x0 = (int)x + (c_ph & 1) - 1;       // input pixel of tap (0, 0) of this phase
+                    cv_base[i] = (unsigned)(((int)(n * (unsigned)p.Hi) + y0) * p.Wi + x0) * (unsigned)p.Cin * 2u + lanechunk;
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) {
+                        f |= (unsigned)(y0 + t >= 0 && y0 + t < p.Hi) << t;
+                        f |= (unsigned)(x0 + t >= 0 && x0 + t < p.Wi) << (3 + t);
+                    }
+                } else if constexpr (UPS) {
                     const int yu = (int)y - 1, xu = (int)x - 1;          // tap (0, 0) on the upsampled grid (stride 1, pad 1)
                     const int y0 = yu >> 1, x0 = xu >> 1;                // its input pixel (-1 for the padding row / column)
                     cv_base[i] = (unsigned)(((int)(n * (unsigned)p.Hi) + y0) * p.Wi + x0) * (unsigned)p.Cin * 2u + lanechunk;
@@ -207,7 +225,7 @@ __global__ void __launch_bounds__(512, 2) k_gemm_z(GemmParams p) {
         if (c_tl >= tiles.len) return;                         // exhausted: the previous stage's offsets again
         if (c_ks == 0) {
             int n0_, tn_;
-            tile_origin(tiles.start + c_tl, c_m0, n0_, tn_);
+            tile_origin(tiles.start + c_tl, c_m0, n0_, tn_, c_ph);
             abase = (const char*)p.A;
             second = false;
             if constexpr (MODE != MODE_DENSE) { c_tap = 0; c_left = 0; c_chunk = 0; }
@@ -224,6 +242,7 @@ __global__ void __launch_bounds__(512, 2) k_gemm_z(GemmParams p) {
                 int n = n0_ + (wv * 5 + j) * 8;
                 n = n < p.N - 8 ? n : p.N - 8;
                 ob[j] = 2u * (unsigned)n * (unsigned)p.K;
+                if constexpr (UP4) ob[j] += (unsigned)c_ph * (2u * (unsigned)p.N * (unsigned)p.K);      // the phase's weight panel
             }
             // (convolution modes: whatever vector-memory operation this once-per-tile branch left pending - hipcc spills inside
             // conv_tile - is drained HERE: left to the merge point, the compiler's scoreboard put an s_waitcnt vmcnt(0) behind the
@@ -247,7 +266,8 @@ __global__ void __launch_bounds__(512, 2) k_gemm_z(GemmParams p) {
             for (int j = 0; j < 5; ++j) ob[j] += 2u * BK;
         }
         if constexpr (MODE == MODE_CONV2D) {                   // k-tile (c_chunk, c_tap), taps innermost; ob[] stay the row offsets
-            const int ty = c_tap / 3, tx = c_tap - 3 * ty;
+            constexpr int TW = UP4 ? 2 : 3;                    // filter taps per row / column
+            const int ty = c_tap / TW, tx = c_tap - TW * ty;
             if constexpr (UPS) {
                 tap_off = (((ty == 2 ? p.Wi : 0) + (tx == 2 ? 1 : 0)) * p.Cin + c_chunk * BK) * 2;
                 add_y = ty == 1 ? (unsigned)(p.Wi * p.Cin * 2) : 0u;
@@ -257,7 +277,7 @@ __global__ void __launch_bounds__(512, 2) k_gemm_z(GemmParams p) {
             }
             tap_mask = (1u << ty) | (8u << tx);
             kb = (unsigned)(c_tap * p.Cin + c_chunk * BK) * 2u;
-            if (++c_tap == 9) { c_tap = 0; ++c_chunk; }
+            if (++c_tap == TW * TW) { c_tap = 0; ++c_chunk; }
         } else if constexpr (MODE == MODE_TCONV) {
             if (c_left == 0) { conv_tap(c_tap); ++c_tap; c_left = cpb; }
             else {
@@ -369,8 +389,8 @@ __global__ void __launch_bounds__(512, 2) k_gemm_z(GemmParams p) {
 #define ZSTAMP(i)
 #endif
     for (unsigned tl = blockIdx.x / 8; tl < tiles.len; tl += tiles.stride) {
-        int m0, n0, tile_n;
-        tile_origin(tiles.start + tl, m0, n0, tile_n);
+        int m0, n0, tile_n, ph;
+        tile_origin(tiles.start + tl, m0, n0, tile_n, ph);
         // Convolution modes (round 6): the per-lane gather state of THIS tile is rebuilt here (it was built once already, one k-tile
         // before the previous tile's epilogue, for the cross-tile request of stage 0).  Carried across the epilogue instead, hipcc
         // kept it in scratch for the whole kernel and reloaded it inside the k-loop - scratch_load + s_waitcnt vmcnt(0) in front of
@@ -499,8 +519,18 @@ __global__ void __launch_bounds__(512, 2) k_gemm_z(GemmParams p) {
         } else {
             const int gn0 = n0 + wn * 160;
             const bool full = gm0 + WM <= p.M && gn0 + 160 <= p.N;
-            widep_store(p, acc[0], epi, le, wv, gm0, gn0, p.N, p.bias, p.residual, p.aux, full);
-            widep_store(p, acc[1], epi, le, wv, gm0, gn0 + WN, p.N, p.bias, p.residual, p.aux, full);
+            if constexpr (UP4) {
+                // lane l holds the output row of logical row gm0 + l (rows past the phase: the last row's, never stored)
+                unsigned m = (unsigned)(gm0 + le), r, x;
+                m = m < (unsigned)p.M ? m : (unsigned)p.M - 1u;
+                const unsigned n = udiv(m, d_hw, r_hw, r), y = udiv(r, d_w, r_w, x);
+                const int orow = (int)((n * 2u * (unsigned)p.Hi + 2u * y + (unsigned)(ph >> 1)) * 2u * (unsigned)p.Wi + 2u * x + (unsigned)(ph & 1));
+                widep_store<true>(p, acc[0], epi, le, wv, gm0, gn0, p.N, p.bias, nullptr, nullptr, full, orow, ph);
+                widep_store<true>(p, acc[1], epi, le, wv, gm0, gn0 + WN, p.N, p.bias, nullptr, nullptr, full, orow, ph);
+            } else {
+                widep_store(p, acc[0], epi, le, wv, gm0, gn0, p.N, p.bias, p.residual, p.aux, full);
+                widep_store(p, acc[1], epi, le, wv, gm0, gn0 + WN, p.N, p.bias, p.residual, p.aux, full);
+            }
         }
         // every wavefront is done with the staging area before the next tile's first DMA piece refills that slot
         __builtin_amdgcn_s_barrier();

@@ -420,6 +420,14 @@ int pack_weights(syn3r_unet& m, const StFile& f, std::vector<HostPack>& packs) {
         b.resize((b.size() + 7) / 8 * 8, 0);
         for (auto& hp : packs) if (hp.name == "conv_out.bias") { hp.rows = (long long)b.size(); hp.cols = 1; hp.d = b; }
     }
+    // the upsamplers' 3x3 weights folded into four 2x2 phase filters (ops.pack_upsample4; the OHWI pack above is their source)
+    for (size_t i = 0, n = packs.size(); i < n; ++i) {
+        if (!has_suffix(packs[i].name, ".upsamplers.0.conv.weight")) continue;
+        const long long O = packs[i].rows, I = packs[i].cols / 9;
+        HostPack hp; hp.name = packs[i].name + "_up4"; hp.rows = 4 * O; hp.cols = 4 * I; hp.d.resize((size_t)(16 * O * I));
+        if (syn3r_pack_upsample4_f16(packs[i].d.data(), hp.d.data(), (int)O, (int)I) != SYN3R_OK) return SYN3R_E_INVALID;
+        packs.push_back(std::move(hp));
+    }
     // fused qkv; GEGLU row groups; stacked time-embedding projections
     for (auto& kv : names) {
         const std::string& k = kv.first;
@@ -498,6 +506,40 @@ int pack_weights(syn3r_unet& m, const StFile& f, std::vector<HostPack>& packs) {
 }
 
 }  // namespace
+
+// The fold rule of the four-phase upsampling convolution (include/syn3r_hip.h): pure host code, the twin of ops.pack_upsample4.
+// After a nearest-2x upsample the 3x3 window of an output pixel of parity (py, px) covers a 2x2 block of input pixels; filter rows
+// ty fall on block row a as  py = 0: {0} | {1, 2},  py = 1: {0, 1} | {2}  (columns the same with px).  Each folded weight is the
+// sum of its 1, 2 or 4 source taps in fp32, taken in ascending (ty, tx) order and rounded once to fp16 (nearest even).
+extern "C" int syn3r_pack_upsample4_f16(const void* w, void* w4, int Cout, int Cin) {
+    SYN3R_REQUIRE(w && w4, "pack_upsample4: null operand");
+    SYN3R_REQUIRE(Cout > 0 && Cin > 0 && Cout <= (1 << 15) && Cin <= (1 << 15), "pack_upsample4: bad sizes Cout=%d Cin=%d", Cout, Cin);
+    const _Float16* src = (const _Float16*)w;
+    _Float16* dst = (_Float16*)w4;
+    const size_t C = (size_t)Cin;
+    for (int ph = 0; ph < 4; ++ph) {
+        const int py = ph >> 1, px = ph & 1;
+        for (int o = 0; o < Cout; ++o)
+            for (int a = 0; a < 2; ++a)
+                for (int b = 0; b < 2; ++b) {
+                    const int ty0 = py == 0 ? (a == 0 ? 0 : 1) : (a == 0 ? 0 : 2), ty1 = py == 0 ? (a == 0 ? 0 : 2) : (a == 0 ? 1 : 2);
+                    const int tx0 = px == 0 ? (b == 0 ? 0 : 1) : (b == 0 ? 0 : 2), tx1 = px == 0 ? (b == 0 ? 0 : 2) : (b == 0 ? 1 : 2);
+                    _Float16* d = dst + ((((size_t)ph * Cout + o) * 2 + a) * 2 + b) * C;
+                    for (size_t c = 0; c < C; ++c) {
+                        float s = 0.f;
+                        bool first = true;
+                        for (int ty = ty0; ty <= ty1; ++ty)
+                            for (int tx = tx0; tx <= tx1; ++tx) {
+                                const float v = (float)src[(((size_t)o * 3 + ty) * 3 + tx) * C + c];
+                                s = first ? v : s + v;
+                                first = false;
+                            }
+                        d[c] = (_Float16)s;
+                    }
+                }
+    }
+    return SYN3R_OK;
+}
 
 namespace {
 int unet_create_impl(const char* weights_dir, const char* variant, syn3r_unet** out);
@@ -729,6 +771,16 @@ struct Run {
         if (go())
             chk(syn3r_conv2d3x3_f16(x.p, wt->p, out.p, Cout, Wp(bname), e.rowvec, e.ldrv, e.rows_per_vec, e.residual ? e.residual->p : nullptr,
                                     e.residual ? Cout : 0, e.s_acc, e.s_res, NB, Hi, Wi, Cin, Cout, stride, ups ? 1 : 0, 1, out.gnp, gnb, &out.gn_ok, stream));
+        return out;
+    }
+    // nearest-2x upsample + 3x3 convolution in its four-phase form (ops.conv3x3_up4; weights folded by pack_weights)
+    T conv3x3_up4(const T& x, int NB, int Hi, int Wi, int Cin, const std::string& wname, const std::string& bname, int* Ho_, int* Wo_) {
+        const Wt* wt = W(wname + "_up4");
+        const int Cout = wt ? (int)(wt->rows / 4) : 0;
+        *Ho_ = 2 * Hi; *Wo_ = 2 * Wi;
+        T out = make((long long)NB * 4 * Hi * Wi, Cout);
+        const size_t gnb = gn_begin(out, true);
+        if (go()) chk(syn3r_conv2d3x3_up4_f16(x.p, wt->p, out.p, Wp(bname), nullptr, NB, Hi, Wi, Cin, Cout, out.gnp, gnb, &out.gn_ok, stream));
         return out;
     }
     T tconv3(const T& x, const std::string& wname, const std::string& bname, int HW, const Epi& e) {
@@ -1103,7 +1155,7 @@ struct Run {
             }
             if (bp.resample) {
                 int Ho, Wo;
-                T y = conv3x3(x, B * F, h, w, bp.ch, bpre + ".upsamplers.0.conv.weight", bpre + ".upsamplers.0.conv.bias", 1, true, Epi(), &Ho, &Wo);
+                T y = conv3x3_up4(x, B * F, h, w, bp.ch, bpre + ".upsamplers.0.conv.weight", bpre + ".upsamplers.0.conv.bias", &Ho, &Wo);
                 drop(x);
                 h = Ho; w = Wo;
                 x = y;

@@ -283,6 +283,8 @@ class UNetSpatioTemporalConditionModel:
                 if w.shape[0] % 8:                                                     # conv_out: pad Cout to 8
                     w = Fn.pad(w, (0, 0, 0, 0, 0, 0, 0, 8 - w.shape[0] % 8))
                 pk[k] = w.permute(0, 2, 3, 1).contiguous()
+                if k.endswith(".upsamplers.0.conv.weight"):                            # four 2x2 phase filters (ops.conv3x3_up4)
+                    pk[k + "_up4"] = ops.pack_upsample4(pk[k])
             elif k.endswith(".weight") and t.dim() == 5:                               # Conv3d (3,1,1)
                 pk[k] = t[..., 0, 0].permute(0, 2, 1).contiguous()
             elif k.endswith("conv_shortcut.weight"):
@@ -595,8 +597,8 @@ class UNetSpatioTemporalConditionModel:
                     x = self._transformer(f"up_blocks.{i}.attentions.{j}", x, st, cout, blk["heads"])
             if blk["up"]:
                 ch = blk["ch"]
-                x = ops.conv3x3(x.view(B * F, st["h"], st["w"], ch), W(f"up_blocks.{i}.upsamplers.0.conv.weight"),
-                                W(f"up_blocks.{i}.upsamplers.0.conv.bias"), upsample=True, gn_stats=TUNE["gn_epilogue"])
+                x = ops.conv3x3_up4(x.view(B * F, st["h"], st["w"], ch), W(f"up_blocks.{i}.upsamplers.0.conv.weight_up4"),
+                                    W(f"up_blocks.{i}.upsamplers.0.conv.bias"), gn_stats=TUNE["gn_epilogue"])
                 st["h"], st["w"] = x.shape[1], x.shape[2]
                 x = ops.keep_gn(x.view(-1, ch), x)
         # 6. out (:481-486)

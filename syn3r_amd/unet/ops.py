@@ -261,6 +261,45 @@ def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] 
     return _gn_collect(out, part, gn[2])
 
 
+def pack_upsample4(weight: torch.Tensor) -> torch.Tensor:
+    """Fold the [Cout,3,3,Cin] weight (OHWI) of a nearest-2x upsample + 3x3 convolution into the four 2x2 phase filters
+    [4,Cout,2,2,Cin] of `conv3x3_up4`, phase = 2 py + px (include/syn3r_hip.h, syn3r_pack_upsample4_f16: the same rule, bit for
+    bit).  Filter rows fall on the 2x2 block's rows as py = 0: {0} | {1, 2}, py = 1: {0, 1} | {2}, columns the same with px; every
+    folded weight is the fp32 sum of its taps in ascending (ty, tx) order, rounded once to fp16."""
+    if weight.dim() != 4 or tuple(weight.shape[1:3]) != (3, 3):
+        raise ValueError(f"pack_upsample4: weight {tuple(weight.shape)} is not [Cout,3,3,Cin]")
+    groups = (((0,), (1, 2)), ((0, 1), (2,)))
+    w = weight.float()
+    out = torch.empty((4, weight.shape[0], 2, 2, weight.shape[3]), dtype=H, device=weight.device)
+    for py in range(2):
+        for px in range(2):
+            for a in range(2):
+                for b in range(2):
+                    acc = None
+                    for ty in groups[py][a]:
+                        for tx in groups[px][b]:
+                            acc = w[:, ty, tx] if acc is None else acc + w[:, ty, tx]
+                    out[2 * py + px, :, a, b] = acc.to(H)
+    return out
+
+
+def conv3x3_up4(x: torch.Tensor, w4: torch.Tensor, bias: Optional[torch.Tensor] = None, *, gn_stats: bool = False) -> torch.Tensor:
+    """x [NB,Hi,Wi,Cin] NHWC, w4 = pack_upsample4(weight) -> [NB,2Hi,2Wi,Cout]: conv3x3(upsample=True) as four 2x2 convolutions
+    at input resolution, K = 4 Cin (syn3r_conv2d3x3_up4_f16)."""
+    dev = _chk(x, w4, bias)
+    NB, Hi, Wi, Cin = x.shape
+    if w4.dim() != 5 or w4.shape[0] != 4 or tuple(w4.shape[2:]) != (2, 2, Cin):
+        raise ValueError(f"conv3x3_up4: w4 {tuple(w4.shape)} does not match Cin={Cin}")
+    Cout = w4.shape[1]
+    out = torch.empty((NB, 2 * Hi, 2 * Wi, Cout), dtype=H, device=dev)
+    lib = L.load()
+    part, gn = _gn_request(dev, NB * 4 * Hi * Wi, Cout, gn_stats)
+    rc = lib.syn3r_conv2d3x3_up4_f16(L.ptr(x), L.ptr(w4), L.ptr(out), L.ptr(bias), None, NB, Hi, Wi, Cin, Cout, *gn, L.stream_ptr(dev))
+    L.check(rc, "syn3r_conv2d3x3_up4_f16")
+    _count("gemm", 2.0 * NB * 4 * Hi * Wi * Cout * 4 * Cin)
+    return _gn_collect(out, part, gn[2])
+
+
 def tconv3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], B: int, F: int, HW: int, *,
            rowvec: Optional[torch.Tensor] = None, rows_per_vec: int = 0, residual: Optional[torch.Tensor] = None,
            s_acc: float = 1.0, s_res: float = 1.0, gn_stats: bool = False) -> torch.Tensor:
