@@ -867,6 +867,57 @@ size_t syn3r_exposure_backward_workspace_bytes(int H, int W);
 int syn3r_exposure_backward(const float* image, const float* A, const float* grad_out, int H, int W, float* grad_image, float* grad_A,
                             int accumulate, void* ws, size_t ws_bytes, void* stream);
 
+/* 3DGS-MCMC density control (EXTENSION: the reference has none; Kheradmand et al., NeurIPS 2024, "3D Gaussian Splatting as Markov
+ * Chain Monte Carlo").  Every constant below is RECALLED from the paper and its released code, neither available to check against:
+ * UNPINNED.  Parameters are the RAW ones of the trainer: xyz [n,3], log-scales [n,3], (w, x, y, z) quaternions [n,4] (normalised
+ * here, / max(|q|, 1e-12)), opacity logits [n], fp32, contiguous, DEVICE memory.  n in [1, 2^24] is checked first in every entry.
+ *
+ * Random numbers are Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85) with counter
+ * (index, 0, tag, step) and key (seed & 0xffffffff, seed >> 32); tag 0 = noise, 1 = sampling.  There is no generator state: the
+ * draw of an index depends on (seed, step, tag, index) alone, not on n, the grid or earlier calls.
+ *
+ * syn3r_mcmc_noise (one launch, in place): xyz_i += scale * gate(o_i) * Sigma_i eps_i with Sigma_i = R diag(exp(ls)^2) R^T,
+ *   o_i = sigmoid(logit_i), gate(o) = 1 / (1 + exp(-100 (0.005 - o))), and eps_i three of the four Box-Muller normals of the four
+ *   words x0..x3 of index i: u(x) = ((x >> 8) + 1) 2^-24 in (0, 1], v(x) = (x >> 8) 2^-24, (eps0, eps1) = sqrt(-2 ln u(x0)) (cospi,
+ *   sinpi)(2 v(x1)), eps2 = sqrt(-2 ln u(x2)) cospi(2 v(x3)).  eps is fp32 arithmetic; everything after it is fp64, rounded to fp32
+ *   once (off-diagonal entries of Sigma cancel).  xyz must not overlap an input; rotations 16-byte aligned.
+ * syn3r_mcmc_reg_step (two launches, no atomics): loss_out[0] = opacity_reg * mean_i sigmoid(logit_i), loss_out[1] = scale_reg *
+ *   mean over 3n of exp(ls); grad_opacity[i] += opacity_reg / n * o (1 - o), grad_log_scales[j] += scale_reg / (3n) * exp(ls_j): the
+ *   gradients with respect to the raw parameters, ADDED in place.  The sums: fp32 per thread, over the wave, over the block's four
+ *   waves in a fixed order, one row per block in ws, then one block in fp64.  The grid depends on n alone: bitwise repeatable.
+ *   ws: syn3r_mcmc_reg_step_workspace_bytes(n) bytes (0 for n outside [1, 2^24]), 16-byte aligned.
+ * syn3r_mcmc_weights (one launch): weights[i] = 0 where logit_i <= dead_logit (dead: decided on the logit, exactly), else
+ *   (unsigned) rintf(sigmoid(logit_i) * 65536), at most 65536 and at least 328 for dead_logit = logit(0.005).
+ * syn3r_mcmc_sample (three launches, integers only): the exclusive prefix sums of weights (32 bits inside chunks of 4096 elements,
+ *   64-bit chunk bases: the total reaches 2^40) and, for every destination d in [0, n + m_extra): src[d] = -1 if d < n and
+ *   weights[d] != 0, or if the total is 0; else r = mulhi64((x0 << 32) | x1, total) with the words of index d and src[d] = the one
+ *   i with excl[i] <= r < excl[i] + weights[i].  counts[i] = the number of destinations that drew i (integer atomics: independent
+ *   of order).  Every element of src [n + m_extra] and counts [n] is written.  weights must not exceed 65536 (larger values give
+ *   draws from a wrong distribution, never an index outside [0, n)).  m_extra in [0, 2^24].
+ *   ws: syn3r_mcmc_sample_workspace_bytes(n) bytes, 16-byte aligned.
+ * syn3r_mcmc_relocate (two launches, in place): a source i with counts[i] > 0 and ratio = min(counts[i] + 1, 51) takes
+ *   o' = clamp(1 - (1 - o)^(1 / ratio), min_opacity, 1 - 2^-23) and scale' = scale * o / sum_{j=1..ratio} sum_{k=0..j-1} C(j-1, k)
+ *   (-1)^k o'^(k+1) / sqrt(k+1) (evaluated as sum_m C(ratio, m) (-1)^(m-1) o'^m / sqrt(m) in fp64); every destination d < n with
+ *   src[d] >= 0 becomes a copy of its source - position, rotation, the feature row of feature_row_len floats - with the source's new
+ *   logit and log-scales.  The first launch writes the destinations from the sources' OLD values, the second rewrites the sources;
+ *   a source must not itself be a destination (true of syn3r_mcmc_sample's output: a source has a non-zero weight, a destination a
+ *   zero one).  moments: a HOST array of 10 device pointers, exp_avg then exp_avg_sq of xyz, features, opacity, log-scales,
+ *   rotations; any may be NULL.  The moments of every touched row (source or destination) are set to zero.
+ * Rejections before any HIP call: n outside [1, 2^24], null pointers, misaligned pointers, outputs overlapping inputs, NaN scalars,
+ * min_opacity outside (0, 1) (SYN3R_E_INVALID), a short workspace (SYN3R_E_WORKSPACE). */
+int syn3r_mcmc_noise(float* xyz, const float* log_scales, const float* rotations, const float* opacity_logits, int n, float scale,
+                     unsigned long long seed, int step, void* stream);
+size_t syn3r_mcmc_reg_step_workspace_bytes(int n);
+int syn3r_mcmc_reg_step(const float* opacity_logits, const float* log_scales, int n, float opacity_reg, float scale_reg,
+                        float* grad_opacity, float* grad_log_scales, float* loss_out, void* ws, size_t ws_bytes, void* stream);
+int syn3r_mcmc_weights(const float* opacity_logits, int n, float dead_logit, unsigned* weights, void* stream);
+size_t syn3r_mcmc_sample_workspace_bytes(int n);
+int syn3r_mcmc_sample(const unsigned* weights, int n, int m_extra, unsigned long long seed, int step, int* src, unsigned* counts,
+                      void* ws, size_t ws_bytes, void* stream);
+int syn3r_mcmc_relocate(int n, const int* src, const unsigned* counts, float* xyz, float* features, int feature_row_len,
+                        float* opacity_logits, float* log_scales, float* rotations, void* const* moments, float min_opacity,
+                        void* stream);
+
 /* One torch.optim.Adam update (no weight decay, no amsgrad) of n fp32 parameters in place, in torch's
  * operation order: exp_avg.lerp_(g, 1-beta1); exp_avg_sq = beta2*exp_avg_sq + (1-beta2)*g*g;
  * param -= lr/(1-beta1^step) * exp_avg / (sqrt(exp_avg_sq)/sqrt(1-beta2^step) + eps).  step is 1-based. */

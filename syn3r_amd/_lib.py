@@ -141,6 +141,13 @@ SIGNATURES = {
     "syn3r_exposure_apply": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
     "syn3r_exposure_backward_workspace_bytes": (c_sz, [c_i, c_i]),
     "syn3r_exposure_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_p, c_sz, c_p]),
+    "syn3r_mcmc_noise": (c_i, [c_p, c_p, c_p, c_p, c_i, c_f, c_ll, c_i, c_p]),
+    "syn3r_mcmc_reg_step_workspace_bytes": (c_sz, [c_i]),
+    "syn3r_mcmc_reg_step": (c_i, [c_p, c_p, c_i, c_f, c_f, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "syn3r_mcmc_weights": (c_i, [c_p, c_i, c_f, c_p, c_p]),
+    "syn3r_mcmc_sample_workspace_bytes": (c_sz, [c_i]),
+    "syn3r_mcmc_sample": (c_i, [c_p, c_i, c_i, c_ll, c_i, c_p, c_p, c_p, c_sz, c_p]),
+    "syn3r_mcmc_relocate": (c_i, [c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_f, c_p]),
     "syn3r_adam_step": (c_i, [c_p, c_p, c_p, c_p, c_ll, c_f, c_f, c_f, c_f, c_i, c_p]),
     "syn3r_adam_step_multi": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p]),
     "syn3r_adam_step_multi_rows": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p]),

@@ -118,6 +118,27 @@ class OptimizationParams:
     exposure_lr: float = 0.01
     exposure_lr_final: Optional[float] = None
     exposure_lr_max_steps: int = 30_000
+    # 3DGS-MCMC density control (EXTENSION: the reference has none; Kheradmand et al., NeurIPS 2024 - what a user of gsplat's MCMC
+    # strategy expects of a sparse-view trainer: no scene-dependent gradient thresholds, a budget, no opacity reset).  With `mcmc` the
+    # clone / split / prune control and its opacity reset do not run; instead (`gs/mcmc.py`, csrc/mcmc.hip), every `mcmc_interval`
+    # iterations inside (`densify_from_iter`, `mcmc_until_iter`), dead Gaussians (opacity <= `mcmc_min_opacity`) are relocated onto
+    # live ones drawn in proportion to their opacity and N grows by 5 % towards `mcmc_cap_max`, after which N, every allocation and the
+    # binning capacities stay fixed; every step adds position noise Sigma eps, gated to low-opacity Gaussians, of scale `mcmc_noise_lr`
+    # x the position group's rate (0: no launch); the loss gains `mcmc_opacity_reg` x mean opacity + `mcmc_scale_reg` x mean scale, on
+    # the plain opacity and scales (not the `filter_3d` ones).  No host read in a step or in a control call.  The draws are a
+    # function of (`seed`, iteration, index): nothing new in checkpoints.  Not combinable with `use_proximity_densify` or
+    # `densify_abs_grad`, and `mcmc_cap_max` must not be below the initial N (ValueError).  All eight values are RECALLED from the
+    # paper and its released code, which are not available to check against: UNPINNED; the step on which the control runs skips the
+    # optimiser step (the trainer's rule; the paper's loop does not): UNPINNED.  Off by default: every render, gradient, launch,
+    # checkpoint file and decision is what it was.
+    mcmc: bool = False
+    mcmc_cap_max: int = 200_000                 # recalled, UNPINNED (scene dependent: the released configurations set it per scene)
+    mcmc_noise_lr: float = 5e5                  # recalled, UNPINNED
+    mcmc_opacity_reg: float = 0.01              # recalled, UNPINNED
+    mcmc_scale_reg: float = 0.01                # recalled, UNPINNED
+    mcmc_interval: int = 100                    # recalled, UNPINNED
+    mcmc_until_iter: int = 25_000               # recalled, UNPINNED
+    mcmc_min_opacity: float = 0.005             # recalled, UNPINNED
 
 
 def expon_lr(step, lr_init: float, lr_final: float, lr_delay_steps: int = 0, lr_delay_mult: float = 1.0,

@@ -9,9 +9,10 @@ heuristics (out of scope).
 
 `GSTrainer` holds construction, the optimiser and its learning rate, camera registration, checkpoints, the two step routes and
 the loop.  What it is made of lives beside it and is re-exported here: the cameras and their registry (`camera.py`), the Gaussians
-(`gaussian_model.py`), the options and `expon_lr` (`params.py`); and four objects it owns, each with the state of one concern:
-adaptive density control (`density.DensityControl`), the camera-gradient table of pose refinement (`pose.PoseTable`), the
-3D filter's camera table (`filter3d.Filter3DCache`) and the per-camera exposure (`exposure.ExposureControl`).
+(`gaussian_model.py`), the options and `expon_lr` (`params.py`); and five objects it owns, each with the state of one concern:
+adaptive density control (`density.DensityControl`) and what takes its seat with `opt.mcmc` (`mcmc.MCMCControl`), the
+camera-gradient table of pose refinement (`pose.PoseTable`), the 3D filter's camera table (`filter3d.Filter3DCache`) and the
+per-camera exposure (`exposure.ExposureControl`).
 """
 from __future__ import annotations
 
@@ -31,10 +32,12 @@ from .exposure import CAMERA_KINDS as EXPOSURE_CAMERA_KINDS
 from .exposure import ExposureControl
 from .filter3d import Filter3DCache
 from .gaussian_model import SH_C0, GaussianModel, build_rotation  # noqa: F401
+from .mcmc import MCMCControl
 from .params import OptimizationParams, expon_lr
 from .pose import PoseTable
 from .train_ops import FusedAdam, depth_correlation_loss, image_metrics, l1_loss, photometric_loss
 from .train_ops import depth_correlation_loss_step, exposure_apply, exposure_apply_step, l1_loss_step, photometric_loss_step
+from .train_ops import mcmc_noise, mcmc_reg_step
 
 
 class GSTrainer:
@@ -56,7 +59,15 @@ class GSTrainer:
             raise ValueError(f"OptimizationParams.pose_opt_cameras must be 'train', 'pseudo' or 'all', got {self.opt.pose_opt_cameras!r}")
         if self.opt.exposure_cameras not in EXPOSURE_CAMERA_KINDS:
             raise ValueError(f"OptimizationParams.exposure_cameras must be 'pseudo', 'train' or 'all', got {self.opt.exposure_cameras!r}")
+        if self.opt.mcmc:
+            if self.opt.use_proximity_densify or self.opt.densify_abs_grad:
+                raise ValueError("OptimizationParams.mcmc replaces the clone / split / prune control: use_proximity_densify and "
+                                 "densify_abs_grad are rules of that control and cannot be combined with it")
+            if int(self.opt.mcmc_cap_max) < int(gaussians._xyz.shape[0]):
+                raise ValueError(f"OptimizationParams.mcmc_cap_max = {self.opt.mcmc_cap_max} is below the initial number of Gaussians, "
+                                 f"{int(gaussians._xyz.shape[0])}")
         self.density = DensityControl(self)           # adaptive density control: every change of the set of Gaussians
+        self.mcmc = MCMCControl(self)                 # `opt.mcmc`: relocation and growth to a cap in the density control's seat
         self.filter3d = Filter3DCache()               # `opt.filter_3d`: the camera table and the age of `gaussians.filter_3D`
         self.pose = PoseTable(self)                   # `opt.pose_opt`: the camera-gradient table and its counts
         self.exposure = ExposureControl(self)         # `opt.exposure_opt`: which cameras have an exposure, its gradient and its Adam step
@@ -374,6 +385,10 @@ class GSTrainer:
                 camera_grad_out=None if pose_row is None else self.pose.table[pose_row], camera_grad_accumulate=True)
             self.pose.count(pose_row)
             g._xyz.grad, g._features.grad, g._opacity.grad, g._scaling.grad, g._rotation.grad = d_m3, d_sh, d_lg.reshape(g._opacity.shape), d_ls, d_rr
+            if self.opt.mcmc:                         # the two L1 regularisers: values to the loss, gradients ADDED to the raw ones
+                reg = mcmc_reg_step(g._opacity.detach(), g._scaling.detach(), self.opt.mcmc_opacity_reg, self.opt.mcmc_scale_reg,
+                                    g._opacity.grad, g._scaling.grad)
+                loss = loss + (reg[0] + reg[1])
         out = {"render": color, "depth": depth, "alpha": alpha, "viewspace_grad": d_m2, "visibility_filter": None,      # visible = radii > 0: add_densification_stats takes it from `radii` on the device
                "radii": radii, **extra}
         return loss, out
@@ -397,6 +412,9 @@ class GSTrainer:
         prior = self._depth_term_prior(cam)
         if prior is not None:
             loss = loss + depth_correlation_loss(out["depth"], prior, self.opt.depth_weight, self.opt.depth_offset)
+        if self.opt.mcmc:                             # the two L1 regularisers on the plain opacity and scales (not the filter_3d ones)
+            g = self.gaussians
+            loss = loss + (self.opt.mcmc_opacity_reg * g.get_opacity.mean() + self.opt.mcmc_scale_reg * g.get_scaling.mean())
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         self.pose.count(pose_row)
@@ -421,6 +439,11 @@ class GSTrainer:
         colour transform `cam.exposure` (`gs/exposure.py`); the photometric and LPIPS terms compare E(render) with its target and the
         transform takes one Adam step per step on its camera, on both routes (four more launches: apply, the backward's two, Adam).
         The depth-correlation term and every render the trainer returns keep the scene colour; `exposed` shows what the loss saw.
+        `opt.mcmc` (EXTENSION, default off: every launch is what it was): 3DGS-MCMC (`gs/mcmc.py`, csrc/mcmc.hip).  The loss gains
+        `mcmc_opacity_reg` x mean opacity + `mcmc_scale_reg` x mean scale (`syn3r_mcmc_reg_step` after the rasteriser backward on the
+        explicit route, torch operators on the autograd one), `mcmc.MCMCControl` takes the density control's seat (a step on which it
+        ran skips the optimiser step), and after the optimiser step EVERY step adds the position noise `syn3r_mcmc_noise` with scale
+        `mcmc_noise_lr` x the position group's current rate (0: no launch).  All read the plain scales and opacity.
         `explicit` (default: whenever the LPIPS term is off): the step without autograd (`_explicit_step`).
         The published schedule, when switched on (`OptimizationParams`): `update_learning_rate(iteration + 1)` before the optimiser
         step, `oneupSHdegree()` after every `sh_degree_interval`-th step (the published loop raises it at the top of the next
@@ -436,13 +459,20 @@ class GSTrainer:
         else:
             loss, out = self._autograd_step(cam, lpips_on)
         changed = False
-        if self.densify:
+        if self.densify and self.opt.mcmc:
+            changed = self.mcmc.control(out)  # (True when it ran: a relocation in place changes the set as an append does)
+        elif self.densify:
             n0 = self.gaussians._xyz.shape[0]
             self.density.control(out)
             changed = self.gaussians._xyz.shape[0] != n0
-        self.update_learning_rate(self.iteration + 1)
+        lr_xyz = self.update_learning_rate(self.iteration + 1)
         if not changed:                       # (the gradients of this step belong to the old set of Gaussians)
             self.optimizer.step()
+        if self.opt.mcmc and self.opt.mcmc_noise_lr != 0.0:
+            g = self.gaussians                # SGLD exploration: every step, after the optimiser's, on the plain scales and opacity
+            with torch.no_grad():
+                mcmc_noise(g._xyz.detach(), g._scaling.detach(), g._rotation.detach(), g._opacity.detach(),
+                           float(self.opt.mcmc_noise_lr) * float(lr_xyz), int(self.opt.seed), self.iteration + 1)
         self.iteration += 1
         self.filter3d.tick()                  # (ensure_filter_3D: steps since the filter was computed)
         o = self.opt

@@ -151,6 +151,20 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--exposure_lr_final", type=float, default=None,
                     help="OptimizationParams.exposure_lr_final: the rate decays log-linearly to it over exposure_lr_max_steps (default: "
                          "the trainer's own, None = constant)")
+    ap.add_argument("--mcmc", type=int, default=0, choices=(0, 1),
+                    help="1: EXTENSION (not in the reference) - 3DGS-MCMC density control (OptimizationParams.mcmc): dead Gaussians are "
+                         "relocated onto live ones, N grows 5 %% per call to --mcmc_cap_max and then stays, position noise every step, L1 "
+                         "regularisers on opacity and scale; no clone / split / prune, no opacity reset.  Not with "
+                         "--use_proximity_densify or --densify_abs_grad.  0 (default): the published control")
+    ap.add_argument("--mcmc_cap_max", type=int, default=None,
+                    help="OptimizationParams.mcmc_cap_max: the budget of Gaussians (default: the trainer's own, 200000 - recalled, UNPINNED)")
+    ap.add_argument("--mcmc_noise_lr", type=float, default=None,
+                    help="OptimizationParams.mcmc_noise_lr: noise scale over the position rate, 0 = no noise (default: the trainer's own, "
+                         "5e5 - recalled, UNPINNED)")
+    ap.add_argument("--mcmc_opacity_reg", type=float, default=None,
+                    help="OptimizationParams.mcmc_opacity_reg (default: the trainer's own, 0.01 - recalled, UNPINNED)")
+    ap.add_argument("--mcmc_scale_reg", type=float, default=None,
+                    help="OptimizationParams.mcmc_scale_reg (default: the trainer's own, 0.01 - recalled, UNPINNED)")
     ap.add_argument("--num_inference_steps", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     # FSGS' parameter groups (scripts/train.py:44-46: -s, --eval, --n_views, --resolution, --use_dust3r ... of the batch scripts)
@@ -163,7 +177,8 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                                                        "--densify_abs_grad", "--densify_abs_grad_threshold", "--pose_opt",
                                                        "--pose_opt_cameras", "--pose_lr_rotation", "--pose_lr_translation",
                                                        "--pose_opt_interval", "--exposure_opt", "--exposure_cameras", "--exposure_lr",
-                                                       "--exposure_lr_final"]
+                                                       "--exposure_lr_final", "--mcmc", "--mcmc_cap_max", "--mcmc_noise_lr",
+                                                       "--mcmc_opacity_reg", "--mcmc_scale_reg"]
     # (a token that IS a declared flag is not an abbreviation of a longer one: --densify_abs_grad / --densify_abs_grad_threshold)
     cut = [t for t in given if t.startswith("--") and t.split("=")[0] not in declared
            and any(d.startswith(t.split("=")[0]) for d in declared)]
@@ -197,7 +212,8 @@ def apply_trainer_flags(opt, args):
     untouched.  `--antialiasing 1` sets `antialiasing`, `--filter_3d 1` sets `filter_3d`, `--densify_abs_grad 1` sets `densify_abs_grad`
     (0, the default, leaves the field as `opt` has it); `--densify_abs_grad_threshold`, when given, sets its field.  `--pose_opt 1`
     sets `pose_opt`; `--pose_opt_cameras`, `--pose_lr_rotation`, `--pose_lr_translation` and `--pose_opt_interval`, when given, set theirs.
-    `--exposure_opt 1` sets `exposure_opt`; `--exposure_cameras`, `--exposure_lr` and `--exposure_lr_final`, when given, set theirs.  (--sh_degree
+    `--exposure_opt 1` sets `exposure_opt`; `--exposure_cameras`, `--exposure_lr` and `--exposure_lr_final`, when given, set theirs.
+    `--mcmc 1` sets `mcmc`; `--mcmc_cap_max`, `--mcmc_noise_lr`, `--mcmc_opacity_reg` and `--mcmc_scale_reg`, when given, set theirs.  (--sh_degree
     describes the model, not the optimiser: the scene factory reads it.)"""
     import dataclasses
     new = {}
@@ -225,6 +241,11 @@ def apply_trainer_flags(opt, args):
     if getattr(args, "exposure_opt", 0):
         new["exposure_opt"] = True
     for flag, typ in (("exposure_cameras", str), ("exposure_lr", float), ("exposure_lr_final", float)):
+        if getattr(args, flag, None) is not None:
+            new[flag] = typ(getattr(args, flag))
+    if getattr(args, "mcmc", 0):
+        new["mcmc"] = True
+    for flag, typ in (("mcmc_cap_max", int), ("mcmc_noise_lr", float), ("mcmc_opacity_reg", float), ("mcmc_scale_reg", float)):
         if getattr(args, flag, None) is not None:
             new[flag] = typ(getattr(args, flag))
     return dataclasses.replace(opt, **new)
