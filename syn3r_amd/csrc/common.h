@@ -23,6 +23,16 @@ inline int check_hip(hipError_t e, const char* what) {
     return SYN3R_OK;
 }
 
+// SYN3R_LAUNCH_CHECK("<who> launch") for a host path that serves several entries and carries the entry's name as `who`
+inline int check_launch(const char* who) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_error("%s launch: %s", who, hipGetErrorString(e));
+        return SYN3R_E_HIP;
+    }
+    return SYN3R_OK;
+}
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-DEVICE setting: remembered per (kernel, device), so a host that
 // drives several GPUs from one process gets the large-LDS attribute on each of them.
 struct DevOnce { std::atomic<unsigned long long> done{0}; };
@@ -135,6 +145,9 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// The four wave totals of a 256-thread block (red[wave], written after wave_sum / wave_sum_d and a barrier) in the fixed order
+// (w0 + w1) + (w2 + w3): bitwise reproducible run to run.  Staging and barriers stay with the caller (one barrier may serve several sums).
+template <class T> __device__ __forceinline__ T block_sum4(const T* red) { return (red[0] + red[1]) + (red[2] + red[3]); }
 __device__ __forceinline__ double wave_max_d(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));

@@ -3,7 +3,7 @@ update that `gsTrainer.training()/finetune()` (call sites `model/diffusionGS.py:
 vendored) run as torch elementwise chains.  No CPU fallback: they raise `Syn3rError` without the extension."""
 from __future__ import annotations
 
-from typing import Iterable, List, Optional
+from typing import Iterable, List, NamedTuple, Optional
 
 import torch
 
@@ -550,6 +550,18 @@ def proximity_unpool(xyz: torch.Tensor, log_scales: torch.Tensor, opacity_logits
     return out
 
 
+class _AdamItem(NamedTuple):
+    """One tensor of a `FusedAdam.step` launch table; `row_len` 0: a plain tensor (`lr_tail`, `head_len` unused)."""
+    param: torch.Tensor
+    grad: torch.Tensor
+    state: dict
+    lr: float
+    eps: float
+    lr_tail: float
+    row_len: int
+    head_len: int
+
+
 class FusedAdam:
     """`torch.optim.Adam(param_groups, eps=...)` (no weight decay / amsgrad) with one kernel per parameter tensor.
     Keeps torch's `param_groups` / `state` layout so checkpoints and lr schedules written for the torch optimiser
@@ -589,7 +601,7 @@ class FusedAdam:
         for g in self.param_groups:
             b1, b2 = g["betas"]
             row_len = int(g.get("row_len") or 0)
-            split = (float(g["lr_tail"]), row_len, int(g["head_len"])) if row_len else (0.0, 0, 0)
+            lr_tail, head_len = (float(g["lr_tail"]), int(g["head_len"])) if row_len else (0.0, 0)
             for p in g["params"]:
                 if p.grad is None:
                     continue
@@ -601,21 +613,21 @@ class FusedAdam:
                     st = self.state[p] = {"step": 0, "exp_avg": torch.zeros_like(p), "exp_avg_sq": torch.zeros_like(p)}
                 st["step"] += 1
                 grad = p.grad.contiguous()
-                batches.setdefault((float(b1), float(b2), p.device), []).append((p, grad, st, float(g["lr"]), float(g["eps"]), split))
+                batches.setdefault((float(b1), float(b2), p.device), []).append(
+                    _AdamItem(p, grad, st, float(g["lr"]), float(g["eps"]), lr_tail, row_len, head_len))
         for (b1, b2, dev), items in batches.items():
             for k0 in range(0, len(items), 8):
                 chunk = items[k0:k0 + 8]
                 n = len(chunk)
-                ptrs = lambda sel: (C.c_void_p * n)(*[sel(it) for it in chunk])
-                tables = (n, ptrs(lambda it: it[0].data_ptr()), ptrs(lambda it: it[1].data_ptr()), ptrs(lambda it: it[2]["exp_avg"].data_ptr()),
-                          ptrs(lambda it: it[2]["exp_avg_sq"].data_ptr()), (C.c_longlong * n)(*[it[0].numel() for it in chunk]),
-                          (C.c_float * n)(*[it[3] for it in chunk]))
-                tail = (b1, b2, (C.c_float * n)(*[it[4] for it in chunk]), (C.c_int * n)(*[int(it[2]["step"]) for it in chunk]),
-                        L.stream_ptr(dev))
-                if any(it[5][1] for it in chunk):
-                    rc = lib.syn3r_adam_step_multi_rows(*tables, (C.c_float * n)(*[it[5][0] for it in chunk]),
-                                                        (C.c_int * n)(*[it[5][1] for it in chunk]),
-                                                        (C.c_int * n)(*[it[5][2] for it in chunk]), *tail)
+                ptrs = lambda sel: (C.c_void_p * n)(*[sel(it).data_ptr() for it in chunk])
+                arr = lambda ctype, sel: (ctype * n)(*[sel(it) for it in chunk])
+                tables = (n, ptrs(lambda it: it.param), ptrs(lambda it: it.grad), ptrs(lambda it: it.state["exp_avg"]),
+                          ptrs(lambda it: it.state["exp_avg_sq"]), arr(C.c_longlong, lambda it: it.param.numel()),
+                          arr(C.c_float, lambda it: it.lr))
+                tail = (b1, b2, arr(C.c_float, lambda it: it.eps), arr(C.c_int, lambda it: int(it.state["step"])), L.stream_ptr(dev))
+                if any(it.row_len for it in chunk):
+                    rc = lib.syn3r_adam_step_multi_rows(*tables, arr(C.c_float, lambda it: it.lr_tail), arr(C.c_int, lambda it: it.row_len),
+                                                        arr(C.c_int, lambda it: it.head_len), *tail)
                     L.check(rc, "adam_step_multi_rows")
                 else:
                     rc = lib.syn3r_adam_step_multi(*tables, *tail)

@@ -1,5 +1,5 @@
 """Float64 reference, derived slacks, an fp32 restatement with mutants, the designs and the five checks for the fused photometric
-loss of csrc/train.hip (k_photo_fwd, k_photo_bwd, photo_final; with and without a weight map).
+loss of csrc/photo_loss.hip (k_photo_fwd, k_photo_bwd, photo_final; with and without a weight map).
 
 NumPy / torch on the CPU, no device code: tests/test_photo_elementwise_cpu.py shows without a GPU that a faithful fp32 restatement of
 both kernels meets every check on every design and that subtly wrong kernels (`mutant=`) fail one; tests/test_photo_elementwise_gpu.py
@@ -12,7 +12,7 @@ WORKSPACE (photo_workspace_bytes, photo_forward): three maps [3][C][H][W] - d ss
 the pixel's weight with a map - then 2 floats per tile (sum |d|, sum ssim), 3 with a map (sum m|d|, sum m ssim, sum m);
 tile t = (c gy + tile_y) gx + tile_x.
 
-SLACKS, u = 2^-24, first order.  train.hip is compiled without contraction: every operation written there rounds once.
+SLACKS, u = 2^-24, first order.  photo_loss.hip is compiled without contraction: every operation written there rounds once.
   GAMMA = 24: a window moment passes 11 serial FMAs in the horizontal and 11 in the vertical pass, so the product of one tap pair
     meets at most 22 roundings; + 1 for the rounded input product (p p, q q, p q; the means have none) + 1 for the rounded
     coefficient: 22 + 1 + 1.  |moment - exact| <= GAMMA u sum_taps w |term|.

@@ -1,4 +1,4 @@
-"""The checks of tests/test_photo_elementwise_gpu.py without a GPU: an fp32 restatement of k_photo_fwd and k_photo_bwd (tile geometry,
+"""The checks of tests/test_photo_elementwise_gpu.py without a GPU: an fp32 restatement of k_photo_fwd and k_photo_bwd (csrc/photo_loss.hip: tile geometry,
 row runs, halo indexing, ascending taps; tests/photo_ref.py) meets checks 1 to 5 on every design, so the derived bounds can be met
 by a faithful fp32 implementation before a GPU is asked; each of nine subtly wrong restatements fails the check named for it."""
 import numpy as np

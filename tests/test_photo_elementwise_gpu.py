@@ -1,4 +1,4 @@
-"""The fused photometric loss (csrc/train.hip: k_photo_fwd, k_photo_bwd, photo_final; with and without a weight map) per pixel and per
+"""The fused photometric loss (csrc/photo_loss.hip: k_photo_fwd, k_photo_bwd, photo_final; with and without a weight map) per pixel and per
 tile against float64.
 
 The ABI entries are called directly with a workspace of the test's own, filled with the NaN pattern of tests/poison.py first, so the

@@ -1,4 +1,4 @@
-"""Cost of the per-pixel weight map in the fused photometric loss (csrc/train.hip, `photometric_loss_step(weight_map=)`): device
+"""Cost of the per-pixel weight map in the fused photometric loss (csrc/photo_loss.hip, `photometric_loss_step(weight_map=)`): device
 time per kernel of the step with and without a map at 3x1080x1920 and 3x576x1024 (HIP events on the dispatches, the two variants
 alternating, several rounds so that the run-to-run spread shows), and GSTrainer.training() iterations / s at 200 000 Gaussians /
 1080p with a map on every camera and without (developer tool).
