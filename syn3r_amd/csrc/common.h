@@ -9,11 +9,9 @@
 #include <stdarg.h>
 #include <atomic>
 #include <type_traits>
-#include "../../include/syn3r_hip.h"
+#include "error.h"      // set_error, SYN3R_REQUIRE and the public header: the HIP-free part
 
 namespace syn3r {
-
-void set_error(const char* fmt, ...);
 
 inline int check_hip(hipError_t e, const char* what) {
     if (e != hipSuccess) {
@@ -79,14 +77,6 @@ constexpr int tune_env(const char*, int dflt) { return dflt; }
 #define SYN3R_DIM_OK(x) ((x) > 0 && (x) <= SYN3R_DIM_MAX)
 #define SYN3R_SIDE_MAX (1 << 15)                 /* image height / width */
 #define SYN3R_SIDE_OK(x) ((x) > 0 && (x) <= SYN3R_SIDE_MAX)
-
-#define SYN3R_REQUIRE(cond, ...)                 \
-    do {                                         \
-        if (!(cond)) {                           \
-            syn3r::set_error(__VA_ARGS__);       \
-            return SYN3R_E_INVALID;              \
-        }                                        \
-    } while (0)
 
 // Kernel launch the tracer can time.  A traced launch goes through hipExtLaunchKernelGGL, which attaches the
 // start / stop events to the dispatch packet itself (the kernel's own begin / end timestamps): no marker

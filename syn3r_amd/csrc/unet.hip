@@ -4,35 +4,24 @@
 // added_time_ids=..., return_dict=False)[0]` (model/SVD_2pass_prob_uncertain_post.py:763,786;
 // diffusers/models/unets/unet_spatio_temporal_condition.py:356-489) as ONE call on device pointers, with the weights read
 // from a diffusers checkpoint directory (`from_pretrained(<local dir>, torch_dtype=float16, variant="fp16")`,
-// model/diffusionGS.py:1089).  This file is the host graph only - the same launch sequence, on the same operators of this
-// library (gemm.hip, attn.hip, norm.hip), that syn3r_amd/unet/model.py issues from Python: safetensors reader, weight
-// repacking (OHWI convolutions, fused qkv, GEGLU row groups, stacked time-embedding projections), a stream-ordered arena
-// over the caller's workspace, and the block loops of unet_3d_blocks.py / transformer_temporal.py / resnet.py.
+// model/diffusionGS.py:1089).  This file is the launch graph only - the same launch sequence, on the same operators of this
+// library (gemm.hip, attn.hip, norm.hip), that syn3r_amd/unet/model.py issues from Python: the upload of what the checkpoint
+// reader (unet_ckpt.hip: config.json, safetensors, weight repacking - host code, no device) hands over, a stream-ordered
+// arena over the caller's workspace, and the block loops of unet_3d_blocks.py / transformer_temporal.py / resnet.py.
 // The handful of elementwise steps the Python host leaves to torch (sinusoidal embeddings, SiLU on [B, 1280] vectors,
 // NCHW <-> NHWC at the two ends) are small kernels at the top of the file.
 #include "common.h"
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <fcntl.h>
-#include <unistd.h>
-#include <math.h>
-#include <string.h>
-#include <ctype.h>
+#include "unet_ckpt.h"
 #include <exception>
 #include <map>
 #include <memory>
 #include <algorithm>
-#include <string>
-#include <unordered_map>
 #include <unordered_set>
 #include <mutex>
-#include <vector>
 
 using namespace syn3r;
 
 namespace {
-
-typedef unsigned short u16;
 
 // ------------------------------------------------------------------------------------------------ glue kernels
 // embeddings.py Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0): [cos | sin] of t * exp(-ln(1e4) i / half),
@@ -95,188 +84,15 @@ __global__ void k_cat_cols(const __half* __restrict__ a, int C1, const __half* _
     y[i] = c < C1 ? a[r * C1 + c] : b[r * C2 + (c - C1)];
 }
 
-// ------------------------------------------------------------------------------------------------ JSON (config.json, safetensors header)
-struct JVal {
-    enum Type { NUL, NUM, STR, ARR, OBJ, BOOL } type = NUL;
-    double num = 0;
-    std::string str;
-    std::vector<JVal> arr;
-    std::vector<std::pair<std::string, JVal>> obj;
-    const JVal* get(const char* k) const {
-        for (auto& kv : obj) if (kv.first == k) return &kv.second;
-        return nullptr;
-    }
-};
-struct JParser {
-    const char* p; const char* e; bool ok = true;
-    void ws() { while (p < e && (*p == ' ' || *p == '\n' || *p == '\t' || *p == '\r')) ++p; }
-    bool lit(const char* s) { size_t n = strlen(s); if ((size_t)(e - p) >= n && !memcmp(p, s, n)) { p += n; return true; } return false; }
-    std::string string_() {
-        std::string s;
-        if (p >= e || *p != '"') { ok = false; return s; }
-        ++p;
-        while (p < e && *p != '"') {
-            if (*p == '\\' && p + 1 < e) {
-                ++p;
-                switch (*p) {
-                    case 'n': s += '\n'; break;
-                    case 't': s += '\t'; break;
-                    case 'u':                                  // \uXXXX: not needed for tensor names; the four digits must exist
-                        if (e - p < 5) { ok = false; return s; }
-                        s += '?'; p += 4; break;
-                    default: s += *p;
-                }
-                ++p;
-            } else s += *p++;
-        }
-        if (p >= e) { ok = false; return s; }
-        ++p;
-        return s;
-    }
-    JVal value(int depth = 0) {
-        JVal v;
-        ws();
-        if (p >= e || depth > 64) { ok = false; return v; }
-        if (*p == '{') {
-            v.type = JVal::OBJ; ++p; ws();
-            if (p < e && *p == '}') { ++p; return v; }
-            while (ok) {
-                ws();
-                std::string k = string_();
-                ws();
-                if (p >= e || *p != ':') { ok = false; break; }
-                ++p;
-                v.obj.emplace_back(std::move(k), value(depth + 1));
-                ws();
-                if (p < e && *p == ',') { ++p; continue; }
-                if (p < e && *p == '}') { ++p; break; }
-                ok = false;
-            }
-        } else if (*p == '[') {
-            v.type = JVal::ARR; ++p; ws();
-            if (p < e && *p == ']') { ++p; return v; }
-            while (ok) {
-                v.arr.push_back(value(depth + 1));
-                ws();
-                if (p < e && *p == ',') { ++p; continue; }
-                if (p < e && *p == ']') { ++p; break; }
-                ok = false;
-            }
-        } else if (*p == '"') { v.type = JVal::STR; v.str = string_(); }
-        else if (lit("true")) { v.type = JVal::BOOL; v.num = 1; }
-        else if (lit("false")) { v.type = JVal::BOOL; v.num = 0; }
-        else if (lit("null")) { v.type = JVal::NUL; }
-        else {
-            // the header is a slice of an mmap'd file: not NUL-terminated, so the number is parsed from a bounded copy
-            char buf[64];
-            size_t n = 0;
-            while (p + n < e && n < sizeof(buf) - 1 && (isdigit((unsigned char)p[n]) || p[n] == '-' || p[n] == '+' || p[n] == '.' || p[n] == 'e' || p[n] == 'E')) ++n;
-            memcpy(buf, p, n);
-            buf[n] = 0;
-            char* end = nullptr;
-            v.type = JVal::NUM; v.num = n ? strtod(buf, &end) : 0.0;
-            if (n == 0 || end != buf + n || !(v.num == v.num)) ok = false; else p += n;
-        }
-        return v;
-    }
-};
-
-bool read_file(const std::string& path, std::string& out) {
-    FILE* f = fopen(path.c_str(), "rb");
-    if (!f) return false;
-    char buf[1 << 16];
-    size_t n;
-    while ((n = fread(buf, 1, sizeof buf, f)) > 0) out.append(buf, n);
-    fclose(f);
-    return true;
-}
-
-// ------------------------------------------------------------------------------------------------ safetensors
-struct StEntry { std::string dtype; std::vector<long long> shape; size_t begin = 0, end = 0; };
-struct StFile {
-    int fd = -1; const unsigned char* map = nullptr; size_t size = 0, data0 = 0;
-    std::unordered_map<std::string, StEntry> entries;
-    ~StFile() { if (map) munmap((void*)map, size); if (fd >= 0) close(fd); }
-    bool open_(const std::string& path, std::string& err) {
-        fd = open(path.c_str(), O_RDONLY);
-        if (fd < 0) { err = "cannot open " + path; return false; }
-        struct stat sb;
-        if (fstat(fd, &sb) || sb.st_size < 8) { err = path + ": not a safetensors file"; return false; }
-        size = (size_t)sb.st_size;
-        map = (const unsigned char*)mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-        if (map == MAP_FAILED) { map = nullptr; err = "mmap failed on " + path; return false; }
-        unsigned long long hl = 0;
-        memcpy(&hl, map, 8);
-        if (hl == 0 || hl > size - 8) { err = path + ": bad header length"; return false; }
-        data0 = 8 + (size_t)hl;
-        JParser jp{(const char*)map + 8, (const char*)map + 8 + hl};
-        JVal h = jp.value();
-        if (!jp.ok || h.type != JVal::OBJ) { err = path + ": header is not JSON"; return false; }
-        for (auto& kv : h.obj) {
-            if (kv.first == "__metadata__") continue;
-            const JVal *dt = kv.second.get("dtype"), *sh = kv.second.get("shape"), *off = kv.second.get("data_offsets");
-            if (!dt || !sh || !off || off->arr.size() != 2) { err = path + ": malformed entry " + kv.first; return false; }
-            StEntry en;
-            en.dtype = dt->str;
-            // dimensions and offsets are file contents: integers in [0, 2^53) only, the element count bounded by the file size
-            auto whole = [](const JVal& x) { return x.type == JVal::NUM && x.num >= 0 && x.num < 9007199254740992.0 && x.num == (double)(unsigned long long)x.num; };
-            if (sh->type != JVal::ARR || sh->arr.size() > 8 || !whole(off->arr[0]) || !whole(off->arr[1])) { err = path + ": malformed entry " + kv.first; return false; }
-            unsigned long long count = 1;
-            for (auto& d : sh->arr) {
-                if (!whole(d)) { err = path + ": bad shape in entry " + kv.first; return false; }
-                if (__builtin_mul_overflow(count, (unsigned long long)d.num, &count) || count > (unsigned long long)size) { err = path + ": shape of entry " + kv.first + " exceeds the file"; return false; }
-                en.shape.push_back((long long)d.num);
-            }
-            en.begin = (size_t)off->arr[0].num; en.end = (size_t)off->arr[1].num;
-            if (en.end < en.begin || en.end > size - data0) { err = path + ": entry " + kv.first + " outside the file"; return false; }
-            entries.emplace(kv.first, std::move(en));
-        }
-        return true;
-    }
-};
-
-inline u16 f32_to_f16_bits(float f) { _Float16 h = (_Float16)f; u16 b; memcpy(&b, &h, 2); return b; }
-inline float f16_bits_to_f32(u16 b) { _Float16 h; memcpy(&h, &b, 2); return (float)h; }
-
-// a checkpoint tensor as fp16 bits on the host (F16 as stored; F32 / BF16 rounded once, as `.to(torch.float16)` does)
-bool host_f16(const StFile& f, const StEntry& e, std::vector<u16>& out, std::string& err) {
-    unsigned long long cnt = 1;
-    for (long long d : e.shape)
-        if (d < 0 || __builtin_mul_overflow(cnt, (unsigned long long)d, &cnt)) { err = "bad shape"; return false; }
-    const size_t esz = e.dtype == "F32" ? 4 : ((e.dtype == "F16" || e.dtype == "BF16") ? 2 : 0);
-    if (!esz) { err = "unsupported dtype " + e.dtype; return false; }
-    if (cnt > (e.end - e.begin) / esz || cnt * esz != e.end - e.begin) { err = "size mismatch"; return false; }   // before any allocation
-    const long long n = (long long)cnt;
-    const unsigned char* src = f.map + f.data0 + e.begin;
-    out.resize((size_t)n);
-    if (e.dtype == "F16") {
-        memcpy(out.data(), src, (size_t)n * 2);
-    } else if (e.dtype == "F32") {
-        if ((size_t)n * 4 != e.end - e.begin) { err = "size mismatch"; return false; }
-        for (long long i = 0; i < n; ++i) { float v; memcpy(&v, src + 4 * i, 4); out[(size_t)i] = f32_to_f16_bits(v); }
-    } else if (e.dtype == "BF16") {
-        if ((size_t)n * 2 != e.end - e.begin) { err = "size mismatch"; return false; }
-        for (long long i = 0; i < n; ++i) { unsigned int u = 0; u16 b; memcpy(&b, src + 2 * i, 2); u = (unsigned)b << 16; float v; memcpy(&v, &u, 4); out[(size_t)i] = f32_to_f16_bits(v); }
-    } else { err = "unsupported dtype " + e.dtype; return false; }
-    return true;
-}
-
 // ------------------------------------------------------------------------------------------------ model
 struct Wt { __half* p = nullptr; long long rows = 0, cols = 0; };       // a packed device tensor ([rows, cols], cols = the rest)
-struct BlockPlan { int idx; bool attn; std::vector<std::pair<int, int>> layers; bool resample; int ch, heads; };
 
 }  // namespace
 
-struct syn3r_unet {
+struct syn3r_unet : Checkpoint {                                        // the plan, alpha and temb_slice as read; `packs` is emptied once uploaded
     int device = 0;
-    int in_ch = 8, out_ch = 4, add_dim = 256, proj_in = 768;
-    std::vector<int> boc, heads, layers, cross;
-    std::vector<BlockPlan> down, up;
     char* blob = nullptr; size_t blob_bytes = 0;                        // every packed weight, one allocation
     std::unordered_map<std::string, Wt> w;
-    std::unordered_map<std::string, std::pair<double, double>> alpha;   // mix_factor -> (alpha, 1 - alpha) as the fp16 values the reference uses
-    std::unordered_map<std::string, std::pair<int, int>> temb_slice;
-    std::vector<std::string> temb_names;
     struct PosEmb { __half* p = nullptr; hipEvent_t ready = nullptr; hipStream_t stream = nullptr; };
     std::map<std::string, PosEmb> pos_cache;                            // frame-position embeddings per (block, F, B): functions of the weights only
     bool ff_ln = true, ln_qkv = true;
@@ -292,259 +108,38 @@ bool unet_live(const syn3r_unet* m) {
     return m && unet_registry().count(m);
 }
 
-struct HostPack { std::string name; long long rows, cols; std::vector<u16> d; };
-
-int fail(const char* fmt, const std::string& a) { set_error(fmt, a.c_str()); return SYN3R_E_INVALID; }
-
-std::vector<int> int_list(const JVal* v, size_t n, int dflt) {
-    std::vector<int> r;
-    if (!v) return std::vector<int>(n, dflt);
-    if (v->type == JVal::ARR) { for (auto& x : v->arr) r.push_back((int)x.num); }
-    else r.assign(n, (int)v->num);
-    return r;
-}
-
-// model.py:_declare - the block plan of unet_spatio_temporal_condition.py:140-330
-int build_plan(syn3r_unet& m, const JVal& cfg) {
-    auto num = [&](const char* k, int d) { const JVal* v = cfg.get(k); return v && v->type == JVal::NUM ? (int)v->num : d; };
-    m.in_ch = num("in_channels", 8); m.out_ch = num("out_channels", 4);
-    m.add_dim = num("addition_time_embed_dim", 256); m.proj_in = num("projection_class_embeddings_input_dim", 768);
-    const JVal* b = cfg.get("block_out_channels");
-    m.boc = b ? int_list(b, 0, 0) : std::vector<int>{320, 640, 1280, 1280};
-    const size_t n = m.boc.size();
-    SYN3R_REQUIRE(n >= 1 && n <= 8, "unet_create: %zu levels", n);
-    m.heads = cfg.get("num_attention_heads") ? int_list(cfg.get("num_attention_heads"), n, 0) : std::vector<int>{5, 10, 20, 20};
-    m.layers = int_list(cfg.get("layers_per_block"), n, 2);
-    m.cross = int_list(cfg.get("cross_attention_dim"), n, 1024);
-    std::vector<int> tl = int_list(cfg.get("transformer_layers_per_block"), n, 1);
-    SYN3R_REQUIRE(m.heads.size() == n && m.layers.size() == n && m.cross.size() == n && tl.size() == n, "unet_create: per-level lists of config.json do not match block_out_channels");
-    for (size_t i = 0; i < n; ++i) {
-        SYN3R_REQUIRE(tl[i] == 1, "unet_create: transformer_layers_per_block != 1 is not used by SVD");
-        SYN3R_REQUIRE(m.boc[i] % 64 == 0 && m.boc[i] == 64 * m.heads[i], "unet_create: attention head dim must be 64 (level %zu: %d channels, %d heads)", i, m.boc[i], m.heads[i]);
-        SYN3R_REQUIRE(m.layers[i] >= 1 && m.layers[i] <= 8, "unet_create: layers_per_block");
+int unet_create_impl(const char* weights_dir, const char* variant, syn3r_unet** out) {
+    std::unique_ptr<syn3r_unet> m(new syn3r_unet);
+    int rc = load_checkpoint(weights_dir, variant, *m);
+    if (rc) return rc;
+    rc = check_hip(hipGetDevice(&m->device), "hipGetDevice");
+    if (rc) return rc;
+    size_t total = 0;
+    for (auto& hp : m->packs) total += (hp.d.size() * 2 + 255) / 256 * 256;
+    rc = check_hip(hipMalloc((void**)&m->blob, total ? total : 256), "hipMalloc(unet weights)");
+    if (rc) return rc;
+    m->blob_bytes = total;
+    size_t off = 0;
+    for (auto& hp : m->packs) {
+        rc = check_hip(hipMemcpy(m->blob + off, hp.d.data(), hp.d.size() * 2, hipMemcpyHostToDevice), "hipMemcpy(unet weights)");
+        if (rc) { (void)hipFree(m->blob); return rc; }
+        m->w[hp.name] = Wt{(__half*)(m->blob + off), hp.rows, hp.cols};
+        off += (hp.d.size() * 2 + 255) / 256 * 256;
     }
-    std::vector<std::string> dt, ut;
-    if (const JVal* v = cfg.get("down_block_types")) for (auto& x : v->arr) dt.push_back(x.str);
-    else { dt.assign(n, "CrossAttnDownBlockSpatioTemporal"); dt.back() = "DownBlockSpatioTemporal"; }
-    if (const JVal* v = cfg.get("up_block_types")) for (auto& x : v->arr) ut.push_back(x.str);
-    else { ut.assign(n, "CrossAttnUpBlockSpatioTemporal"); ut.front() = "UpBlockSpatioTemporal"; }
-    SYN3R_REQUIRE(dt.size() == n && ut.size() == n, "unet_create: block type lists do not match block_out_channels");
-    int out_ch = m.boc[0];
-    for (size_t i = 0; i < n; ++i) {
-        const int in_ch = out_ch;
-        out_ch = m.boc[i];
-        const bool attn = dt[i] == "CrossAttnDownBlockSpatioTemporal";
-        if (!attn && dt[i] != "DownBlockSpatioTemporal") return fail("unet_create: %s does not exist", dt[i]);
-        BlockPlan bp{(int)i, attn, {}, i != n - 1, out_ch, m.heads[i]};
-        for (int j = 0; j < m.layers[i]; ++j) bp.layers.emplace_back(j == 0 ? in_ch : out_ch, out_ch);
-        m.down.push_back(bp);
-    }
-    std::vector<int> rev(m.boc.rbegin(), m.boc.rend()), rev_heads(m.heads.rbegin(), m.heads.rend()), rev_layers(m.layers.rbegin(), m.layers.rend());
-    out_ch = rev[0];
-    for (size_t i = 0; i < n; ++i) {
-        const bool attn = ut[i] == "CrossAttnUpBlockSpatioTemporal";
-        if (!attn && ut[i] != "UpBlockSpatioTemporal") return fail("unet_create: %s does not exist", ut[i]);
-        const int prev_out = out_ch;
-        out_ch = rev[i];
-        const int in_ch = rev[std::min(i + 1, n - 1)];
-        const int nl = rev_layers[i] + 1;
-        BlockPlan bp{(int)i, attn, {}, i != n - 1, out_ch, rev_heads[i]};
-        for (int j = 0; j < nl; ++j) {
-            const int res_skip = j == nl - 1 ? in_ch : out_ch, res_in = j == 0 ? prev_out : out_ch;
-            bp.layers.emplace_back(res_in + res_skip, out_ch);
-        }
-        m.up.push_back(bp);
-    }
-    return SYN3R_OK;
-}
-
-// model.py:_pack - the kernel-side layouts, built on the host from the checkpoint's tensors
-int pack_weights(syn3r_unet& m, const StFile& f, std::vector<HostPack>& packs) {
-    std::string err;
-    auto has_suffix = [](const std::string& s, const char* suf) { size_t n = strlen(suf); return s.size() >= n && !s.compare(s.size() - n, n, suf); };
-    std::map<std::string, const StEntry*> names;                         // sorted: a deterministic blob layout
-    for (auto& kv : f.entries) names[kv.first] = &kv.second;
-    auto get = [&](const std::string& k, std::vector<u16>& out, std::vector<long long>* shape = nullptr) -> bool {
-        auto it = f.entries.find(k);
-        if (it == f.entries.end()) { err = "missing tensor " + k; return false; }
-        if (shape) *shape = it->second.shape;
-        return host_f16(f, it->second, out, err);
-    };
-    // load_state_dict's order is the DECLARATION order; the stacked time-embedding projection follows it.  Recreate that order.
-    auto res_names = [&](const std::string& pre, std::vector<std::string>& out) {
-        out.push_back(pre + ".spatial_res_block.time_emb_proj");
-        out.push_back(pre + ".temporal_res_block.time_emb_proj");
-    };
-    for (auto& bp : m.down) for (size_t j = 0; j < bp.layers.size(); ++j) res_names("down_blocks." + std::to_string(bp.idx) + ".resnets." + std::to_string(j), m.temb_names);
-    res_names("mid_block.resnets.0", m.temb_names);
-    res_names("mid_block.resnets.1", m.temb_names);
-    for (auto& bp : m.up) for (size_t j = 0; j < bp.layers.size(); ++j) res_names("up_blocks." + std::to_string(bp.idx) + ".resnets." + std::to_string(j), m.temb_names);
-
-    for (auto& kv : names) {
-        const std::string& k = kv.first;
-        const StEntry& e = *kv.second;
-        std::vector<u16> t;
-        if (!host_f16(f, e, t, err)) return fail("unet_create: %s", k + ": " + err);
-        const auto& s = e.shape;
-        HostPack hp; hp.name = k;
-        if (has_suffix(k, ".weight") && s.size() == 4 && s[3] == 3) {                   // Conv2d 3x3 [O, I, 3, 3] -> OHWI, I padded to 64, O to 8
-            const long long O = s[0], I = s[1], IP = (I + 63) / 64 * 64, OP = (O + 7) / 8 * 8;
-            hp.rows = OP; hp.cols = 9 * IP; hp.d.assign((size_t)(OP * 9 * IP), 0);
-            for (long long o = 0; o < O; ++o) for (long long i = 0; i < I; ++i) for (int y = 0; y < 3; ++y) for (int x = 0; x < 3; ++x)
-                hp.d[(size_t)(((o * 3 + y) * 3 + x) * IP + i)] = t[(size_t)(((o * I + i) * 3 + y) * 3 + x)];
-        } else if (has_suffix(k, ".weight") && s.size() == 5) {                         // Conv3d (3,1,1) [O, I, 3, 1, 1] -> [O, 3, I]
-            const long long O = s[0], I = s[1];
-            hp.rows = O; hp.cols = 3 * I; hp.d.resize((size_t)(O * 3 * I));
-            for (long long o = 0; o < O; ++o) for (long long i = 0; i < I; ++i) for (int tt = 0; tt < 3; ++tt)
-                hp.d[(size_t)((o * 3 + tt) * I + i)] = t[(size_t)((o * I + i) * 3 + tt)];
-        } else if (has_suffix(k, "mix_factor")) {
-            // AlphaBlender (resnet.py:789-802): alpha = sigmoid(mix_factor) in fp16 (`alpha.to(x_spatial.dtype)`), 1 - alpha in fp16 arithmetic
-            const float mf = f16_bits_to_f32(t[0]);                                      // (load_state_dict keeps every parameter in fp16)
-            const _Float16 a = (_Float16)(1.0f / (1.0f + expf(-mf)));
-            const _Float16 om = (_Float16)((_Float16)1.0f - a);
-            m.alpha[k] = {(double)(float)a, (double)(float)om};
-            continue;
-        } else {                                                                          // Linear / norm / bias / 1x1 shortcut: as stored ([rows, rest])
-            hp.rows = s.empty() ? 1 : s[0];
-            long long n = 1;
-            for (long long d : s) n *= d;
-            hp.cols = hp.rows ? n / hp.rows : 0;
-            hp.d = std::move(t);
-        }
-        packs.push_back(std::move(hp));
-    }
-    // conv_out.bias padded to 8 outputs
+    std::vector<HostPack>().swap(m->packs);                // the host copies are on the device now
+    m->ff_ln = tune_env("SYN3R_FF_LN", 1) != 0;          // tuning builds only (common.h): the shipped library reads no environment
+    m->ln_qkv = tune_env("SYN3R_LN_QKV", 1) != 0;
+    *out = m.release();
     {
-        std::vector<u16> b;
-        if (!get("conv_out.bias", b)) return fail("unet_create: %s", err);
-        b.resize((b.size() + 7) / 8 * 8, 0);
-        for (auto& hp : packs) if (hp.name == "conv_out.bias") { hp.rows = (long long)b.size(); hp.cols = 1; hp.d = b; }
-    }
-    // the upsamplers' 3x3 weights folded into four 2x2 phase filters (ops.pack_upsample4; the OHWI pack above is their source)
-    for (size_t i = 0, n = packs.size(); i < n; ++i) {
-        if (!has_suffix(packs[i].name, ".upsamplers.0.conv.weight")) continue;
-        const long long O = packs[i].rows, I = packs[i].cols / 9;
-        HostPack hp; hp.name = packs[i].name + "_up4"; hp.rows = 4 * O; hp.cols = 4 * I; hp.d.resize((size_t)(16 * O * I));
-        if (syn3r_pack_upsample4_f16(packs[i].d.data(), hp.d.data(), (int)O, (int)I) != SYN3R_OK) return SYN3R_E_INVALID;
-        packs.push_back(std::move(hp));
-    }
-    // fused qkv; GEGLU row groups; stacked time-embedding projections
-    for (auto& kv : names) {
-        const std::string& k = kv.first;
-        if (has_suffix(k, "attn1.to_q.weight")) {
-            const std::string pre = k.substr(0, k.size() - strlen("to_q.weight"));
-            HostPack hp; hp.name = pre + "qkv";
-            std::vector<long long> sh;
-            for (const char* part : {"to_q.weight", "to_k.weight", "to_v.weight"}) {
-                std::vector<u16> t;
-                if (!get(pre + part, t, &sh)) return fail("unet_create: %s", err);
-                hp.d.insert(hp.d.end(), t.begin(), t.end());
-            }
-            hp.cols = sh[1]; hp.rows = (long long)hp.d.size() / hp.cols;
-            packs.push_back(std::move(hp));
-        } else if (has_suffix(k, ".net.0.proj.weight")) {
-            const std::string pre = k.substr(0, k.size() - strlen("weight"));
-            std::vector<u16> wv, bv;
-            std::vector<long long> sh;
-            if (!get(k, wv, &sh) || !get(pre + "bias", bv)) return fail("unet_create: %s", err);
-            const long long D2 = sh[0], K = sh[1], D = D2 / 2;
-            HostPack pw, pb;
-            if (K == 320) {                                                               // ops.pack_geglu_chunked: per 64-wide hidden chunk 4 x [16 hidden | 16 gate]
-                if (D % 64) return fail("unet_create: %s: hidden width must be a multiple of 64", k);
-                pw.name = pre + "geglu_cw"; pb.name = pre + "geglu_cb";
-                pw.rows = 2 * D; pw.cols = K; pw.d.resize((size_t)(2 * D * K)); pb.rows = 2 * D; pb.cols = 1; pb.d.resize((size_t)(2 * D));
-                long long r = 0;
-                for (long long j = 0; j < D / 64; ++j) for (int q = 0; q < 64; q += 16) for (int half = 0; half < 2; ++half) for (int i = 0; i < 16; ++i, ++r) {
-                    const long long src = (half ? D : 0) + 64 * j + q + i;
-                    memcpy(&pw.d[(size_t)(r * K)], &wv[(size_t)(src * K)], (size_t)K * 2);
-                    pb.d[(size_t)r] = bv[(size_t)src];
-                }
-            } else {                                                                      // ops.pack_geglu: per 80-column output tile [80 hidden | 80 gate], zero-padded
-                const long long tiles = (D + 79) / 80;
-                pw.name = pre + "geglu_w"; pb.name = pre + "geglu_b";
-                pw.rows = tiles * 160; pw.cols = K; pw.d.assign((size_t)(tiles * 160 * K), 0); pb.rows = tiles * 160; pb.cols = 1; pb.d.assign((size_t)(tiles * 160), 0);
-                for (long long t = 0; t < tiles; ++t) {
-                    const long long n = std::min<long long>(80, D - 80 * t);
-                    memcpy(&pw.d[(size_t)(160 * t * K)], &wv[(size_t)(80 * t * K)], (size_t)(n * K) * 2);
-                    memcpy(&pw.d[(size_t)((160 * t + 80) * K)], &wv[(size_t)((D + 80 * t) * K)], (size_t)(n * K) * 2);
-                    memcpy(&pb.d[(size_t)(160 * t)], &bv[(size_t)(80 * t)], (size_t)n * 2);
-                    memcpy(&pb.d[(size_t)(160 * t + 80)], &bv[(size_t)(D + 80 * t)], (size_t)n * 2);
-                }
-            }
-            packs.push_back(std::move(pw)); packs.push_back(std::move(pb));
-            if (K != 320 && D % 128 == 0) {                                              // ops.pack_geglu64 beside it: per 64-wide hidden chunk [64 hidden | 64 gate] (k_gemm_g256, round 6)
-                HostPack qw, qb;
-                qw.name = pre + "geglu_w64"; qb.name = pre + "geglu_b64";
-                qw.rows = 2 * D; qw.cols = K; qw.d.resize((size_t)(2 * D * K)); qb.rows = 2 * D; qb.cols = 1; qb.d.resize((size_t)(2 * D));
-                for (long long j = 0; j < D / 64; ++j) {
-                    memcpy(&qw.d[(size_t)(128 * j * K)], &wv[(size_t)(64 * j * K)], (size_t)(64 * K) * 2);
-                    memcpy(&qw.d[(size_t)((128 * j + 64) * K)], &wv[(size_t)((D + 64 * j) * K)], (size_t)(64 * K) * 2);
-                    memcpy(&qb.d[(size_t)(128 * j)], &bv[(size_t)(64 * j)], 64 * 2);
-                    memcpy(&qb.d[(size_t)(128 * j + 64)], &bv[(size_t)(D + 64 * j)], 64 * 2);
-                }
-                packs.push_back(std::move(qw)); packs.push_back(std::move(qb));
-            }
-        }
-    }
-    {
-        HostPack pw, pb; pw.name = "time_emb_proj.all.weight"; pb.name = "time_emb_proj.all.bias";
-        int off = 0; long long K = 0;
-        for (auto& nme : m.temb_names) {
-            std::vector<u16> wv, bv;
-            std::vector<long long> sh;
-            if (!get(nme + ".weight", wv, &sh) || !get(nme + ".bias", bv)) return fail("unet_create: %s", err);
-            K = sh[1];
-            m.temb_slice[nme] = {off, off + (int)sh[0]};
-            off += (int)sh[0];
-            pw.d.insert(pw.d.end(), wv.begin(), wv.end());
-            pb.d.insert(pb.d.end(), bv.begin(), bv.end());
-        }
-        pw.rows = off; pw.cols = K; pb.rows = off; pb.cols = 1;
-        packs.push_back(std::move(pw)); packs.push_back(std::move(pb));
+        std::lock_guard<std::mutex> lk(g_unet_mu);
+        unet_registry().insert(*out);
     }
     return SYN3R_OK;
 }
 
 }  // namespace
 
-// The fold rule of the four-phase upsampling convolution (include/syn3r_hip.h): pure host code, the twin of ops.pack_upsample4.
-// After a nearest-2x upsample the 3x3 window of an output pixel of parity (py, px) covers a 2x2 block of input pixels; filter rows
-// ty fall on block row a as  py = 0: {0} | {1, 2},  py = 1: {0, 1} | {2}  (columns the same with px).  Each folded weight is the
-// sum of its 1, 2 or 4 source taps in fp32, taken in ascending (ty, tx) order and rounded once to fp16 (nearest even).
-extern "C" int syn3r_pack_upsample4_f16(const void* w, void* w4, int Cout, int Cin) {
-    SYN3R_REQUIRE(w && w4, "pack_upsample4: null operand");
-    SYN3R_REQUIRE(Cout > 0 && Cin > 0 && Cout <= (1 << 15) && Cin <= (1 << 15), "pack_upsample4: bad sizes Cout=%d Cin=%d", Cout, Cin);
-    const _Float16* src = (const _Float16*)w;
-    _Float16* dst = (_Float16*)w4;
-    const size_t C = (size_t)Cin;
-    for (int ph = 0; ph < 4; ++ph) {
-        const int py = ph >> 1, px = ph & 1;
-        for (int o = 0; o < Cout; ++o)
-            for (int a = 0; a < 2; ++a)
-                for (int b = 0; b < 2; ++b) {
-                    const int ty0 = py == 0 ? (a == 0 ? 0 : 1) : (a == 0 ? 0 : 2), ty1 = py == 0 ? (a == 0 ? 0 : 2) : (a == 0 ? 1 : 2);
-                    const int tx0 = px == 0 ? (b == 0 ? 0 : 1) : (b == 0 ? 0 : 2), tx1 = px == 0 ? (b == 0 ? 0 : 2) : (b == 0 ? 1 : 2);
-                    _Float16* d = dst + ((((size_t)ph * Cout + o) * 2 + a) * 2 + b) * C;
-                    for (size_t c = 0; c < C; ++c) {
-                        float s = 0.f;
-                        bool first = true;
-                        for (int ty = ty0; ty <= ty1; ++ty)
-                            for (int tx = tx0; tx <= tx1; ++tx) {
-                                const float v = (float)src[(((size_t)o * 3 + ty) * 3 + tx) * C + c];
-                                s = first ? v : s + v;
-                                first = false;
-                            }
-                        d[c] = (_Float16)s;
-                    }
-                }
-    }
-    return SYN3R_OK;
-}
-
-namespace {
-int unet_create_impl(const char* weights_dir, const char* variant, syn3r_unet** out);
-}
-// The loader parses files it does not control (config.json, the safetensors header): nothing may leave through extern "C" as a
+// The reader parses files it does not control (config.json, the safetensors header): nothing may leave through extern "C" as a
 // C++ exception (bad_alloc / length_error from a hostile header would terminate a ctypes / cgo host).
 extern "C" int syn3r_unet_create(const char* weights_dir, const char* variant, syn3r_unet** out) {
     SYN3R_REQUIRE(weights_dir && out, "unet_create: null argument");
@@ -559,62 +154,6 @@ extern "C" int syn3r_unet_create(const char* weights_dir, const char* variant, s
     *out = nullptr;
     return SYN3R_E_INVALID;
 }
-namespace {
-int unet_create_impl(const char* weights_dir, const char* variant, syn3r_unet** out) {
-    const std::string dir(weights_dir);
-    std::string cfg_text;
-    if (!read_file(dir + "/config.json", cfg_text)) return fail("unet_create: cannot read %s/config.json", dir);
-    JParser jp{cfg_text.data(), cfg_text.data() + cfg_text.size()};
-    JVal cfg = jp.value();
-    if (!jp.ok || cfg.type != JVal::OBJ) return fail("unet_create: %s/config.json is not a JSON object", dir);
-    std::unique_ptr<syn3r_unet> m(new syn3r_unet);
-    int rc = build_plan(*m, cfg);
-    if (rc) return rc;
-    std::unique_ptr<StFile> fp;
-    std::string err;
-    auto absent = [](const std::string& e) { return e.compare(0, 11, "cannot open") == 0; };
-    if (variant && *variant) {
-        fp.reset(new StFile);
-        if (!fp->open_(dir + "/diffusion_pytorch_model." + variant + ".safetensors", err)) {
-            if (!absent(err)) return fail("unet_create: %s", err);               // the file is there and is not a checkpoint
-            fp.reset();
-        }
-    }
-    if (!fp) {
-        fp.reset(new StFile);
-        if (!fp->open_(dir + "/diffusion_pytorch_model.safetensors", err)) {
-            if (!absent(err)) return fail("unet_create: %s", err);
-            return fail("unet_create: no safetensors weights under %s (diffusion_pytorch_model[.variant].safetensors)", dir);
-        }
-    }
-    const StFile& f = *fp;
-    std::vector<HostPack> packs;
-    rc = pack_weights(*m, f, packs);
-    if (rc) return rc;
-    rc = check_hip(hipGetDevice(&m->device), "hipGetDevice");
-    if (rc) return rc;
-    size_t total = 0;
-    for (auto& hp : packs) total += (hp.d.size() * 2 + 255) / 256 * 256;
-    rc = check_hip(hipMalloc((void**)&m->blob, total ? total : 256), "hipMalloc(unet weights)");
-    if (rc) return rc;
-    m->blob_bytes = total;
-    size_t off = 0;
-    for (auto& hp : packs) {
-        rc = check_hip(hipMemcpy(m->blob + off, hp.d.data(), hp.d.size() * 2, hipMemcpyHostToDevice), "hipMemcpy(unet weights)");
-        if (rc) { (void)hipFree(m->blob); return rc; }
-        m->w[hp.name] = Wt{(__half*)(m->blob + off), hp.rows, hp.cols};
-        off += (hp.d.size() * 2 + 255) / 256 * 256;
-    }
-    m->ff_ln = tune_env("SYN3R_FF_LN", 1) != 0;          // tuning builds only (common.h): the shipped library reads no environment
-    m->ln_qkv = tune_env("SYN3R_LN_QKV", 1) != 0;
-    *out = m.release();
-    {
-        std::lock_guard<std::mutex> lk(g_unet_mu);
-        unet_registry().insert(*out);
-    }
-    return SYN3R_OK;
-}
-}  // namespace
 
 extern "C" int syn3r_unet_destroy(syn3r_unet* m) {
     if (!m) return SYN3R_OK;
@@ -683,6 +222,11 @@ struct Epi {                                                              // the
     const __half* rowvec = nullptr; long long ldrv = 0; int rows_per_vec = 0, rv_group = 0;
     const T* residual = nullptr; const T* aux = nullptr;
     float s_acc = 1.f, s_res = 1.f, s_aux = 1.f;
+    const __half* res_p() const { return residual ? residual->p : nullptr; }
+    int res_ld() const { return residual ? residual->cols : 0; }
+    int res_ld(int ld) const { return residual ? ld : 0; }               // (conv3x3 / tconv3 name the output's width)
+    const __half* aux_p() const { return aux ? aux->p : nullptr; }
+    int aux_ld() const { return aux ? aux->cols : 0; }
 };
 
 struct Run {
@@ -690,12 +234,12 @@ struct Run {
     Arena ar;
     bool dry = false;
     hipStream_t stream = nullptr;
-    int B = 0, F = 0, h = 0, w = 0, G = 0;
-    bool shared_ctx = false;
+    int B, F, h, w, G;                              // G: the context group (it changes epilogue arguments, not buffers)
+    bool shared_ctx;
     T ehs, temb_all;
     std::unordered_map<std::string, T> cross;      // folded cross-attention vectors of this forward
     int rc = SYN3R_OK;
-    explicit Run(syn3r_unet& m_) : m(m_) {}
+    Run(syn3r_unet& m_, int B_, int F_, int h_, int w_, int G_, int ehs_rows) : m(m_), B(B_), F(F_), h(h_), w(w_), G(G_), shared_ctx(B_ == 1 || ehs_rows == 1) {}
 
     const Wt* W(const std::string& k) {
         auto it = m.w.find(k);
@@ -704,11 +248,14 @@ struct Run {
     }
     const __half* Wp(const std::string& k) { const Wt* t = W(k); return t ? t->p : nullptr; }
     bool ok() const { return rc == SYN3R_OK; }
+    // every buffer of a forward comes from the arena through here (nothing after the first error)
+    void* take(size_t bytes) {
+        void* p = ok() ? ar.alloc(bytes) : nullptr;
+        if (ok() && !p) { set_error("unet_forward: workspace too small (needs syn3r_unet_workspace_bytes)"); rc = SYN3R_E_WORKSPACE; }
+        return p;
+    }
     T make(long long rows, int cols) {
-        T t; t.rows = rows; t.cols = cols;
-        if (!ok()) return t;
-        t.p = (__half*)ar.alloc((size_t)rows * cols * 2);
-        if (!t.p) { set_error("unet_forward: workspace too small (needs syn3r_unet_workspace_bytes)"); rc = SYN3R_E_WORKSPACE; }
+        T t; t.rows = rows; t.cols = cols; t.p = (__half*)take((size_t)rows * cols * 2);
         return t;
     }
     void drop(T& t) { ar.release(t.p); t.p = nullptr; ar.release(t.gnp); t.gnp = nullptr; t.gn_ok = 0; }
@@ -719,12 +266,15 @@ struct Run {
         static const int gn_env = tune_env("SYN3R_GN_EPILOGUE", 1);
         const size_t nb = (want && gn_env != 0 && out.rows <= SYN3R_DIM_MAX) ? syn3r_gn_partials_bytes((int)out.rows, out.cols) : 0;
         if (!nb || !ok()) return 0;
-        out.gnp = (float*)ar.alloc(nb);
-        if (!out.gnp) { set_error("unet_forward: workspace too small (needs syn3r_unet_workspace_bytes)"); rc = SYN3R_E_WORKSPACE; return 0; }
-        return nb;
+        out.gnp = (float*)take(nb);
+        return out.gnp ? nb : 0;
     }
     void chk(int r) { if (r && !rc) rc = r; }
     bool go() const { return ok() && !dry; }
+    // a glue kernel over n elements, one thread each
+    template <class K, class... A> void launch1d(K kernel, long long n, A... args) {
+        if (go()) hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, args...);
+    }
 
     // ---- operators (ops.py)
     T linear(const T& x, long long ldx, int K, const std::string& wname, const char* bias_name, const Epi& e = Epi(), bool gn = false) {
@@ -734,8 +284,7 @@ struct Run {
         const size_t gnb = gn_begin(out, gn);
         if (go())
             chk(syn3r_gemm_f16(x.p, ldx, wt->p, out.p, out.cols, b, e.rowvec, e.ldrv, e.rows_per_vec, e.rv_group,
-                               e.residual ? e.residual->p : nullptr, e.residual ? e.residual->cols : 0, e.aux ? e.aux->p : nullptr,
-                               e.aux ? e.aux->cols : 0, e.s_acc, e.s_res, e.s_aux, (int)x.rows, out.cols, K, out.gnp, gnb, &out.gn_ok, stream));
+                               e.res_p(), e.res_ld(), e.aux_p(), e.aux_ld(), e.s_acc, e.s_res, e.s_aux, (int)x.rows, out.cols, K, out.gnp, gnb, &out.gn_ok, stream));
         return out;
     }
     T linear(const T& x, const std::string& wname, const std::string& bname, const Epi& e = Epi(), bool gn = false) {
@@ -750,10 +299,7 @@ struct Run {
             return out;
         }
         T cat = make(x1.rows, x1.cols + x2.cols);
-        if (go()) {
-            const long long n = cat.rows * cat.cols;
-            hipLaunchKernelGGL(k_cat_cols, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x1.p, x1.cols, x2.p, x2.cols, cat.p, cat.rows);
-        }
+        launch1d(k_cat_cols, cat.rows * cat.cols, x1.p, x1.cols, x2.p, x2.cols, cat.p, cat.rows);
         T out = linear(cat, wname, bname);
         drop(cat);
         return out;
@@ -769,8 +315,7 @@ struct Run {
         T out = make((long long)NB * Ho * Wo, Cout);
         const size_t gnb = gn_begin(out, gn);
         if (go())
-            chk(syn3r_conv2d3x3_f16(x.p, wt->p, out.p, Cout, Wp(bname), e.rowvec, e.ldrv, e.rows_per_vec, e.residual ? e.residual->p : nullptr,
-                                    e.residual ? Cout : 0, e.s_acc, e.s_res, NB, Hi, Wi, Cin, Cout, stride, ups ? 1 : 0, 1, out.gnp, gnb, &out.gn_ok, stream));
+            chk(syn3r_conv2d3x3_f16(x.p, wt->p, out.p, Cout, Wp(bname), e.rowvec, e.ldrv, e.rows_per_vec, e.res_p(), e.res_ld(Cout), e.s_acc, e.s_res, NB, Hi, Wi, Cin, Cout, stride, ups ? 1 : 0, 1, out.gnp, gnb, &out.gn_ok, stream));
         return out;
     }
     // nearest-2x upsample + 3x3 convolution in its four-phase form (ops.conv3x3_up4; weights folded by pack_weights)
@@ -789,17 +334,15 @@ struct Run {
         T out = make(x.rows, Cout);
         const size_t gnb = gn_begin(out, true);  // (every temporal convolution's output is a GroupNorm input, model.py:_resblock)
         if (go())
-            chk(syn3r_tconv3_f16(x.p, wt->p, out.p, Cout, Wp(bname), e.rowvec, e.ldrv, e.rows_per_vec, e.residual ? e.residual->p : nullptr,
-                                 e.residual ? Cout : 0, e.s_acc, e.s_res, B, F, HW, x.cols, Cout, out.gnp, gnb, &out.gn_ok, stream));
+            chk(syn3r_tconv3_f16(x.p, wt->p, out.p, Cout, Wp(bname), e.rowvec, e.ldrv, e.rows_per_vec, e.res_p(), e.res_ld(Cout), e.s_acc, e.s_res, B, F, HW, x.cols, Cout, out.gnp, gnb, &out.gn_ok, stream));
         return out;
     }
     T groupnorm(const T& x, const std::string& pre, int samples, float eps, bool silu, const T* x2 = nullptr) {
         const int rows = (int)(x.rows / samples);
         const size_t wsb = syn3r_groupnorm_workspace_bytes(samples, rows);
-        T out = make(x.rows, x.cols + (x2 ? x2->cols : 0));
-        void* ws = ok() ? ar.alloc(wsb) : nullptr;
-        if (ok() && !ws) { set_error("unet_forward: workspace too small (needs syn3r_unet_workspace_bytes)"); rc = SYN3R_E_WORKSPACE; }
         const int Ct = x.cols + (x2 ? x2->cols : 0);
+        T out = make(x.rows, Ct);
+        void* ws = take(wsb);
         if (go() && x.gn_ok && (!x2 || x2->gn_ok) && rows % 32 == 0 && Ct % 320 == 0 && x.cols % 10 == 0) {      // ops.py:groupnorm, the same rule
             chk(syn3r_groupnorm_pre_f16(x.p, x.cols, x.gnp, x2 ? x2->p : nullptr, x2 ? x2->cols : 0, x2 ? x2->gnp : nullptr, out.p, samples, rows,
                                         Wp(pre + ".weight"), Wp(pre + ".bias"), eps, silu, ws, wsb, stream));
@@ -858,15 +401,13 @@ struct Run {
             if (!norm.empty() && !fuse_ln) { x = layernorm(x_in, norm); own = true; }
             out = make(x.rows, x.cols);
             if (go()) {
-                const void *r = e.residual ? e.residual->p : nullptr, *a = e.aux ? e.aux->p : nullptr;
-                const long long ldr = e.residual ? e.residual->cols : 0, lda = e.aux ? e.aux->cols : 0;
                 if (fuse_ln)
                     chk(syn3r_feedforward_fused_ln_f16(x.p, x.cols, Wp(norm + ".weight"), Wp(norm + ".bias"), 1e-5f, Wp(pre + ".net.0.proj.geglu_cw"),
-                                                       Wp(pre + ".net.0.proj.geglu_cb"), D, Wp(w2), Wp(b2), out.p, out.cols, r, ldr, a, lda,
+                                                       Wp(pre + ".net.0.proj.geglu_cb"), D, Wp(w2), Wp(b2), out.p, out.cols, e.res_p(), e.res_ld(), e.aux_p(), e.aux_ld(),
                                                        e.s_acc, e.s_res, e.s_aux, (int)x.rows, x.cols, stream));
                 else
                     chk(syn3r_feedforward_fused_f16(x.p, x.cols, Wp(pre + ".net.0.proj.geglu_cw"), Wp(pre + ".net.0.proj.geglu_cb"), D, Wp(w2), Wp(b2),
-                                                    out.p, out.cols, r, ldr, a, lda, e.s_acc, e.s_res, e.s_aux, (int)x.rows, x.cols, stream));
+                                                    out.p, out.cols, e.res_p(), e.res_ld(), e.aux_p(), e.aux_ld(), e.s_acc, e.s_res, e.s_aux, (int)x.rows, x.cols, stream));
             }
         } else {
             if (!norm.empty()) { x = layernorm(x_in, norm); own = true; }
@@ -874,19 +415,16 @@ struct Run {
             const int N = wt2 ? (int)wt2->rows : 0;
             out = make(x.rows, N);
             const size_t wsb = syn3r_feedforward_workspace_bytes((int)x.rows, D);
-            void* ws = ok() ? ar.alloc(wsb) : nullptr;
-            if (ok() && !ws) { set_error("unet_forward: workspace too small (needs syn3r_unet_workspace_bytes)"); rc = SYN3R_E_WORKSPACE; }
+            void* ws = take(wsb);
             // model.py:_ff - net.0 on the 256 x 256 tile where the shape has whole tiles (bit-identical to the 80-column path)
             static const int g256_env = tune_env("SYN3R_FF_G256", 1);
             const bool p64 = g256_env != 0 && m.w.count(pre + ".net.0.proj.geglu_w64") && syn3r_feedforward_p64_supported((int)x.rows, D, x.cols);
             if (go() && p64)
                 chk(syn3r_feedforward_p64_f16(x.p, x.cols, Wp(pre + ".net.0.proj.geglu_w64"), Wp(pre + ".net.0.proj.geglu_b64"), D, Wp(w2), Wp(b2), out.p, N,
-                                              e.residual ? e.residual->p : nullptr, e.residual ? e.residual->cols : 0, e.aux ? e.aux->p : nullptr,
-                                              e.aux ? e.aux->cols : 0, e.s_acc, e.s_res, e.s_aux, (int)x.rows, x.cols, N, ws, wsb, stream));
+                                              e.res_p(), e.res_ld(), e.aux_p(), e.aux_ld(), e.s_acc, e.s_res, e.s_aux, (int)x.rows, x.cols, N, ws, wsb, stream));
             else if (go())
                 chk(syn3r_feedforward_f16(x.p, x.cols, Wp(pre + ".net.0.proj.geglu_w"), Wp(pre + ".net.0.proj.geglu_b"), D, Wp(w2), Wp(b2), out.p, N,
-                                          e.residual ? e.residual->p : nullptr, e.residual ? e.residual->cols : 0, e.aux ? e.aux->p : nullptr,
-                                          e.aux ? e.aux->cols : 0, e.s_acc, e.s_res, e.s_aux, (int)x.rows, x.cols, N, ws, wsb, stream));
+                                          e.res_p(), e.res_ld(), e.aux_p(), e.aux_ld(), e.s_acc, e.s_res, e.s_aux, (int)x.rows, x.cols, N, ws, wsb, stream));
             ar.release(ws);
         }
         if (own) drop(x);
@@ -894,9 +432,18 @@ struct Run {
     }
     T silu(const T& x) {
         T y = make(x.rows, x.cols);
-        const long long n = x.rows * x.cols;
-        if (go()) hipLaunchKernelGGL(k_silu, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x.p, y.p, n);
+        launch1d(k_silu, x.rows * x.cols, x.p, y.p, x.rows * x.cols);
         return y;
+    }
+    // TimestepEmbedding (embeddings.py): linear_2(silu(linear_1(x))); x is released as soon as linear_1 has read it
+    T embed_mlp(const std::string& pre, T& x) {
+        T a = linear(x, pre + ".linear_1.weight", pre + ".linear_1.bias");
+        drop(x);
+        T s = silu(a);
+        drop(a);
+        T o = linear(s, pre + ".linear_2.weight", pre + ".linear_2.bias");
+        drop(s);
+        return o;
     }
     // attn2 with a single key: to_out(to_v(ctx)) per context row (model.py:_cross_vec); kept for the forward
     const T& cross_vec(const std::string& pre) {
@@ -906,6 +453,13 @@ struct Run {
         T o = linear(v, pre + ".to_out.0.weight", pre + ".to_out.0.bias");
         drop(v);
         return cross.emplace(pre, o).first->second;
+    }
+
+    // AlphaBlender scales of `pre`.time_mixer: (alpha, 1 - alpha), model.py:_blend_scales
+    void blend(const std::string& pre, double& a, double& om) {
+        auto al = m.alpha.find(pre + ".time_mixer.mix_factor");
+        a = al != m.alpha.end() ? al->second.first : 0.5; om = al != m.alpha.end() ? al->second.second : 0.5;
+        if (al == m.alpha.end() && !rc) { set_error("unet_forward: the checkpoint has no %s.time_mixer.mix_factor", pre.c_str()); rc = SYN3R_E_INVALID; }
     }
 
     // SpatioTemporalResBlock (resnet.py:325-378, 613-636, 789-802); x2: the block input is [x | x2] (up blocks)
@@ -938,9 +492,8 @@ struct Run {
         drop(g1);
         T g2 = groupnorm(c1, t + ".norm2", B, 1e-5f, true);
         drop(c1);
-        auto al = m.alpha.find(pre + ".time_mixer.mix_factor");
-        const double a = al != m.alpha.end() ? al->second.first : 0.5, om = al != m.alpha.end() ? al->second.second : 0.5;
-        if (al == m.alpha.end() && !rc) { set_error("unet_forward: the checkpoint has no %s.time_mixer.mix_factor", pre.c_str()); rc = SYN3R_E_INVALID; }
+        double a, om;
+        blend(pre, a, om);
         Epi e4; e4.residual = &xs; e4.s_acc = (float)om; e4.s_res = (float)(a + om);     // alpha xs + (1 - alpha)(xs + conv2)
         T out = tconv3(g2, t + ".conv2.weight", t + ".conv2.bias", HW, e4);
         drop(g2);
@@ -959,19 +512,13 @@ struct Run {
             return it->second.p;
         }
         T pos = make(F, ch);
-        if (go()) hipLaunchKernelGGL(k_timestep_embedding, dim3((unsigned)((F * (ch / 2) + 255) / 256)), dim3(256), 0, stream, (const float*)nullptr, 0.0, 1.0f, F, ch, pos.p);
-        T e1 = linear(pos, pre + ".time_pos_embed.linear_1.weight", pre + ".time_pos_embed.linear_1.bias");
-        drop(pos);
-        T e1s = silu(e1);
-        drop(e1);
-        T e2 = linear(e1s, pre + ".time_pos_embed.linear_2.weight", pre + ".time_pos_embed.linear_2.bias");
-        drop(e1s);
+        launch1d(k_timestep_embedding, F * (ch / 2), (const float*)nullptr, 0.0, 1.0f, F, ch, pos.p);
+        T e2 = embed_mlp(pre + ".time_pos_embed", pos);
         __half* keep = nullptr;
         if (go()) {
             chk(check_hip(hipMalloc((void**)&keep, (size_t)B * F * ch * 2), "hipMalloc(position embedding)"));
             if (ok()) {
-                const long long n = (long long)B * F * ch;
-                hipLaunchKernelGGL(k_repeat_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, e2.p, keep, F, (long long)B * F, ch);
+                launch1d(k_repeat_rows, (long long)B * F * ch, e2.p, keep, F, (long long)B * F, ch);
                 syn3r_unet::PosEmb pe;
                 pe.p = keep; pe.stream = stream;
                 if (hipEventCreateWithFlags(&pe.ready, hipEventDisableTiming) == hipSuccess) {
@@ -1044,9 +591,8 @@ struct Run {
             drop(tt);
             tt = o;
         }
-        auto al = m.alpha.find(pre + ".time_mixer.mix_factor");
-        const double a = al != m.alpha.end() ? al->second.first : 0.5, om = al != m.alpha.end() ? al->second.second : 0.5;
-        if (al == m.alpha.end() && !rc) { set_error("unet_forward: the checkpoint has no %s.time_mixer.mix_factor", pre.c_str()); rc = SYN3R_E_INVALID; }
+        double a, om;
+        blend(pre, a, om);
         Epi em; em.residual = &tt; em.aux = &hs; em.s_acc = (float)om; em.s_res = (float)om; em.s_aux = (float)a;   // alpha hs + (1 - alpha)(ff + tt)
         T mix = ff(t + ".ff", tt, t + ".norm3", em);
         drop(tt);
@@ -1059,7 +605,6 @@ struct Run {
 
     // unet_spatio_temporal_condition.py:356-489
     void forward(const __half* sample, double timestep, const __half* ehs_in, int ehs_rows, const float* added_ids, __half* out) {
-        const int c0 = m.boc[0];
         // split-K scratch for the lowest level's convolutions (model.py:forward, the same rule): set for this forward, on this thread
         void* splitk = nullptr;
         {
@@ -1067,8 +612,7 @@ struct Run {
             const long long m_low = (long long)B * F * (h / down) * (w / down);
             if (tune_env("SYN3R_SPLITK", 1) != 0 && ((m_low + 255) / 256) * ((m.boc.back() + 159) / 160) * 2 <= 256) {
                 const size_t bytes = (size_t)4 * m_low * m.boc.back() * 4;
-                splitk = ok() ? ar.alloc(bytes) : nullptr;
-                if (ok() && !splitk) { set_error("unet_forward: workspace too small (needs syn3r_unet_workspace_bytes)"); rc = SYN3R_E_WORKSPACE; }
+                splitk = take(bytes);
                 if (go()) chk(syn3r_gemm_set_splitk_workspace(splitk, bytes));
             }
         }
@@ -1082,25 +626,15 @@ struct Run {
         const int c0 = m.boc[0];
         // 1. time (:385-418)
         T te = make(B, c0);
-        if (go()) hipLaunchKernelGGL(k_timestep_embedding, dim3((unsigned)((B * (c0 / 2) + 255) / 256)), dim3(256), 0, stream, (const float*)nullptr, timestep, 0.0f, B, c0, te.p);
-        T e1 = linear(te, "time_embedding.linear_1.weight", "time_embedding.linear_1.bias");
-        drop(te);
-        T e1s = silu(e1);
-        drop(e1);
-        T emb = linear(e1s, "time_embedding.linear_2.weight", "time_embedding.linear_2.bias");
-        drop(e1s);
+        launch1d(k_timestep_embedding, B * (c0 / 2), (const float*)nullptr, timestep, 0.0f, B, c0, te.p);
+        T emb = embed_mlp("time_embedding", te);
         const int nid = m.proj_in / m.add_dim;                             // time ids per sample (3: fps, motion bucket, noise aug)
         T ta = make((long long)B * nid, m.add_dim);
-        if (go()) hipLaunchKernelGGL(k_timestep_embedding, dim3((unsigned)((B * nid * (m.add_dim / 2) + 255) / 256)), dim3(256), 0, stream, added_ids, 0.0, 0.0f, B * nid, m.add_dim, ta.p);
+        launch1d(k_timestep_embedding, B * nid * (m.add_dim / 2), added_ids, 0.0, 0.0f, B * nid, m.add_dim, ta.p);
         T ta2 = ta; ta2.rows = B; ta2.cols = nid * m.add_dim;              // reshape(B, -1)
-        T a1 = linear(ta2, "add_embedding.linear_1.weight", "add_embedding.linear_1.bias");
-        drop(ta);
-        T a1s = silu(a1);
-        drop(a1);
-        T aug = linear(a1s, "add_embedding.linear_2.weight", "add_embedding.linear_2.bias");
-        drop(a1s);
+        T aug = embed_mlp("add_embedding", ta2);
         T es = make(emb.rows, emb.cols);
-        if (go()) { const long long n = es.rows * es.cols; hipLaunchKernelGGL(k_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, emb.p, aug.p, es.p, n); }
+        launch1d(k_add, es.rows * es.cols, emb.p, aug.p, es.p, es.rows * es.cols);
         drop(emb);
         drop(aug);
         T act = silu(es);
@@ -1111,7 +645,7 @@ struct Run {
         // 2. conv_in on NHWC with the channels padded to 64 (:428)
         const int CP = (m.in_ch + 63) / 64 * 64;
         T xin = make((long long)B * F * h * w, CP);
-        if (go()) { const long long n = xin.rows * CP; hipLaunchKernelGGL(k_nchw_to_nhwc, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, sample, xin.p, B * F, m.in_ch, h * w, CP); }
+        launch1d(k_nchw_to_nhwc, xin.rows * CP, sample, xin.p, B * F, m.in_ch, h * w, CP);
         T x = conv3x3(xin, B * F, h, w, CP, "conv_in.weight", "conv_in.bias", 1, false, Epi());
         drop(xin);
         std::vector<T> skips{x};
@@ -1166,7 +700,7 @@ struct Run {
         drop(x);
         T y = conv3x3(gn, B * F, h, w, c0, "conv_out.weight", "conv_out.bias", 1, false, Epi(), nullptr, nullptr, false);
         drop(gn);
-        if (go()) { const long long n = (long long)B * F * m.out_ch * h * w; hipLaunchKernelGGL(k_nhwc_to_nchw, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, y.p, out, B * F, m.out_ch, h * w, y.cols); }
+        launch1d(k_nhwc_to_nchw, (long long)B * F * m.out_ch * h * w, y.p, out, B * F, m.out_ch, h * w, y.cols);
         drop(y);
         for (auto& kv : cross) drop(kv.second);
         cross.clear();
@@ -1190,11 +724,9 @@ int check_shape(const syn3r_unet* m, int B, int F, int h, int w, int ehs_rows, i
 extern "C" size_t syn3r_unet_workspace_bytes(syn3r_unet* m, int B, int F, int h, int w, int ehs_rows) {
     if (check_shape(m, B, F, h, w, ehs_rows, 0)) return 0;
     try {
-    Run r(*m);
+    Run r(*m, B, F, h, w, 1, ehs_rows);
     r.dry = true;
     r.ar.reset((char*)4096, (size_t)1 << 46);
-    r.B = B; r.F = F; r.h = h; r.w = w; r.G = 1;                    // (the context grouping changes epilogue arguments, not buffers)
-    r.shared_ctx = B == 1 || ehs_rows == 1;
     r.forward(nullptr, 0.0, (const __half*)4096, r.shared_ctx ? 1 : B, nullptr, nullptr);
     return r.ok() ? r.ar.peak + 256 : 0;
     } catch (...) { set_error("unet_workspace_bytes: unexpected exception"); return 0; }
@@ -1209,12 +741,9 @@ extern "C" int syn3r_unet_forward(syn3r_unet* m, const void* sample, double time
     SYN3R_REQUIRE(workspace && ((uintptr_t)workspace % 256) == 0, "unet_forward: workspace must be non-null and 256-byte aligned");
     SYN3R_REQUIRE((((uintptr_t)sample | (uintptr_t)encoder_hidden_states | (uintptr_t)out) % 16) == 0, "unet_forward: misaligned tensor");
     try {
-    Run r(*m);
+    Run r(*m, B, F, h, w, ctx_group > 0 ? ctx_group : B, ehs_rows);
     r.ar.reset((char*)workspace, workspace_bytes / 256 * 256);
     r.stream = (hipStream_t)stream;
-    r.B = B; r.F = F; r.h = h; r.w = w;
-    r.G = ctx_group > 0 ? ctx_group : B;
-    r.shared_ctx = B == 1 || ehs_rows == 1;
     r.forward((const __half*)sample, timestep, (const __half*)encoder_hidden_states, r.shared_ctx ? 1 : B, added_time_ids, (__half*)out);
     if (r.ok()) {
         hipError_t e = hipGetLastError();
