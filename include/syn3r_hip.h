@@ -846,6 +846,45 @@ int syn3r_depth_corr_loss_backward(const float* depth, const float* prior, long 
 int syn3r_depth_corr_loss_step(const float* depth, const float* prior, long long n, float weight, float offset, int mode,
                                const float* grad_loss, float* parts, float* grad_depth, void* ws, size_t ws_bytes, void* stream);
 
+/* The same term PATCH-WISE (EXTENSION in the spirit of SparseGS' patch-based Pearson and DNGaussian's local depth normalisation:
+ * a monocular prior is one monotone transform of the depth only locally).  d and p are H x W fp32 maps, P the patch size,
+ * (oy, ox) the origin of the patch grid, 0 <= oy, ox < P.  Patch (i, j) covers rows oy + iP .. oy + (i+1)P - 1 and columns
+ * ox + jP .. ox + (j+1)P - 1; only the K = floor((H - oy) / P) * floor((W - ox) / P) patches inside the image count, K >= 1.
+ * Per patch k, over its P^2 pixels, the rules of the global term above:
+ *   r_A = Pearson(d, -p), r_B = Pearson(d, 1 / (p + offset)) from centred sums, clamped to [-1, 1]; a branch with S_dd == 0 or
+ *   S_tt == 0 has r = 0, loss 1 and a zero gradient (no NaN); L_k = min(1 - r_A, 1 - r_B) (SYN3R_DCORR_MIN, A on a tie) or one
+ *   branch (SYN3R_DCORR_A / _B); the branch is chosen per patch.
+ *   loss = weight / K * sum_k L_k
+ *   grad_depth_i = weight * grad_loss[0] / K * -[ (t_i - t_mean) / sqrt(S_dd S_tt) - r (d_i - d_mean) / S_dd ]  with patch k's
+ *   sums and means for i in patch k; pixels in no full patch contribute nothing and have a zero gradient.
+ * Flat patches stay in K, so K depends on the geometry alone.  The two transforms and offset = 200 are recalled from FSGS'
+ * train.py (not available): UNPINNED, hence arguments; the patch grid is this library's own.
+ * fp64 throughout, sums shifted by the first element, fixed merge orders, no float atomics, no host read: the loss and the gradient
+ * are bitwise repeatable for a given shape.  parts (device, 16-byte aligned, 4 floats): [loss, mean over patches of the chosen r,
+ * share of patches on branch B, share of flat patches].
+ * accumulate 0: every pixel of grad_depth is written (zeros outside the full patches; the buffer may hold anything);
+ * accumulate 1: the gradient is ADDED to grad_depth inside the patches and the rest is left alone (the global and the patch-wise
+ * term then share one buffer without an add launch).
+ * ws: syn3r_depth_corr_local_workspace_bytes(H, W, P, oy, ox) bytes, 16-byte aligned (0 for arguments the entries reject); it
+ * holds one finished 64-byte record per patch, which the backward reads: syn3r_depth_corr_local_loss_backward takes the SAME
+ * workspace and the same mode and offset as the call that filled it.
+ * Rejections before any HIP call (SYN3R_E_INVALID): null pointers, H or W outside [1, 2^15], P outside [2, 256], oy or ox outside
+ * [0, P), K = 0, an unknown mode, a non-finite weight or offset, accumulate not 0 or 1, a misaligned parts or workspace; a short
+ * workspace is SYN3R_E_WORKSPACE. */
+size_t syn3r_depth_corr_local_workspace_bytes(int H, int W, int P, int oy, int ox);
+/* value only: the statistics launch and a one-block sum */
+int syn3r_depth_corr_local_loss(const float* depth, const float* prior, int H, int W, int P, int oy, int ox, float weight, float offset,
+                                int mode, float* parts, void* ws, size_t ws_bytes, void* stream);
+/* the gradient launch on the records of syn3r_depth_corr_local_loss (grad_loss: device scalar, NULL = 1) */
+int syn3r_depth_corr_local_loss_backward(const float* depth, const float* prior, int H, int W, int P, int oy, int ox, float weight,
+                                         float offset, int mode, const float* grad_loss, const void* ws, size_t ws_bytes,
+                                         float* grad_depth, int accumulate, void* stream);
+/* Value AND gradient in two launches: the statistics, then the gradient, whose first block also writes parts.  Same bits as
+ * syn3r_depth_corr_local_loss + syn3r_depth_corr_local_loss_backward. */
+int syn3r_depth_corr_local_loss_step(const float* depth, const float* prior, int H, int W, int P, int oy, int ox, float weight,
+                                     float offset, int mode, const float* grad_loss, float* parts, float* grad_depth, int accumulate,
+                                     void* ws, size_t ws_bytes, void* stream);
+
 /* Per-camera affine exposure compensation (EXTENSION: the reference has none; the published 3DGS code base has since grown a
  * per-image exposure model, gsplat an appearance optimisation).  A is 3 x 4 fp32, row-major, 12 floats in DEVICE memory; image,
  * out, grad_out and grad_image are [3,H,W] fp32 planes:

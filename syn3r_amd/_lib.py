@@ -138,6 +138,10 @@ SIGNATURES = {
     "syn3r_depth_corr_loss": (c_i, [c_p, c_p, c_ll, c_f, c_f, c_i, c_p, c_p, c_sz, c_p]),
     "syn3r_depth_corr_loss_backward": (c_i, [c_p, c_p, c_ll, c_f, c_f, c_i, c_p, c_p, c_sz, c_p, c_p]),
     "syn3r_depth_corr_loss_step": (c_i, [c_p, c_p, c_ll, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "syn3r_depth_corr_local_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
+    "syn3r_depth_corr_local_loss": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_p, c_p, c_sz, c_p]),
+    "syn3r_depth_corr_local_loss_backward": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_p, c_p, c_sz, c_p, c_i, c_p]),
+    "syn3r_depth_corr_local_loss_step": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
     "syn3r_exposure_apply": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
     "syn3r_exposure_backward_workspace_bytes": (c_sz, [c_i, c_i]),
     "syn3r_exposure_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_p, c_sz, c_p]),

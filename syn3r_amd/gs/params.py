@@ -22,6 +22,15 @@ class OptimizationParams:
     # FSGS' depth-correlation term (GSTrainer.train_step): weight 0 = off; `depth_offset` is the c of its 1 / (prior + c) branch
     depth_weight: float = 0.0
     depth_offset: float = 200.0
+    # The same term PATCH-WISE (EXTENSION after SparseGS' patch-based Pearson / DNGaussian's local depth normalisation; a monocular
+    # prior is consistent only locally): `depth_local_weight` x the mean over the `depth_patch_size`-pixel square patches of a grid
+    # of (1 - Pearson) per patch (`train_ops.depth_correlation_local_loss`), next to the global term; weight 0 = off.  The patch
+    # size and the jitter rule are CHOSEN here, not taken from a source: UNPINNED, and resolution dependent (32 px suits the
+    # 72 x 128 .. 1080p views this trainer sees; scale it with the image).  `depth_patch_jitter`: the grid's origin is drawn per
+    # step from (seed, iteration) alone, so patch borders do not stay on the same pixels; False keeps the origin at (0, 0).
+    depth_local_weight: float = 0.0
+    depth_patch_size: int = 32
+    depth_patch_jitter: bool = True
     # adaptive density control, published 3DGS defaults (Kerbl et al. 2023 section 5.2 and its released arguments); used when
     # training()/finetune() run with disable_densification=False
     percent_dense: float = 0.01

@@ -258,6 +258,100 @@ def depth_correlation_loss_step(depth: torch.Tensor, prior: torch.Tensor, weight
     return (parts[0], grad, parts) if return_parts else (parts[0], grad)
 
 
+def _dlocal_args(who: str, depth: torch.Tensor, prior: torch.Tensor, patch: int, origin, mode: str):
+    """`_dcorr_args` plus the patch grid: -> (depth, prior, mode tag, (H, W, P, oy, ox)).  The grid's own limits (P in [2, 256], the
+    origin in [0, P), at least one full patch) are the library's to reject."""
+    d, p, m = _dcorr_args(who, depth, prior, mode)
+    try:
+        oy, ox = (int(v) for v in origin)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: origin must be a pair (oy, ox) of integers, got {origin!r}") from None
+    H, W = (int(v) for v in d.shape[-2:])
+    return d, p, m, (H, W, int(patch), oy, ox)
+
+
+class _DepthCorrLocalLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth: torch.Tensor, prior: torch.Tensor, weight: float, patch: int, origin, offset: float, mode: str):
+        d, p, m, geom = _dlocal_args("depth_correlation_local_loss", depth, prior, patch, origin, mode)
+        lib = L.load()
+        # own buffer, not the shared workspace cache: the patch records must survive until backward
+        ws = torch.empty(max(lib.syn3r_depth_corr_local_workspace_bytes(*geom), 256), dtype=torch.uint8, device=d.device)
+        parts = torch.empty(4, dtype=torch.float32, device=d.device)
+        L.check(lib.syn3r_depth_corr_local_loss(L.ptr(d), L.ptr(p), *geom, float(weight), float(offset), m, L.ptr(parts), L.ptr(ws),
+                                                ws.numel(), L.stream_ptr(d.device)), "depth_corr_local_loss")
+        ctx.save_for_backward(d, p, ws)
+        ctx.args = (geom, float(weight), float(offset), m, depth.shape)
+        ctx.mark_non_differentiable(parts)
+        return parts[0].clone(), parts
+
+    @staticmethod
+    def backward(ctx, grad_loss: torch.Tensor, _grad_parts):
+        L.join_active_trace()
+        d, p, ws = ctx.saved_tensors
+        geom, weight, offset, m, shape = ctx.args
+        go = grad_loss.to(torch.float32).contiguous()
+        grad = torch.empty_like(d)
+        L.check(L.load().syn3r_depth_corr_local_loss_backward(L.ptr(d), L.ptr(p), *geom, weight, offset, m, L.ptr(go), L.ptr(ws),
+                                                              ws.numel(), L.ptr(grad), 0, L.stream_ptr(d.device)),
+                "depth_corr_local_loss_backward")
+        return grad.reshape(shape), None, None, None, None, None, None
+
+
+def depth_correlation_local_loss(depth: torch.Tensor, prior: torch.Tensor, weight: float = 1.0, patch: int = 32, origin=(0, 0),
+                                 offset: float = 200.0, mode: str = "min", return_parts: bool = False):
+    """The depth-correlation term PATCH-WISE (EXTENSION after SparseGS' patch-based Pearson / DNGaussian's local normalisation: a
+    monocular prior is one monotone transform of the depth only locally): `weight / K * sum_k min(1 - r_A, 1 - r_B)` over the K
+    `patch` x `patch` tiles of the grid with origin `origin` = (oy, ox), 0 <= oy, ox < patch, that lie inside the image, the
+    branch and the flat rule of `depth_correlation_loss` taken per patch; pixels in no full patch have a zero gradient.  The two
+    transforms and offset 200 are recalled (UNPINNED).  Device scalar, no host synchronisation; backward is the kernel's gradient pass
+    (csrc/depth_loss.hip).  `return_parts`: also the device tensor [loss, mean chosen r, share of patches on B, share of flat patches]."""
+    loss, parts = _DepthCorrLocalLoss.apply(depth, prior, weight, patch, origin, offset, mode)
+    return (loss, parts) if return_parts else loss
+
+
+def depth_correlation_local_loss_step(depth: torch.Tensor, prior: torch.Tensor, weight: float = 1.0, patch: int = 32, origin=(0, 0),
+                                      offset: float = 200.0, mode: str = "min", grad_loss: torch.Tensor = None,
+                                      grad_out: torch.Tensor = None, return_parts: bool = False):
+    """Value AND depth gradient of `depth_correlation_local_loss` without autograd (`syn3r_depth_corr_local_loss_step`: two
+    launches).  Returns (loss - a view of parts[0] -, grad_depth shaped like depth) [+ parts]; `grad_loss`: device scalar, default 1.
+    `grad_out` (float32, contiguous, depth's number of elements, on its device): the gradient is ADDED to it inside the full patches,
+    the rest is left alone, and it is what comes back; without it a new tensor with zeros outside the patches.  Same bits as the
+    autograd Function's forward + backward."""
+    who = "depth_correlation_local_loss_step"
+    d, p, m, geom = _dlocal_args(who, depth, prior, patch, origin, mode)
+    dev = d.device
+    lib = L.load()
+    if grad_out is not None:
+        L.require_gpu(d, grad_out)
+        if grad_out.dtype != torch.float32 or grad_out.numel() != d.numel() or not grad_out.is_contiguous():
+            raise ValueError(f"{who}: grad_out must be a contiguous float32 tensor of depth's {d.numel()} elements")
+    ws = L.workspace(dev, lib.syn3r_depth_corr_local_workspace_bytes(*geom), "dcorr_local_step")
+    parts = torch.empty(4, dtype=torch.float32, device=dev)
+    grad = torch.empty_like(d) if grad_out is None else grad_out
+    go = grad_loss.to(torch.float32).contiguous() if grad_loss is not None else None
+    L.check(lib.syn3r_depth_corr_local_loss_step(L.ptr(d), L.ptr(p), *geom, float(weight), float(offset), m, L.ptr(go), L.ptr(parts),
+                                                 L.ptr(grad), int(grad_out is not None), L.ptr(ws), ws.numel(), L.stream_ptr(dev)),
+            "depth_corr_local_loss_step")
+    return (parts[0], grad, parts) if return_parts else (parts[0], grad)
+
+
+def depth_correlation_local_records(depth: torch.Tensor, prior: torch.Tensor, patch: int = 32, origin=(0, 0), offset: float = 200.0,
+                                    mode: str = "min") -> torch.Tensor:
+    """The finished per-patch records of the patch-wise term as a float64 [PY, PX, 8] device tensor (diagnostics and tests): per
+    patch [mean depth, mean of the chosen transform's variable, the two gradient coefficients for weight 1, L_k, the chosen r,
+    branch (0 = A, 1 = B), flat (0 / 1)] - what `syn3r_depth_corr_local_loss` leaves at the head of its workspace."""
+    d, p, m, geom = _dlocal_args("depth_correlation_local_records", depth, prior, patch, origin, mode)
+    lib = L.load()
+    H, W, P, oy, ox = geom
+    ws = torch.empty(max(lib.syn3r_depth_corr_local_workspace_bytes(*geom), 256), dtype=torch.uint8, device=d.device)
+    parts = torch.empty(4, dtype=torch.float32, device=d.device)
+    L.check(lib.syn3r_depth_corr_local_loss(L.ptr(d), L.ptr(p), *geom, 1.0, float(offset), m, L.ptr(parts), L.ptr(ws), ws.numel(),
+                                            L.stream_ptr(d.device)), "depth_corr_local_loss")
+    PY, PX = (H - oy) // P, (W - ox) // P
+    return ws[:PY * PX * 64].view(torch.float64).reshape(PY, PX, 8).clone()
+
+
 def _exposure_args(who: str, image: torch.Tensor, A: torch.Tensor, *more: torch.Tensor):
     """The device, and A as a contiguous [12] view: `image` (and every tensor of `more`) float32 [3,H,W] of one shape and contiguous
     (a view at any 4-byte offset is taken as it is: the library picks its scalar path), A float32 with 12 elements."""

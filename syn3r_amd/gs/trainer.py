@@ -36,6 +36,7 @@ from .mcmc import MCMCControl
 from .params import OptimizationParams, expon_lr
 from .pose import PoseTable
 from .train_ops import FusedAdam, depth_correlation_loss, image_metrics, l1_loss, photometric_loss
+from .train_ops import depth_correlation_local_loss, depth_correlation_local_loss_step
 from .train_ops import depth_correlation_loss_step, exposure_apply, exposure_apply_step, l1_loss_step, photometric_loss_step
 from .train_ops import mcmc_noise, mcmc_reg_step
 
@@ -331,7 +332,24 @@ class GSTrainer:
 
     # ------------------------------------------------------------------ the loss of one step, assembled once for the two routes
     def _depth_term_prior(self, cam: Camera) -> Optional[torch.Tensor]:
-        return self.depth_prior(cam) if self.opt.depth_weight > 0.0 else None
+        """The prior of a step on `cam` when either depth-correlation term is on (None: neither, or a camera without a prior)"""
+        return self.depth_prior(cam) if self.opt.depth_weight > 0.0 or self.opt.depth_local_weight > 0.0 else None
+
+    def depth_patch_origin(self, cam: Camera, iteration: Optional[int] = None) -> Tuple[int, int]:
+        """The origin (oy, ox) of the patch grid of `opt.depth_local_weight` for a step on `cam` at `iteration` (default: the
+        current one).  With `opt.depth_patch_jitter` it is drawn uniformly from [0, min(P, H - P + 1)) x [0, min(P, W - P + 1)) -
+        at least one full patch always fits - by a generator seeded with (`opt.seed`, iteration) ALONE: not `self._rng`, so the
+        camera-pick sequence is the one of a run without the term, a resumed run continues the sequence, and a checkpoint holds
+        nothing new.  Without jitter (0, 0).  The rule is chosen, not taken from a source: UNPINNED."""
+        P, H, W = int(self.opt.depth_patch_size), int(cam.image_height), int(cam.image_width)
+        if H < P or W < P:
+            raise ValueError(f"OptimizationParams.depth_patch_size = {P} does not fit a {H} x {W} camera: the patch-wise depth term "
+                             "needs at least one full patch")
+        if not self.opt.depth_patch_jitter:
+            return 0, 0
+        it = self.iteration if iteration is None else int(iteration)
+        rng = np.random.default_rng([int(self.opt.seed) & (2 ** 64 - 1), it])
+        return int(rng.integers(min(P, H - P + 1))), int(rng.integers(min(P, W - P + 1)))
 
     def _photo_loss(self, image: torch.Tensor, cam: Camera, with_grad: bool):
         """The photometric term of a step on `cam`: the scalar weight is `cam.cam_confidence`, the per-pixel one `cam.confidence_map`
@@ -373,8 +391,12 @@ class GSTrainer:
                 d_color = self.exposure.backward(color, cam, d_color)       # then ITS Adam step (no host read)
                 self.exposure.step(cam)
             d_depth = None
-            if prior is not None:
+            if prior is not None and self.opt.depth_weight > 0.0:
                 d_loss, d_depth = depth_correlation_loss_step(depth, prior, self.opt.depth_weight, self.opt.depth_offset)
+                loss = loss + d_loss
+            if prior is not None and self.opt.depth_local_weight > 0.0:        # ADDED into the global term's buffer when both are on
+                d_loss, d_depth = depth_correlation_local_loss_step(depth, prior, self.opt.depth_local_weight, self.opt.depth_patch_size,
+                                                                    self.depth_patch_origin(cam), self.opt.depth_offset, grad_out=d_depth)
                 loss = loss + d_loss
             extra = {}
             if self.opt.densify_abs_grad:             # (uninitialised: the backward writes every row)
@@ -410,8 +432,11 @@ class GSTrainer:
             # (un-vendored): UNPINNED.
             loss = loss + (self.opt.lpips_weight * float(cam.cam_confidence)) * self.lpips(image.clamp(0, 1), cam.original_image)
         prior = self._depth_term_prior(cam)
-        if prior is not None:
+        if prior is not None and self.opt.depth_weight > 0.0:
             loss = loss + depth_correlation_loss(out["depth"], prior, self.opt.depth_weight, self.opt.depth_offset)
+        if prior is not None and self.opt.depth_local_weight > 0.0:
+            loss = loss + depth_correlation_local_loss(out["depth"], prior, self.opt.depth_local_weight, self.opt.depth_patch_size,
+                                                       self.depth_patch_origin(cam), self.opt.depth_offset)
         if self.opt.mcmc:                             # the two L1 regularisers on the plain opacity and scales (not the filter_3d ones)
             g = self.gaussians
             loss = loss + (self.opt.mcmc_opacity_reg * g.get_opacity.mean() + self.opt.mcmc_scale_reg * g.get_scaling.mean())
@@ -432,6 +457,11 @@ class GSTrainer:
         its two prior transforms, `train_ops.depth_correlation_loss`) for a camera with a prior (`depth_prior`: `cam.depth_image` or
         the injected `depth_net`); a camera without one skips it.  As FSGS' `loss += depth_weight * depth_loss` the term is weighted
         by `depth_weight` alone, not by the camera confidence - UNPINNED for SYN3R's FSGS fork (not vendored).
+        `opt.depth_local_weight` > 0 (EXTENSION, default off: every launch is what it was) adds the same term PATCH-WISE next to it,
+        `depth_local_weight` x the mean over `opt.depth_patch_size` pixel patches of (1 - Pearson) per patch
+        (`train_ops.depth_correlation_local_loss`: two more launches), on both routes and for the same cameras, weighted by
+        `depth_local_weight` alone; the patch grid's origin is `depth_patch_origin`'s.  A camera smaller than the patch on a side is a
+        ValueError.  On the explicit route its gradient is added into the global term's buffer when both are on.
         `cam.confidence_map` (EXTENSION, default None: the scalar-only, reference-shaped loss): a per-pixel weight on the photometric
         term (L1 and D-SSIM, `train_ops.photometric_loss(weight_map=)`) on top of the scalar `cam.cam_confidence`, on both the
         explicit and the autograd path.  The depth-correlation and LPIPS terms are NOT touched by the map.

@@ -92,6 +92,13 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--depth_weight", type=float, default=0.0,
                     help="weight of FSGS' depth-correlation term, 1 - Pearson(rendered depth, monocular prior), on every training step "
                          "(0 = off); views need a prior (Camera.depth_image or an injected GSTrainer.depth_net)")
+    ap.add_argument("--depth_local_weight", type=float, default=0.0,
+                    help="EXTENSION (not in the reference): weight of the PATCH-WISE depth-correlation term, the mean over "
+                         "--depth_patch_size pixel patches of 1 - Pearson(rendered depth, prior) per patch (a monocular prior is "
+                         "consistent only locally), next to --depth_weight (0 = off); the patch grid's origin is drawn per step")
+    ap.add_argument("--depth_patch_size", type=int, default=32,
+                    help="patch size of --depth_local_weight in pixels (2 .. 256, no larger than a view's sides); chosen, not taken "
+                         "from a source, and resolution dependent")
     ap.add_argument("--pixel_confidence", type=int, default=0, choices=(0, 1),
                     help="1: EXTENSION (not in the reference) - every diffusion pseudo-view is weighted per pixel in the photometric loss by "
                          "1 - the fused uncertainty of its interpolation (backward_warp only), on top of --cam_confidence; the pairs' .pt "
@@ -290,7 +297,7 @@ def synthetic_scene(name: str, args, device) -> dict:
     """`synthetic:<seed>[:<N>]` — a seeded Gaussian cloud rendered from three cameras on a baseline (the views to fit),
     a perturbed copy of it as the initial model, and two held-out cameras between the inputs for PSNR / SSIM.  Each training
     camera carries the truth cloud's disparity as its depth prior (`depth_image`: alpha / depth where alpha >= 0.5, else 0;
-    read only when `--depth_weight` > 0).  `--sh_degree` d (0..3): the model's largest SH degree; the 16 coefficient rows stay,
+    read only when `--depth_weight` or `--depth_local_weight` > 0).  `--sh_degree` d (0..3): the model's largest SH degree; the 16 coefficient rows stay,
     those above (d + 1)^2 are never read."""
     from .gs import Camera, GaussianModel, GSTrainer, OptimizationParams
     from .synthetic import synthetic_gaussians
@@ -376,6 +383,8 @@ def run_scene(name: str, args, device, factory: Callable) -> List[float]:
         comps = args.svd_dir if args.svd_dir else _stand_in_svd(device)
     trainer.opt.lpips_weight = float(getattr(args, "lpips_weight", 0.0))
     trainer.opt.depth_weight = float(getattr(args, "depth_weight", 0.0))
+    trainer.opt.depth_local_weight = float(getattr(args, "depth_local_weight", 0.0))
+    trainer.opt.depth_patch_size = int(getattr(args, "depth_patch_size", 32))
     trainer.opt.use_proximity_densify = bool(getattr(args, "use_proximity_densify", 0))
     trainer.opt = apply_trainer_flags(trainer.opt, args)
     if getattr(args, "gs_schedule", "constant") == "published" and trainer.iteration == 0:
