@@ -885,6 +885,46 @@ int syn3r_depth_corr_local_loss_step(const float* depth, const float* prior, int
                                      float offset, int mode, const float* grad_loss, float* parts, float* grad_depth, int accumulate,
                                      void* ws, size_t ws_bytes, void* stream);
 
+/* Prior-free edge-aware depth smoothness (EXTENSION: the reference has none; the form of Monodepth2, Godard et al., ICCV 2019, which
+ * DNGaussian-, SparseGS- and RegNeRF-style sparse-view pipelines use as well): the rendered depth d [H,W] fp32 should be piecewise
+ * smooth and may jump only where the camera's own target image has an edge.  It needs no depth prior.
+ *   weights = [wx, wy], two fp32 planes [2,H,W] from the image I [3,H,W] (syn3r_depth_edge_weights):
+ *     wx[y,x] = exp(-gamma * mean_c |I_c[y,x+1] - I_c[y,x]|)      wy[y,x] = exp(-gamma * mean_c |I_c[y+1,x] - I_c[y,x]|)
+ *     (fp32, expf; the last column of wx and the last row of wy are written as zeros)
+ *   m    = mean of d over all H*W pixels
+ *   S_x  = 1/N_x * sum_{y, x<W-1} wx[y,x] * |d[y,x+1] - d[y,x]|      N_x = H (W-1)
+ *   S_y  = 1/N_y * sum_{y<H-1, x} wy[y,x] * |d[y+1,x] - d[y,x]|      N_y = (H-1) W
+ *   loss = weight * (S_x + S_y) / m
+ *   grad_depth_i = weight * grad_loss[0] * [ (dS/dd_i) / m - (S_x + S_y) / (m^2 H W) ]      (grad_loss: device scalar, NULL = 1)
+ * dS/dd_i is the signed sum over the up to four edges at pixel i, sign(0) = 0; the derivative goes through the mean.  A direction
+ * without pairs (W == 1 or H == 1) contributes 0.  m <= 0 (an empty render) gives loss 0 and a zero gradient, never NaN.  The loss
+ * entries treat the last column of wx and the last row of wy as absent, whatever they hold.  gamma = 1 and the division by the
+ * mean are recalled from Monodepth2 (not available): UNPINNED, hence gamma is an argument.
+ * The statistics pass keeps fp32 running sums per thread, adds them over the wave and the block's waves in a fixed order and leaves
+ * one row per block in ws; the rows are added in fp64 in a fixed order.  The gradient is a gather (every pixel forms its own edges,
+ * fp64, one fp32 rounding): no float atomics.  The grid is a function of H and W alone: bitwise repeatable for a given shape.
+ * Rows go through 16-byte accesses when every pointer is 16-byte aligned and W % 4 == 0, anything else through scalar ones, with
+ * the same bits.  parts (device, 16-byte aligned, 4 floats): [loss, S_x, S_y, m].
+ * accumulate 0: every pixel of grad_depth is written (the buffer may hold anything); accumulate 1: the gradient is ADDED to it (the
+ * depth terms then share one buffer without an add launch).
+ * ws: syn3r_depth_smooth_workspace_bytes(H, W) bytes (0 for H or W outside [1, 2^15]), 16-byte aligned; it holds the rows the
+ * backward reads, so syn3r_depth_smooth_loss_backward takes the SAME workspace.
+ * Rejections before any HIP call (SYN3R_E_INVALID): null pointers, H or W outside [1, 2^15], a non-finite weight or gamma, gamma < 0,
+ * accumulate not 0 or 1, a misaligned parts or workspace, weights (syn3r_depth_edge_weights) or grad_depth overlapping an input; a
+ * short workspace is SYN3R_E_WORKSPACE. */
+int syn3r_depth_edge_weights(const float* image, int H, int W, float gamma, float* weights /* [2,H,W] */, void* stream);
+size_t syn3r_depth_smooth_workspace_bytes(int H, int W);
+/* value only: two launches (statistics, one-block combine) */
+int syn3r_depth_smooth_loss(const float* depth, const float* weights, int H, int W, float weight, float* parts, void* ws,
+                            size_t ws_bytes, void* stream);
+/* the gradient launch on the rows of syn3r_depth_smooth_loss */
+int syn3r_depth_smooth_loss_backward(const float* depth, const float* weights, int H, int W, float weight, const float* grad_loss,
+                                     const void* ws, size_t ws_bytes, float* grad_depth, int accumulate, void* stream);
+/* Value AND gradient in two launches: the statistics, then the gradient, every block of which combines the rows in the same fixed
+ * order and whose block 0 writes parts.  Same bits as syn3r_depth_smooth_loss + syn3r_depth_smooth_loss_backward. */
+int syn3r_depth_smooth_loss_step(const float* depth, const float* weights, int H, int W, float weight, const float* grad_loss,
+                                 float* parts, float* grad_depth, int accumulate, void* ws, size_t ws_bytes, void* stream);
+
 /* Per-camera affine exposure compensation (EXTENSION: the reference has none; the published 3DGS code base has since grown a
  * per-image exposure model, gsplat an appearance optimisation).  A is 3 x 4 fp32, row-major, 12 floats in DEVICE memory; image,
  * out, grad_out and grad_image are [3,H,W] fp32 planes:

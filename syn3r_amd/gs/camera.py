@@ -38,11 +38,15 @@ class Camera:
     `confidence_map` (EXTENSION, not in the reference's camera; default None): a per-pixel weight [H,W] (or [1,H,W]) in [0,1] for
     the photometric loss of this view (`train_ops.photometric_loss(weight_map=)`), on top of the scalar `cam_confidence`; stored as
     fp32 [H,W] on `data_device`, its shape checked against the image's.  Also settable as an attribute.  `gt_alpha_mask` stays
-    ignored: in published 3DGS it multiplies the image, which is a different thing."""
+    ignored: in published 3DGS it multiplies the image, which is a different thing.
+    `depth_edge_weights` (EXTENSION; default None): the caller's own edge weights [2,H,W] = [wx, wy] for the trainer's depth-smoothness
+    term (`OptimizationParams.depth_smooth_weight`), stored as fp32 on `data_device` and then NEVER recomputed; None: the trainer
+    computes them from `original_image` once (`GSTrainer.depth_edge_weights`) and keeps them in `_depth_edge_cache`, 8 bytes per
+    pixel, with the gamma and the image they were made from.  Also settable as an attribute."""
 
     def __init__(self, colmap_id, R, T, FoVx, FoVy, image, gt_alpha_mask=None, image_name="", uid=0,
                  trans=np.array([0.0, 0.0, 0.0]), scale=1.0, data_device="cuda", cam_confidence: float = 1.0, depth_image=None,
-                 confidence_map=None):
+                 confidence_map=None, depth_edge_weights=None):
         self.uid, self.colmap_id, self.image_name = uid, colmap_id, image_name
         self.R, self.T, self.FoVx, self.FoVy = np.asarray(R, np.float32), np.asarray(T, np.float32), FoVx, FoVy
         self.cam_confidence = float(cam_confidence)
@@ -65,6 +69,9 @@ class Camera:
             self.depth_image = (d[0] if d.dim() == 3 and d.shape[0] == 1 else d).contiguous()
         self._confidence_map = None
         self.confidence_map = confidence_map
+        self._depth_edge_weights = None
+        self._depth_edge_cache = None    # (gamma, image, image version, weights) of GSTrainer.depth_edge_weights
+        self.depth_edge_weights = depth_edge_weights
 
     @property
     def confidence_map(self) -> Optional[torch.Tensor]:
@@ -85,16 +92,35 @@ class Camera:
                              f"got {tuple(m.shape)}")
         self._confidence_map = m.contiguous()
 
+    @property
+    def depth_edge_weights(self) -> Optional[torch.Tensor]:
+        return self._depth_edge_weights
+
+    @depth_edge_weights.setter
+    def depth_edge_weights(self, w):
+        if w is None:
+            self._depth_edge_weights = None
+            return
+        w = torch.as_tensor(w).detach().to(dtype=torch.float32, device=self.data_device)
+        hw = (self.image_height, self.image_width)
+        if hw[0] is None:
+            raise ValueError("Camera: depth_edge_weights need a camera with an image size")
+        if tuple(w.shape) != (2, int(hw[0]), int(hw[1])):
+            raise ValueError(f"Camera: depth_edge_weights must be [2,H,W] for the image's H, W = ({int(hw[0])}, {int(hw[1])}); "
+                             f"got {tuple(w.shape)}")
+        self._depth_edge_weights = w.contiguous()
+
     @classmethod
     def from_w2c(cls, w2c: np.ndarray, K: np.ndarray, H: int, W: int, image=None, **kw):
         """Build from a 4x4 world-to-camera matrix and intrinsics (the orchestrator's pose format)."""
         fovx = 2 * math.atan(W / (2 * K[0, 0]))
         fovy = 2 * math.atan(H / (2 * K[1, 1]))
-        cmap = kw.pop("confidence_map", None)
+        cmap, edge = kw.pop("confidence_map", None), kw.pop("depth_edge_weights", None)
         cam = cls(0, np.asarray(w2c[:3, :3]).T, np.asarray(w2c[:3, 3]), fovx, fovy, image, **kw)
         if image is None:
             cam.image_height, cam.image_width = H, W
         cam.confidence_map = cmap                      # (after the size is known)
+        cam.depth_edge_weights = edge
         return cam
 
     def set_pose(self, R, T):

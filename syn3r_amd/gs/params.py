@@ -31,6 +31,18 @@ class OptimizationParams:
     depth_local_weight: float = 0.0
     depth_patch_size: int = 32
     depth_patch_jitter: bool = True
+    # Prior-free edge-aware depth smoothness (EXTENSION: the reference has none; Monodepth2's form, which DNGaussian-, SparseGS- and
+    # RegNeRF-style sparse-view pipelines use as well): `depth_smooth_weight` x (S_x + S_y) / mean depth, S the mean over a direction's
+    # pixel pairs of exp(-gamma |target image difference|) x |rendered depth difference| (`train_ops.depth_smoothness_loss`,
+    # csrc/depth_smooth.hip).  It needs the camera's own target image alone - no `depth_image`, no `depth_net` - so it acts on
+    # pseudo-views as well.  `depth_smooth_cameras`: "all", "train" (the input views) or "pseudo" (the views `update_cameras`
+    # registered).  The edge weights are computed once per camera and cached on it (8 bytes per pixel).  Weighted by
+    # `depth_smooth_weight` alone, not by the camera confidence or its map, as the other depth terms.  gamma = 1 and the division by
+    # the mean are RECALLED from Monodepth2, which is not available to check against: UNPINNED.  Weight 0 = off: every launch,
+    # gradient, checkpoint and decision is what it was.  Nothing of it goes into checkpoints.
+    depth_smooth_weight: float = 0.0
+    depth_smooth_gamma: float = 1.0             # recalled, UNPINNED
+    depth_smooth_cameras: str = "all"
     # adaptive density control, published 3DGS defaults (Kerbl et al. 2023 section 5.2 and its released arguments); used when
     # training()/finetune() run with disable_densification=False
     percent_dense: float = 0.01

@@ -352,6 +352,95 @@ def depth_correlation_local_records(depth: torch.Tensor, prior: torch.Tensor, pa
     return ws[:PY * PX * 64].view(torch.float64).reshape(PY, PX, 8).clone()
 
 
+def depth_edge_weights(image: torch.Tensor, gamma: float = 1.0) -> torch.Tensor:
+    """The edge weights of the depth-smoothness term from a camera's target image [3,H,W] fp32 (`syn3r_depth_edge_weights`,
+    csrc/depth_smooth.hip: one launch): [2,H,W] fp32, wx[y,x] = exp(-gamma mean_c |I_c[y,x+1] - I_c[y,x]|), wy the same downwards;
+    zeros in the absent last column of wx and last row of wy.  gamma = 1 is recalled from Monodepth2: UNPINNED."""
+    dev = L.require_gpu(image)
+    if image.dim() != 3 or image.shape[0] != 3 or image.dtype != torch.float32:
+        raise ValueError(f"depth_edge_weights: image must be a float32 [3,H,W] tensor, got {image.dtype} {tuple(image.shape)}")
+    image = image.detach().contiguous()
+    H, W = int(image.shape[1]), int(image.shape[2])
+    out = torch.empty((2, H, W), dtype=torch.float32, device=dev)
+    L.check(L.load().syn3r_depth_edge_weights(L.ptr(image), H, W, float(gamma), L.ptr(out), L.stream_ptr(dev)), "depth_edge_weights")
+    return out
+
+
+def _dsmooth_args(who: str, depth: torch.Tensor, weights: torch.Tensor):
+    """(depth, weights) as contiguous fp32 tensors (a view at any 4-byte offset is taken as it is: the library picks its scalar
+    path) and (H, W); depth [1,H,W] or [H,W], weights [2,H,W]."""
+    L.require_gpu(depth, weights)
+    if depth.dtype != torch.float32 or weights.dtype != torch.float32:
+        raise ValueError(f"{who}: depth and weights must be float32")
+    hw = tuple(depth.shape[1:]) if depth.dim() == 3 and depth.shape[0] == 1 else (tuple(depth.shape) if depth.dim() == 2 else None)
+    if hw is None or weights.dim() != 3 or tuple(weights.shape) != (2,) + hw:
+        raise ValueError(f"{who}: depth [1,H,W] or [H,W] and weights [2,H,W] of the same H, W; got {tuple(depth.shape)} and "
+                         f"{tuple(weights.shape)}")
+    return depth.detach().contiguous(), weights.detach().contiguous(), (int(hw[0]), int(hw[1]))
+
+
+class _DepthSmoothLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth: torch.Tensor, weights: torch.Tensor, weight: float):
+        d, w, hw = _dsmooth_args("depth_smoothness_loss", depth, weights)
+        lib = L.load()
+        # own buffer, not the shared workspace cache: the block rows must survive until backward
+        ws = torch.empty(max(lib.syn3r_depth_smooth_workspace_bytes(*hw), 256), dtype=torch.uint8, device=d.device)
+        parts = torch.empty(4, dtype=torch.float32, device=d.device)
+        L.check(lib.syn3r_depth_smooth_loss(L.ptr(d), L.ptr(w), *hw, float(weight), L.ptr(parts), L.ptr(ws), ws.numel(),
+                                            L.stream_ptr(d.device)), "depth_smooth_loss")
+        ctx.save_for_backward(d, w, ws)
+        ctx.args = (hw, float(weight), depth.shape)
+        ctx.mark_non_differentiable(parts)
+        return parts[0].clone(), parts
+
+    @staticmethod
+    def backward(ctx, grad_loss: torch.Tensor, _grad_parts):
+        L.join_active_trace()
+        d, w, ws = ctx.saved_tensors
+        hw, weight, shape = ctx.args
+        go = grad_loss.to(torch.float32).contiguous()
+        grad = torch.empty_like(d)
+        L.check(L.load().syn3r_depth_smooth_loss_backward(L.ptr(d), L.ptr(w), *hw, weight, L.ptr(go), L.ptr(ws), ws.numel(), L.ptr(grad),
+                                                          0, L.stream_ptr(d.device)), "depth_smooth_loss_backward")
+        return grad.reshape(shape), None, None
+
+
+def depth_smoothness_loss(depth: torch.Tensor, weights: torch.Tensor, weight: float = 1.0, return_parts: bool = False):
+    """Prior-free edge-aware smoothness of one rendered depth map (EXTENSION; Monodepth2's form): `weight * (S_x + S_y) / m`, m the
+    mean depth, S_x the mean over the H (W - 1) horizontal pixel pairs of wx |d[y,x+1] - d[y,x]|, S_y the same over the (H - 1) W
+    vertical ones with wy; `weights` = [wx, wy] from `depth_edge_weights` (their last column / row is never read).  The gradient goes
+    through the mean; m <= 0 (an empty render) gives 0 and a zero gradient, not NaN.  The division by the mean is recalled from
+    Monodepth2: UNPINNED.  Device scalar, no host synchronisation; backward is the kernel's gradient pass (csrc/depth_smooth.hip).
+    `return_parts`: also the device tensor [loss, S_x, S_y, m]."""
+    loss, parts = _DepthSmoothLoss.apply(depth, weights, weight)
+    return (loss, parts) if return_parts else loss
+
+
+def depth_smoothness_loss_step(depth: torch.Tensor, weights: torch.Tensor, weight: float = 1.0, grad_loss: torch.Tensor = None,
+                               grad_out: torch.Tensor = None, return_parts: bool = False):
+    """Value AND depth gradient of `depth_smoothness_loss` without autograd (`syn3r_depth_smooth_loss_step`: two launches).  Returns
+    (loss - a view of parts[0] -, grad_depth shaped like depth) [+ parts]; `grad_loss`: device scalar, default 1.  `grad_out`
+    (float32, contiguous, depth's number of elements, on its device): the gradient is ADDED to it, and it is what comes back;
+    without it a new tensor, every pixel written.  Same bits as the autograd Function's forward + backward."""
+    who = "depth_smoothness_loss_step"
+    d, w, hw = _dsmooth_args(who, depth, weights)
+    dev = d.device
+    lib = L.load()
+    if grad_out is not None:
+        L.require_gpu(d, grad_out)
+        if grad_out.dtype != torch.float32 or grad_out.numel() != d.numel() or not grad_out.is_contiguous():
+            raise ValueError(f"{who}: grad_out must be a contiguous float32 tensor of depth's {d.numel()} elements")
+    ws = L.workspace(dev, lib.syn3r_depth_smooth_workspace_bytes(*hw), "dsmooth_step")
+    parts = torch.empty(4, dtype=torch.float32, device=dev)
+    grad = torch.empty_like(d) if grad_out is None else grad_out
+    go = grad_loss.to(torch.float32).contiguous() if grad_loss is not None else None
+    L.check(lib.syn3r_depth_smooth_loss_step(L.ptr(d), L.ptr(w), *hw, float(weight), L.ptr(go), L.ptr(parts), L.ptr(grad),
+                                             int(grad_out is not None), L.ptr(ws), ws.numel(), L.stream_ptr(dev)),
+            "depth_smooth_loss_step")
+    return (parts[0], grad, parts) if return_parts else (parts[0], grad)
+
+
 def _exposure_args(who: str, image: torch.Tensor, A: torch.Tensor, *more: torch.Tensor):
     """The device, and A as a contiguous [12] view: `image` (and every tensor of `more`) float32 [3,H,W] of one shape and contiguous
     (a view at any 4-byte offset is taken as it is: the library picks its scalar path), A float32 with 12 elements."""

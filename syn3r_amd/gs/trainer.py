@@ -38,7 +38,12 @@ from .pose import PoseTable
 from .train_ops import FusedAdam, depth_correlation_loss, image_metrics, l1_loss, photometric_loss
 from .train_ops import depth_correlation_local_loss, depth_correlation_local_loss_step
 from .train_ops import depth_correlation_loss_step, exposure_apply, exposure_apply_step, l1_loss_step, photometric_loss_step
+from .train_ops import depth_edge_weights as edge_weights_of_image
+from .train_ops import depth_smoothness_loss, depth_smoothness_loss_step
 from .train_ops import mcmc_noise, mcmc_reg_step
+
+
+DEPTH_SMOOTH_CAMERA_KINDS = ("all", "train", "pseudo")
 
 
 class GSTrainer:
@@ -60,6 +65,9 @@ class GSTrainer:
             raise ValueError(f"OptimizationParams.pose_opt_cameras must be 'train', 'pseudo' or 'all', got {self.opt.pose_opt_cameras!r}")
         if self.opt.exposure_cameras not in EXPOSURE_CAMERA_KINDS:
             raise ValueError(f"OptimizationParams.exposure_cameras must be 'pseudo', 'train' or 'all', got {self.opt.exposure_cameras!r}")
+        if self.opt.depth_smooth_cameras not in DEPTH_SMOOTH_CAMERA_KINDS:
+            raise ValueError("OptimizationParams.depth_smooth_cameras must be 'all', 'train' or 'pseudo', got "
+                             f"{self.opt.depth_smooth_cameras!r}")
         if self.opt.mcmc:
             if self.opt.use_proximity_densify or self.opt.densify_abs_grad:
                 raise ValueError("OptimizationParams.mcmc replaces the clone / split / prune control: use_proximity_densify and "
@@ -351,6 +359,37 @@ class GSTrainer:
         rng = np.random.default_rng([int(self.opt.seed) & (2 ** 64 - 1), it])
         return int(rng.integers(min(P, H - P + 1))), int(rng.integers(min(P, W - P + 1)))
 
+    def depth_edge_weights(self, cam: Camera) -> torch.Tensor:
+        """The edge weights [2,H,W] of the depth-smoothness term for `cam`: the caller's own (`cam.depth_edge_weights`, never
+        recomputed), else `train_ops.depth_edge_weights(cam.original_image, opt.depth_smooth_gamma)` computed ONCE under no_grad and
+        cached on the camera with the gamma and the image (its identity and version) they were made from; recomputed when either
+        changes.  8 bytes per pixel per camera."""
+        own = getattr(cam, "depth_edge_weights", None)
+        if own is not None:
+            return own
+        image, gamma = cam.original_image, float(self.opt.depth_smooth_gamma)
+        if image is None:
+            raise ValueError("depth_edge_weights: the camera has no original_image")
+        c = getattr(cam, "_depth_edge_cache", None)
+        if c is None or c[0] != gamma or c[1] is not image or c[2] != image._version:
+            with torch.no_grad():
+                c = (gamma, image, image._version, edge_weights_of_image(image, gamma))
+            cam._depth_edge_cache = c
+        return c[3]
+
+    def _depth_smooth_weights(self, cam: Camera) -> Optional[torch.Tensor]:
+        """The edge weights of a step on `cam` when the depth-smoothness term acts on it (None: the term is off, the camera is not of
+        `opt.depth_smooth_cameras`, or it has no target image).  Touches neither `depth_prior` nor `depth_net`."""
+        if not self.opt.depth_smooth_weight > 0.0:
+            return None
+        kind = self.opt.depth_smooth_cameras
+        if kind not in DEPTH_SMOOTH_CAMERA_KINDS:
+            raise ValueError(f"OptimizationParams.depth_smooth_cameras must be 'all', 'train' or 'pseudo', got {kind!r}")
+        pseudo = bool(getattr(cam, "is_pseudo", False))
+        if (kind == "train" and pseudo) or (kind == "pseudo" and not pseudo) or cam.original_image is None:
+            return None
+        return self.depth_edge_weights(cam)
+
     def _photo_loss(self, image: torch.Tensor, cam: Camera, with_grad: bool):
         """The photometric term of a step on `cam`: the scalar weight is `cam.cam_confidence`, the per-pixel one `cam.confidence_map`
         (None: none), `opt.lambda_dssim` > 0 takes the D-SSIM loss and 0 plain L1.  `with_grad` (the explicit route): the operators
@@ -379,6 +418,7 @@ class GSTrainer:
         if conf is not None and getattr(conf, "requires_grad", False):
             raise ValueError("_explicit_step: a confidence tensor that requires grad needs train_step(explicit=False)")
         prior = self._depth_term_prior(cam)
+        edge = self._depth_smooth_weights(cam)
         f3 = self.ensure_filter_3D()
         with torch.no_grad():
             # log-scales / raw quaternions / logits in, THEIR gradients out (syn3r_raster_*_raw)
@@ -397,6 +437,9 @@ class GSTrainer:
             if prior is not None and self.opt.depth_local_weight > 0.0:        # ADDED into the global term's buffer when both are on
                 d_loss, d_depth = depth_correlation_local_loss_step(depth, prior, self.opt.depth_local_weight, self.opt.depth_patch_size,
                                                                     self.depth_patch_origin(cam), self.opt.depth_offset, grad_out=d_depth)
+                loss = loss + d_loss
+            if edge is not None:                      # prior-free smoothness: ADDED into the buffer of the terms above when one is on
+                d_loss, d_depth = depth_smoothness_loss_step(depth, edge, self.opt.depth_smooth_weight, grad_out=d_depth)
                 loss = loss + d_loss
             extra = {}
             if self.opt.densify_abs_grad:             # (uninitialised: the backward writes every row)
@@ -437,6 +480,9 @@ class GSTrainer:
         if prior is not None and self.opt.depth_local_weight > 0.0:
             loss = loss + depth_correlation_local_loss(out["depth"], prior, self.opt.depth_local_weight, self.opt.depth_patch_size,
                                                        self.depth_patch_origin(cam), self.opt.depth_offset)
+        edge = self._depth_smooth_weights(cam)
+        if edge is not None:
+            loss = loss + depth_smoothness_loss(out["depth"], edge, self.opt.depth_smooth_weight)
         if self.opt.mcmc:                             # the two L1 regularisers on the plain opacity and scales (not the filter_3d ones)
             g = self.gaussians
             loss = loss + (self.opt.mcmc_opacity_reg * g.get_opacity.mean() + self.opt.mcmc_scale_reg * g.get_scaling.mean())
@@ -462,6 +508,14 @@ class GSTrainer:
         (`train_ops.depth_correlation_local_loss`: two more launches), on both routes and for the same cameras, weighted by
         `depth_local_weight` alone; the patch grid's origin is `depth_patch_origin`'s.  A camera smaller than the patch on a side is a
         ValueError.  On the explicit route its gradient is added into the global term's buffer when both are on.
+        `opt.depth_smooth_weight` > 0 (EXTENSION, default off: every launch is what it was) adds the prior-free edge-aware smoothness
+        term `depth_smooth_weight` x (S_x + S_y) / mean depth after the two Pearson terms (`train_ops.depth_smoothness_loss`: two more
+        launches; S the mean of exp(-`depth_smooth_gamma` |target image difference|) |rendered depth difference| over a direction's
+        pixel pairs), on both routes, for the cameras of `opt.depth_smooth_cameras` ("all", "train", "pseudo") that have an
+        `original_image`.  It needs no prior: `depth_prior` / `depth_net` are not touched by it, so pseudo-views are regularised as
+        well.  The edge weights come from `depth_edge_weights(cam)` (once per camera, cached on it).  Weighted by
+        `depth_smooth_weight` alone, not by the camera confidence or its map.  On the explicit route its gradient is added into the
+        Pearson terms' buffer when one of them made one.  gamma = 1 and the division by the mean are recalled from Monodepth2: UNPINNED.
         `cam.confidence_map` (EXTENSION, default None: the scalar-only, reference-shaped loss): a per-pixel weight on the photometric
         term (L1 and D-SSIM, `train_ops.photometric_loss(weight_map=)`) on top of the scalar `cam.cam_confidence`, on both the
         explicit and the autograd path.  The depth-correlation and LPIPS terms are NOT touched by the map.

@@ -99,6 +99,16 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--depth_patch_size", type=int, default=32,
                     help="patch size of --depth_local_weight in pixels (2 .. 256, no larger than a view's sides); chosen, not taken "
                          "from a source, and resolution dependent")
+    ap.add_argument("--depth_smooth_weight", type=float, default=0.0,
+                    help="EXTENSION (not in the reference): weight of the prior-free edge-aware smoothness term on the rendered depth, "
+                         "(S_x + S_y) / mean depth with S the mean of exp(-gamma |image gradient|) |depth gradient| per direction "
+                         "(Monodepth2's form; needs no depth prior, so it runs on pseudo-views as well); 0 = off")
+    ap.add_argument("--depth_smooth_gamma", type=float, default=1.0,
+                    help="OptimizationParams.depth_smooth_gamma: the edge weights' decay with the target image's contrast (1: "
+                         "recalled from Monodepth2, UNPINNED)")
+    ap.add_argument("--depth_smooth_cameras", type=str, default="all", choices=("all", "train", "pseudo"),
+                    help="OptimizationParams.depth_smooth_cameras: the cameras --depth_smooth_weight acts on - the input views, the "
+                         "diffusion pseudo-views, or both")
     ap.add_argument("--pixel_confidence", type=int, default=0, choices=(0, 1),
                     help="1: EXTENSION (not in the reference) - every diffusion pseudo-view is weighted per pixel in the photometric loss by "
                          "1 - the fused uncertainty of its interpolation (backward_warp only), on top of --cam_confidence; the pairs' .pt "
@@ -185,7 +195,8 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                                                        "--pose_opt_cameras", "--pose_lr_rotation", "--pose_lr_translation",
                                                        "--pose_opt_interval", "--exposure_opt", "--exposure_cameras", "--exposure_lr",
                                                        "--exposure_lr_final", "--mcmc", "--mcmc_cap_max", "--mcmc_noise_lr",
-                                                       "--mcmc_opacity_reg", "--mcmc_scale_reg"]
+                                                       "--mcmc_opacity_reg", "--mcmc_scale_reg", "--depth_smooth_weight",
+                                                       "--depth_smooth_gamma", "--depth_smooth_cameras"]
     # (a token that IS a declared flag is not an abbreviation of a longer one: --densify_abs_grad / --densify_abs_grad_threshold)
     cut = [t for t in given if t.startswith("--") and t.split("=")[0] not in declared
            and any(d.startswith(t.split("=")[0]) for d in declared)]
@@ -220,7 +231,8 @@ def apply_trainer_flags(opt, args):
     (0, the default, leaves the field as `opt` has it); `--densify_abs_grad_threshold`, when given, sets its field.  `--pose_opt 1`
     sets `pose_opt`; `--pose_opt_cameras`, `--pose_lr_rotation`, `--pose_lr_translation` and `--pose_opt_interval`, when given, set theirs.
     `--exposure_opt 1` sets `exposure_opt`; `--exposure_cameras`, `--exposure_lr` and `--exposure_lr_final`, when given, set theirs.
-    `--mcmc 1` sets `mcmc`; `--mcmc_cap_max`, `--mcmc_noise_lr`, `--mcmc_opacity_reg` and `--mcmc_scale_reg`, when given, set theirs.  (--sh_degree
+    `--mcmc 1` sets `mcmc`; `--mcmc_cap_max`, `--mcmc_noise_lr`, `--mcmc_opacity_reg` and `--mcmc_scale_reg`, when given, set theirs.
+    `--depth_smooth_weight`, `--depth_smooth_gamma` and `--depth_smooth_cameras` set theirs (the flags' defaults are the options' own: 0, 1, "all").  (--sh_degree
     describes the model, not the optimiser: the scene factory reads it.)"""
     import dataclasses
     new = {}
@@ -253,6 +265,9 @@ def apply_trainer_flags(opt, args):
     if getattr(args, "mcmc", 0):
         new["mcmc"] = True
     for flag, typ in (("mcmc_cap_max", int), ("mcmc_noise_lr", float), ("mcmc_opacity_reg", float), ("mcmc_scale_reg", float)):
+        if getattr(args, flag, None) is not None:
+            new[flag] = typ(getattr(args, flag))
+    for flag, typ in (("depth_smooth_weight", float), ("depth_smooth_gamma", float), ("depth_smooth_cameras", str)):
         if getattr(args, flag, None) is not None:
             new[flag] = typ(getattr(args, flag))
     return dataclasses.replace(opt, **new)
