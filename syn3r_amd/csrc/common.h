@@ -31,6 +31,30 @@ inline int check_launch(const char* who) {
     return SYN3R_OK;
 }
 
+// Argument checks the trainer entries share; like SYN3R_REQUIRE they leave the message with set_error, and they return the code.
+// An entry's workspace: 16-byte aligned and at least `need` bytes, `size_fn` the name of the function that says how many.
+inline int check_workspace(const char* who, const void* ws, size_t ws_bytes, size_t need, const char* size_fn) {
+    SYN3R_REQUIRE(((uintptr_t)ws & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    if (ws_bytes < need) {
+        set_error("%s: workspace %zu < %zu bytes (%s)", who, ws_bytes, need, size_fn);
+        return SYN3R_E_WORKSPACE;
+    }
+    return SYN3R_OK;
+}
+// The float4 of partial results a loss entry writes with one store.
+inline int check_parts(const char* who, const float* parts) {
+    SYN3R_REQUIRE(parts, "%s: null pointer", who);
+    SYN3R_REQUIRE(((uintptr_t)parts & 15) == 0, "%s: parts must be 16-byte aligned", who);
+    return SYN3R_OK;
+}
+// [a, a + a_bytes) and [b, b + b_bytes) share a byte
+inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 ? b0 - a0 < a_bytes : a0 - b0 < b_bytes;
+}
+// neither NaN nor infinite
+inline bool finite_f32(float v) { return v == v && fabsf(v) <= 3.0e38f; }
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-DEVICE setting: remembered per (kernel, device), so a host that
 // drives several GPUs from one process gets the large-LDS attribute on each of them.
 struct DevOnce { std::atomic<unsigned long long> done{0}; };

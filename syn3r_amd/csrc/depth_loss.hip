@@ -217,15 +217,9 @@ int dc_check(const char* who, const float* depth, const float* prior, long long 
     SYN3R_REQUIRE(n >= 2 && n <= kDcMaxN, "%s: n=%lld must be in [2, 2^30]", who, n);
     SYN3R_REQUIRE(depth && prior && ws, "%s: null pointer", who);
     SYN3R_REQUIRE(mode == SYN3R_DCORR_MIN || mode == SYN3R_DCORR_A || mode == SYN3R_DCORR_B, "%s: mode=%d is not MIN / A / B", who, mode);
-    SYN3R_REQUIRE(weight == weight && fabsf(weight) <= 3.0e38f, "%s: weight must be finite", who);
-    SYN3R_REQUIRE(mode == SYN3R_DCORR_A || (offset == offset && fabsf(offset) <= 3.0e38f), "%s: offset must be finite", who);
-    SYN3R_REQUIRE(((uintptr_t)ws & 15) == 0, "%s: workspace must be 16-byte aligned", who);
-    if (ws_bytes < syn3r_depth_corr_loss_workspace_bytes(n)) {
-        set_error("%s: workspace %zu < %zu bytes (syn3r_depth_corr_loss_workspace_bytes)", who, ws_bytes,
-                  syn3r_depth_corr_loss_workspace_bytes(n));
-        return SYN3R_E_WORKSPACE;
-    }
-    return SYN3R_OK;
+    SYN3R_REQUIRE(finite_f32(weight), "%s: weight must be finite", who);
+    SYN3R_REQUIRE(mode == SYN3R_DCORR_A || finite_f32(offset), "%s: offset must be finite", who);
+    return check_workspace(who, ws, ws_bytes, syn3r_depth_corr_loss_workspace_bytes(n), "syn3r_depth_corr_loss_workspace_bytes");
 }
 
 void dc_stats(const float* depth, const float* prior, long long n, float offset, int mode, void* ws, hipStream_t stream) {
@@ -261,8 +255,7 @@ extern "C" int syn3r_depth_corr_loss(const float* depth, const float* prior, lon
                                      float* parts, void* ws, size_t ws_bytes, void* stream_) {
     const int rc = dc_check("depth_corr_loss", depth, prior, n, weight, offset, mode, ws, ws_bytes);
     if (rc) return rc;
-    SYN3R_REQUIRE(parts, "depth_corr_loss: null pointer");
-    SYN3R_REQUIRE(((uintptr_t)parts & 15) == 0, "depth_corr_loss: parts must be 16-byte aligned");
+    if (const int rp = check_parts("depth_corr_loss", parts)) return rp;
     hipStream_t stream = (hipStream_t)stream_;
     dc_stats(depth, prior, n, offset, mode, ws, stream);
     SYN3R_LAUNCH(k_dcorr_final, dim3(1), dim3(kDcThreads), 0, stream, (const DcMom*)ws, dc_blocks(n), mode, weight, parts);
@@ -285,8 +278,8 @@ extern "C" int syn3r_depth_corr_loss_step(const float* depth, const float* prior
                                           void* stream_) {
     const int rc = dc_check("depth_corr_loss_step", depth, prior, n, weight, offset, mode, ws, ws_bytes);
     if (rc) return rc;
-    SYN3R_REQUIRE(parts && grad_depth, "depth_corr_loss_step: null pointer");
-    SYN3R_REQUIRE(((uintptr_t)parts & 15) == 0, "depth_corr_loss_step: parts must be 16-byte aligned");
+    SYN3R_REQUIRE(grad_depth, "depth_corr_loss_step: null pointer");
+    if (const int rp = check_parts("depth_corr_loss_step", parts)) return rp;
     hipStream_t stream = (hipStream_t)stream_;
     dc_stats(depth, prior, n, offset, mode, ws, stream);
     dc_grad(depth, prior, n, weight, offset, mode, grad_loss, ws, grad_depth, parts, stream);
@@ -519,15 +512,10 @@ int dl_check(const char* who, const float* depth, const float* prior, int H, int
     SYN3R_REQUIRE(dl_geom(H, W, P, oy, ox, g), "%s: K=0: no full %dx%d patch in %dx%d from origin (%d, %d)", who, P, P, H, W, oy, ox);
     SYN3R_REQUIRE(depth && prior && ws, "%s: null pointer", who);
     SYN3R_REQUIRE(mode == SYN3R_DCORR_MIN || mode == SYN3R_DCORR_A || mode == SYN3R_DCORR_B, "%s: mode=%d is not MIN / A / B", who, mode);
-    SYN3R_REQUIRE(weight == weight && fabsf(weight) <= 3.0e38f, "%s: weight must be finite", who);
-    SYN3R_REQUIRE(mode == SYN3R_DCORR_A || (offset == offset && fabsf(offset) <= 3.0e38f), "%s: offset must be finite", who);
-    SYN3R_REQUIRE(((uintptr_t)ws & 15) == 0, "%s: workspace must be 16-byte aligned", who);
-    const size_t need = syn3r_depth_corr_local_workspace_bytes(H, W, P, oy, ox);
-    if (ws_bytes < need) {
-        set_error("%s: workspace %zu < %zu bytes (syn3r_depth_corr_local_workspace_bytes)", who, ws_bytes, need);
-        return SYN3R_E_WORKSPACE;
-    }
-    return SYN3R_OK;
+    SYN3R_REQUIRE(finite_f32(weight), "%s: weight must be finite", who);
+    SYN3R_REQUIRE(mode == SYN3R_DCORR_A || finite_f32(offset), "%s: offset must be finite", who);
+    return check_workspace(who, ws, ws_bytes, syn3r_depth_corr_local_workspace_bytes(H, W, P, oy, ox),
+                           "syn3r_depth_corr_local_workspace_bytes");
 }
 
 void dl_stats(const float* depth, const float* prior, int W, int P, int oy, int ox, const DlGeom& g, float offset, int mode, void* ws,
@@ -565,8 +553,7 @@ extern "C" int syn3r_depth_corr_local_loss(const float* depth, const float* prio
     DlGeom g;
     const int rc = dl_check("depth_corr_local_loss", depth, prior, H, W, P, oy, ox, weight, offset, mode, ws, ws_bytes, &g);
     if (rc) return rc;
-    SYN3R_REQUIRE(parts, "depth_corr_local_loss: null pointer");
-    SYN3R_REQUIRE(((uintptr_t)parts & 15) == 0, "depth_corr_local_loss: parts must be 16-byte aligned");
+    if (const int rp = check_parts("depth_corr_local_loss", parts)) return rp;
     hipStream_t stream = (hipStream_t)stream_;
     dl_stats(depth, prior, W, P, oy, ox, g, offset, mode, ws, stream);
     SYN3R_LAUNCH(k_dlocal_final, dim3(1), dim3(kDcThreads), 0, stream, (const DlSum*)((const char*)ws + dl_rec_bytes(g)), g.blocks, g.K,
@@ -596,7 +583,7 @@ extern "C" int syn3r_depth_corr_local_loss_step(const float* depth, const float*
     if (rc) return rc;
     SYN3R_REQUIRE(parts && grad_depth, "depth_corr_local_loss_step: null pointer");
     SYN3R_REQUIRE(accumulate == 0 || accumulate == 1, "depth_corr_local_loss_step: accumulate=%d must be 0 or 1", accumulate);
-    SYN3R_REQUIRE(((uintptr_t)parts & 15) == 0, "depth_corr_local_loss_step: parts must be 16-byte aligned");
+    if (const int rp = check_parts("depth_corr_local_loss_step", parts)) return rp;      // after `accumulate`, as ever
     hipStream_t stream = (hipStream_t)stream_;
     dl_stats(depth, prior, W, P, oy, ox, g, offset, mode, ws, stream);
     dl_grad(depth, prior, H, W, P, oy, ox, g, weight, offset, grad_loss, ws, grad_depth, accumulate, parts, stream);

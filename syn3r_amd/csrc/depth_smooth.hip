@@ -247,26 +247,12 @@ int ds_blocks(int H, int W) {
     return (int)b;
 }
 
-// [a, a + a_bytes) and [b, b + b_bytes) share a byte
-bool ds_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 ? b0 - a0 < a_bytes : a0 - b0 < b_bytes;
-}
-
-bool ds_finite(float v) { return v == v && fabsf(v) <= 3.0e38f; }
-
 // argument checks shared by the three loss entries, all before any HIP call (ws: the rows of the statistics pass)
 int ds_check(const char* who, const float* depth, const float* weights, int H, int W, float weight, const void* ws, size_t ws_bytes) {
     SYN3R_REQUIRE(SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W), "%s: H=%d, W=%d must be in [1, 2^15]", who, H, W);
     SYN3R_REQUIRE(depth && weights && ws, "%s: null pointer", who);
-    SYN3R_REQUIRE(ds_finite(weight), "%s: weight must be finite", who);
-    SYN3R_REQUIRE(((uintptr_t)ws & 15) == 0, "%s: workspace must be 16-byte aligned", who);
-    const size_t need = syn3r_depth_smooth_workspace_bytes(H, W);
-    if (ws_bytes < need) {
-        set_error("%s: workspace %zu < %zu bytes (syn3r_depth_smooth_workspace_bytes)", who, ws_bytes, need);
-        return SYN3R_E_WORKSPACE;
-    }
-    return SYN3R_OK;
+    SYN3R_REQUIRE(finite_f32(weight), "%s: weight must be finite", who);
+    return check_workspace(who, ws, ws_bytes, syn3r_depth_smooth_workspace_bytes(H, W), "syn3r_depth_smooth_workspace_bytes");
 }
 
 // the checks of an entry that writes grad_depth
@@ -274,7 +260,7 @@ int ds_check_grad(const char* who, const float* depth, const float* weights, int
     SYN3R_REQUIRE(grad_depth, "%s: null pointer", who);
     SYN3R_REQUIRE(accumulate == 0 || accumulate == 1, "%s: accumulate=%d must be 0 or 1", who, accumulate);
     const size_t bytes = (size_t)H * (size_t)W * sizeof(float);
-    SYN3R_REQUIRE(!ds_overlap(grad_depth, bytes, depth, bytes) && !ds_overlap(grad_depth, bytes, weights, 2 * bytes),
+    SYN3R_REQUIRE(!ranges_overlap(grad_depth, bytes, depth, bytes) && !ranges_overlap(grad_depth, bytes, weights, 2 * bytes),
                   "%s: grad_depth aliases an input", who);
     return SYN3R_OK;
 }
@@ -306,9 +292,9 @@ void ds_grad(const float* depth, const float* weights, int H, int W, float weigh
 extern "C" int syn3r_depth_edge_weights(const float* image, int H, int W, float gamma, float* weights, void* stream_) {
     SYN3R_REQUIRE(SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W), "depth_edge_weights: H=%d, W=%d must be in [1, 2^15]", H, W);
     SYN3R_REQUIRE(image && weights, "depth_edge_weights: null pointer");
-    SYN3R_REQUIRE(ds_finite(gamma) && gamma >= 0.0f, "depth_edge_weights: gamma must be finite and >= 0");
+    SYN3R_REQUIRE(finite_f32(gamma) && gamma >= 0.0f, "depth_edge_weights: gamma must be finite and >= 0");
     const size_t plane = (size_t)H * (size_t)W * sizeof(float);
-    SYN3R_REQUIRE(!ds_overlap(weights, 2 * plane, image, 3 * plane), "depth_edge_weights: weights aliases an input");
+    SYN3R_REQUIRE(!ranges_overlap(weights, 2 * plane, image, 3 * plane), "depth_edge_weights: weights aliases an input");
     const dim3 grid((unsigned)ds_blocks(H, W));
     const int G = ds_groups_per_row(W);
     hipStream_t stream = (hipStream_t)stream_;
@@ -327,10 +313,9 @@ extern "C" size_t syn3r_depth_smooth_workspace_bytes(int H, int W) {
 
 extern "C" int syn3r_depth_smooth_loss(const float* depth, const float* weights, int H, int W, float weight, float* parts, void* ws,
                                        size_t ws_bytes, void* stream_) {
-    const int rc = ds_check("depth_smooth_loss", depth, weights, H, W, weight, ws, ws_bytes);
+    int rc = ds_check("depth_smooth_loss", depth, weights, H, W, weight, ws, ws_bytes);
     if (rc) return rc;
-    SYN3R_REQUIRE(parts, "depth_smooth_loss: null pointer");
-    SYN3R_REQUIRE(((uintptr_t)parts & 15) == 0, "depth_smooth_loss: parts must be 16-byte aligned");
+    if ((rc = check_parts("depth_smooth_loss", parts))) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     ds_stats(depth, weights, H, W, ws, stream);
     SYN3R_LAUNCH(k_dsmooth_final, dim3(1), dim3(kDsThreads), 0, stream, (const float4*)ws, ds_blocks(H, W), H, W, weight, parts);
@@ -354,8 +339,7 @@ extern "C" int syn3r_depth_smooth_loss_step(const float* depth, const float* wei
                                             float* parts, float* grad_depth, int accumulate, void* ws, size_t ws_bytes, void* stream_) {
     int rc = ds_check("depth_smooth_loss_step", depth, weights, H, W, weight, ws, ws_bytes);
     if (rc) return rc;
-    SYN3R_REQUIRE(parts, "depth_smooth_loss_step: null pointer");
-    SYN3R_REQUIRE(((uintptr_t)parts & 15) == 0, "depth_smooth_loss_step: parts must be 16-byte aligned");
+    if ((rc = check_parts("depth_smooth_loss_step", parts))) return rc;
     rc = ds_check_grad("depth_smooth_loss_step", depth, weights, H, W, grad_depth, accumulate);
     if (rc) return rc;
     hipStream_t stream = (hipStream_t)stream_;

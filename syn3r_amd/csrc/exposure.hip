@@ -168,12 +168,6 @@ int exp_blocks(long long n) {
     return (int)b;
 }
 
-// [a, a + a_bytes) and [b, b + b_bytes) share a byte
-bool exp_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 ? b0 - a0 < a_bytes : a0 - b0 < b_bytes;
-}
-
 bool exp_aligned16(const void* a, const void* b, const void* c) { return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0; }
 
 }  // namespace
@@ -184,7 +178,7 @@ extern "C" int syn3r_exposure_apply(const float* image, const float* A, int H, i
     SYN3R_REQUIRE((((uintptr_t)image | (uintptr_t)A | (uintptr_t)out) & 3) == 0, "exposure_apply: pointers must be 4-byte aligned");
     const long long n = (long long)H * W;
     const size_t bytes = (size_t)n * 3 * sizeof(float), a_bytes = kExpRow * sizeof(float);
-    SYN3R_REQUIRE(!exp_overlap(out, bytes, image, bytes) && !exp_overlap(out, bytes, A, a_bytes), "exposure_apply: out aliases an input");
+    SYN3R_REQUIRE(!ranges_overlap(out, bytes, image, bytes) && !ranges_overlap(out, bytes, A, a_bytes), "exposure_apply: out aliases an input");
     hipStream_t stream = (hipStream_t)stream_;
     const dim3 grid((unsigned)exp_blocks(n));
     if (n % 4 == 0 && exp_aligned16(image, out, nullptr))
@@ -206,16 +200,12 @@ extern "C" int syn3r_exposure_backward(const float* image, const float* A, const
     SYN3R_REQUIRE(image && A && grad_out && grad_image && grad_A && ws, "exposure_backward: null pointer");
     SYN3R_REQUIRE((((uintptr_t)image | (uintptr_t)A | (uintptr_t)grad_out | (uintptr_t)grad_image | (uintptr_t)grad_A) & 3) == 0,
                   "exposure_backward: pointers must be 4-byte aligned");
-    SYN3R_REQUIRE(((uintptr_t)ws & 15) == 0, "exposure_backward: workspace must be 16-byte aligned");
-    if (ws_bytes < syn3r_exposure_backward_workspace_bytes(H, W)) {
-        set_error("exposure_backward: workspace %zu < %zu bytes (syn3r_exposure_backward_workspace_bytes)", ws_bytes,
-                  syn3r_exposure_backward_workspace_bytes(H, W));
-        return SYN3R_E_WORKSPACE;
-    }
+    if (const int rc = check_workspace("exposure_backward", ws, ws_bytes, syn3r_exposure_backward_workspace_bytes(H, W),
+                                       "syn3r_exposure_backward_workspace_bytes")) return rc;
     const long long n = (long long)H * W;
     const size_t bytes = (size_t)n * 3 * sizeof(float), a_bytes = kExpRow * sizeof(float);
-    SYN3R_REQUIRE(!exp_overlap(grad_image, bytes, image, bytes) && !exp_overlap(grad_image, bytes, grad_out, bytes) &&
-                  !exp_overlap(grad_image, bytes, A, a_bytes), "exposure_backward: grad_image aliases an input");
+    SYN3R_REQUIRE(!ranges_overlap(grad_image, bytes, image, bytes) && !ranges_overlap(grad_image, bytes, grad_out, bytes) &&
+                  !ranges_overlap(grad_image, bytes, A, a_bytes), "exposure_backward: grad_image aliases an input");
     hipStream_t stream = (hipStream_t)stream_;
     const int nb = exp_blocks(n);
     float* rows = (float*)ws;

@@ -55,12 +55,6 @@ int blocks_for(long long items) {
     return (int)b;
 }
 
-// [a, a + a_bytes) and [b, b + b_bytes) share a byte
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 ? b0 - a0 < a_bytes : a0 - b0 < b_bytes;
-}
-
 size_t round256(size_t b) { return ((b + 255) / 256) * 256; }
 
 // ------------------------------------------------------------------------------------------------------------------ noise
@@ -331,8 +325,8 @@ extern "C" int syn3r_mcmc_noise(float* xyz, const float* log_scales, const float
                   "mcmc_noise: pointers must be 4-byte aligned, rotations 16-byte aligned");
     SYN3R_REQUIRE(scale == scale, "mcmc_noise: scale is NaN");
     const size_t b3 = (size_t)n * 3 * sizeof(float);
-    SYN3R_REQUIRE(!overlap(xyz, b3, log_scales, b3) && !overlap(xyz, b3, rotations, (size_t)n * 16) &&
-                  !overlap(xyz, b3, opacity_logits, (size_t)n * 4), "mcmc_noise: xyz aliases an input");
+    SYN3R_REQUIRE(!ranges_overlap(xyz, b3, log_scales, b3) && !ranges_overlap(xyz, b3, rotations, (size_t)n * 16) &&
+                  !ranges_overlap(xyz, b3, opacity_logits, (size_t)n * 4), "mcmc_noise: xyz aliases an input");
     SYN3R_LAUNCH(k_mcmc_noise, dim3((unsigned)blocks_for(n)), dim3(kThreads), 0, (hipStream_t)stream_, xyz, log_scales,
                  (const float4*)rotations, opacity_logits, n, (double)scale, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32),
                  (unsigned)step);
@@ -351,17 +345,13 @@ extern "C" int syn3r_mcmc_reg_step(const float* opacity_logits, const float* log
     SYN3R_REQUIRE(opacity_logits && log_scales && grad_opacity && grad_log_scales && loss_out && ws, "mcmc_reg_step: null pointer");
     SYN3R_REQUIRE((((uintptr_t)opacity_logits | (uintptr_t)log_scales | (uintptr_t)grad_opacity | (uintptr_t)grad_log_scales |
                     (uintptr_t)loss_out) & 3) == 0, "mcmc_reg_step: pointers must be 4-byte aligned");
-    SYN3R_REQUIRE(((uintptr_t)ws & 15) == 0, "mcmc_reg_step: workspace must be 16-byte aligned");
-    if (ws_bytes < syn3r_mcmc_reg_step_workspace_bytes(n)) {
-        set_error("mcmc_reg_step: workspace %zu < %zu bytes (syn3r_mcmc_reg_step_workspace_bytes)", ws_bytes,
-                  syn3r_mcmc_reg_step_workspace_bytes(n));
-        return SYN3R_E_WORKSPACE;
-    }
+    if (const int rc = check_workspace("mcmc_reg_step", ws, ws_bytes, syn3r_mcmc_reg_step_workspace_bytes(n),
+                                       "syn3r_mcmc_reg_step_workspace_bytes")) return rc;
     const size_t b1 = (size_t)n * sizeof(float), b3 = 3 * b1;
-    SYN3R_REQUIRE(!overlap(grad_opacity, b1, opacity_logits, b1) && !overlap(grad_opacity, b1, log_scales, b3) &&
-                  !overlap(grad_log_scales, b3, opacity_logits, b1) && !overlap(grad_log_scales, b3, log_scales, b3) &&
-                  !overlap(grad_opacity, b1, grad_log_scales, b3) && !overlap(loss_out, 8, grad_opacity, b1) &&
-                  !overlap(loss_out, 8, grad_log_scales, b3), "mcmc_reg_step: an output aliases an input or another output");
+    SYN3R_REQUIRE(!ranges_overlap(grad_opacity, b1, opacity_logits, b1) && !ranges_overlap(grad_opacity, b1, log_scales, b3) &&
+                  !ranges_overlap(grad_log_scales, b3, opacity_logits, b1) && !ranges_overlap(grad_log_scales, b3, log_scales, b3) &&
+                  !ranges_overlap(grad_opacity, b1, grad_log_scales, b3) && !ranges_overlap(loss_out, 8, grad_opacity, b1) &&
+                  !ranges_overlap(loss_out, 8, grad_log_scales, b3), "mcmc_reg_step: an output aliases an input or another output");
     hipStream_t stream = (hipStream_t)stream_;
     const int nb = blocks_for(n);
     const double wo = (double)opacity_reg / (double)n, wsc = (double)scale_reg / (3.0 * (double)n);
@@ -377,7 +367,7 @@ extern "C" int syn3r_mcmc_weights(const float* opacity_logits, int n, float dead
     SYN3R_REQUIRE(opacity_logits && weights, "mcmc_weights: null pointer");
     SYN3R_REQUIRE((((uintptr_t)opacity_logits | (uintptr_t)weights) & 3) == 0, "mcmc_weights: pointers must be 4-byte aligned");
     SYN3R_REQUIRE(dead_logit == dead_logit, "mcmc_weights: dead_logit is NaN");
-    SYN3R_REQUIRE(!overlap(weights, (size_t)n * 4, opacity_logits, (size_t)n * 4), "mcmc_weights: weights aliases the logits");
+    SYN3R_REQUIRE(!ranges_overlap(weights, (size_t)n * 4, opacity_logits, (size_t)n * 4), "mcmc_weights: weights aliases the logits");
     SYN3R_LAUNCH(k_mcmc_weights, dim3((unsigned)blocks_for(n)), dim3(kThreads), 0, (hipStream_t)stream_, opacity_logits, n, dead_logit,
                  weights);
     SYN3R_LAUNCH_CHECK("mcmc_weights launch");
@@ -397,14 +387,10 @@ extern "C" int syn3r_mcmc_sample(const unsigned* weights, int n, int m_extra, un
     SYN3R_REQUIRE(m_extra >= 0 && m_extra <= SYN3R_DIM_MAX, "mcmc_sample: m_extra=%d must be in [0, 2^24]", m_extra);
     SYN3R_REQUIRE(weights && src && counts && ws, "mcmc_sample: null pointer");
     SYN3R_REQUIRE((((uintptr_t)weights | (uintptr_t)src | (uintptr_t)counts) & 3) == 0, "mcmc_sample: pointers must be 4-byte aligned");
-    SYN3R_REQUIRE(((uintptr_t)ws & 15) == 0, "mcmc_sample: workspace must be 16-byte aligned");
-    if (ws_bytes < syn3r_mcmc_sample_workspace_bytes(n)) {
-        set_error("mcmc_sample: workspace %zu < %zu bytes (syn3r_mcmc_sample_workspace_bytes)", ws_bytes,
-                  syn3r_mcmc_sample_workspace_bytes(n));
-        return SYN3R_E_WORKSPACE;
-    }
+    if (const int rc = check_workspace("mcmc_sample", ws, ws_bytes, syn3r_mcmc_sample_workspace_bytes(n),
+                                       "syn3r_mcmc_sample_workspace_bytes")) return rc;
     const size_t bn = (size_t)n * 4, bs = ((size_t)n + (size_t)m_extra) * 4;
-    SYN3R_REQUIRE(!overlap(src, bs, weights, bn) && !overlap(counts, bn, weights, bn) && !overlap(src, bs, counts, bn),
+    SYN3R_REQUIRE(!ranges_overlap(src, bs, weights, bn) && !ranges_overlap(counts, bn, weights, bn) && !ranges_overlap(src, bs, counts, bn),
                   "mcmc_sample: src / counts alias each other or the weights");
     hipStream_t stream = (hipStream_t)stream_;
     const int nchunks = (n + kChunk - 1) / kChunk;
@@ -437,7 +423,7 @@ extern "C" int syn3r_mcmc_relocate(int n, const int* src, const unsigned* counts
     const size_t len[7] = {b1, b1, 3 * b1, (size_t)feature_row_len * b1, b1, 3 * b1, 4 * b1};
     for (int a = 0; a < 7; ++a)
         for (int b = a + 1; b < 7; ++b)
-            SYN3R_REQUIRE(!overlap(arr[a], len[a], arr[b], len[b]), "mcmc_relocate: two arrays alias each other");
+            SYN3R_REQUIRE(!ranges_overlap(arr[a], len[a], arr[b], len[b]), "mcmc_relocate: two arrays alias each other");
     hipStream_t stream = (hipStream_t)stream_;
     const dim3 grid((unsigned)blocks_for(n));
     SYN3R_LAUNCH(k_mcmc_relocate_dst, grid, dim3(kThreads), 0, stream, n, src, counts, xyz, features, feature_row_len, opacity_logits,

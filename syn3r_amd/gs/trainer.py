@@ -4,7 +4,7 @@
 The reference delegates all of this to `FSGS.utils.trainer_v4.GSTrainer` (un-vendored submodule): only the
 call surface is visible.  This module provides that surface with the published 3DGS training step
 (render -> (1-lambda) L1 + lambda (1-SSIM) photometric loss weighted by the camera confidence -> backward ->
-Adam; the loss and the Adam update are the fused HIP operators of `train_ops.py`), no densification
+Adam; the loss and the Adam update are the fused HIP operators of `train_ops`), no densification
 heuristics (out of scope).
 
 `GSTrainer` holds construction, the optimiser and its learning rate, camera registration, checkpoints, the two step routes and
@@ -459,7 +459,7 @@ class GSTrainer:
         return loss, out
 
     def _autograd_step(self, cam: Camera, lpips_on: bool = False) -> Tuple[torch.Tensor, dict]:
-        """One optimisation step THROUGH autograd (`render_view`, the autograd operators of `train_ops.py`, `loss.backward()`): the
+        """One optimisation step THROUGH autograd (`render_view`, the autograd operators of `train_ops`, `loss.backward()`): the
         route of the LPIPS term (`lpips_on`) and of a trainable confidence.  `out` is `render_view`'s dictionary: its boolean
         `visibility_filter` and the gradient on `viewspace_points` are what the density control reads on this route."""
         pose_row = self.pose.row(cam)

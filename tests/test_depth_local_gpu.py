@@ -14,6 +14,7 @@ import torch
 
 from oracle import raster_oracle as RO
 from tests import depth_local_ref as R
+from tests.depth_terms import prior as _prior, same as _same, scene as _scene, spy_rasterize_backward, step_bits as _step_bits
 from tests.poison import PATTERNS, poisoned
 from tests.test_depth_loss_gpu import make_case as global_case
 
@@ -307,16 +308,6 @@ def test_op_rejects_bad_arguments(gpu):
 
 
 # ---------------------------------------------------------------- the trainer with the term on
-def _scene(N, H, W, seed, dev):
-    from tests.test_trainer_gpu import make_scene
-    return make_scene(N, H, W, seed, dev)
-
-
-def _prior(H, W, K, dev, seed=21):
-    from tests.test_depth_loss_gpu import _prior as prior_of_another_cloud
-    return prior_of_another_cloud(H, W, K, dev, seed)
-
-
 @pytest.mark.parametrize("weights", [(0.0, 0.05), (0.05, 0.05)], ids=["local", "both"])
 def test_explicit_step_equals_autograd_step(weights, gpu):
     from syn3r_amd.gs import Camera, GSTrainer, OptimizationParams
@@ -390,16 +381,8 @@ def test_one_step_with_local_term_matches_oracle(gpu, measurements):
 def test_weight_zero_leaves_the_step_unchanged(gpu, monkeypatch):
     """depth_local_weight = 0, with and without a prior on the camera: the explicit step's loss and the gradients it hands the
     rasteriser are bitwise those of a trainer without the option; depth_net runs once per camera, and only with a term on."""
-    from syn3r_amd import raster
     from syn3r_amd.gs import Camera, GSTrainer, OptimizationParams
-    from tests.test_depth_loss_gpu import _same, _step_bits
-    seen = []
-    real_bwd = raster.rasterize_backward
-
-    def spy(st, g_color, g_depth=None, g_alpha=None, **kw):
-        seen.append((g_color.clone(), None if g_depth is None else g_depth.clone()))
-        return real_bwd(st, g_color, g_depth, g_alpha, **kw)
-    monkeypatch.setattr(raster, "rasterize_backward", spy)
+    seen = spy_rasterize_backward(monkeypatch)
     N, H, W = 2000, 48, 64
     target = torch.rand(3, H, W, generator=torch.Generator().manual_seed(2))
     _, K = _scene(N, H, W, 4, gpu)

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle import raster_oracle as RO
+from tests.depth_terms import prior as _prior, same as _same, scene as _scene, spy_rasterize_backward, step_bits as _step_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -166,20 +167,6 @@ def test_op_rejects_bad_shapes(gpu):
 
 
 # ---------------------------------------------------------------- the trainer with the term on
-def _scene(N, H, W, seed, dev):
-    from tests.test_trainer_gpu import make_scene
-    return make_scene(N, H, W, seed, dev)
-
-
-def _prior(H, W, K, dev, seed=21):
-    """A disparity prior from ANOTHER cloud: correlated with nothing in particular, so the term has work to do."""
-    from syn3r_amd.gs import Camera, GSTrainer
-    from syn3r_amd.launch import truth_disparity
-    gm, _ = _scene(2000, H, W, seed, dev)
-    cam = Camera.from_w2c(np.eye(4, dtype=np.float32), K, H, W, data_device=dev)
-    return truth_disparity(GSTrainer(gm, [cam]), cam)
-
-
 def test_explicit_step_equals_autograd_step_with_depth_term(gpu):
     from syn3r_amd.gs import Camera, GSTrainer, OptimizationParams
     N, H, W = 3000, 72, 104
@@ -262,37 +249,12 @@ def test_one_step_with_depth_term_matches_oracle(gpu, measurements):
         assert (d > 1e-6).double().mean() < 2e-2
 
 
-def _step_bits(tr, cam, seen):
-    """The explicit step's loss and the loss gradients it hands the rasteriser's backward (bitwise: both come from fixed-order
-    kernels), and the parameter gradients (the rasteriser's backward accumulates with float atomics: equal to rounding)."""
-    seen.clear()
-    loss, out = tr._explicit_step(cam)
-    (g_color, g_depth), = seen
-    return [loss.clone(), g_color, g_depth], [p.grad.detach().clone() for p in tr.gaussians.parameters()] + [out["viewspace_grad"].clone()]
-
-
-def _same(a, b):
-    bits_a, grads_a = a
-    bits_b, grads_b = b
-    assert torch.equal(bits_a[0], bits_b[0]) and torch.equal(bits_a[1], bits_b[1])
-    assert (bits_a[2] is None) == (bits_b[2] is None) and (bits_a[2] is None or torch.equal(bits_a[2], bits_b[2]))
-    for x, y in zip(grads_a, grads_b):
-        assert float((x - y).abs().max()) <= 2e-5 * (float(y.abs().max()) + 1e-20)
-
-
 def test_default_leaves_the_step_unchanged(gpu, monkeypatch):
     """depth_weight = 0 (with a prior on the camera), or a camera without a prior and no depth_net: the explicit step's loss and
     the gradients it forms are bitwise those of a trainer built without any of it, and the rasteriser gets no depth gradient.
     depth_net runs once per camera, and only with the term on."""
-    from syn3r_amd import raster
     from syn3r_amd.gs import Camera, GSTrainer, OptimizationParams
-    seen = []
-    real_bwd = raster.rasterize_backward
-
-    def spy(st, g_color, g_depth=None, g_alpha=None, **kw):
-        seen.append((g_color.clone(), None if g_depth is None else g_depth.clone()))
-        return real_bwd(st, g_color, g_depth, g_alpha, **kw)
-    monkeypatch.setattr(raster, "rasterize_backward", spy)
+    seen = spy_rasterize_backward(monkeypatch)
     N, H, W = 2000, 48, 64
     target = torch.rand(3, H, W, generator=torch.Generator().manual_seed(2))
     _, K = _scene(N, H, W, 4, gpu)

@@ -28,6 +28,7 @@ import pytest
 import torch
 
 from tests import depth_smooth_ref as R
+from tests.depth_terms import prior as _prior, same as _same, scene as _scene, spy_rasterize_backward, step_bits as _step_bits
 from tests.poison import PATTERNS, poisoned
 
 pytestmark = pytest.mark.gpu
@@ -395,16 +396,6 @@ def test_op_rejects_bad_arguments(gpu):
 N_T, H_T, W_T = 2000, 48, 64
 
 
-def _scene(N, H, W, seed, dev):
-    from tests.test_trainer_gpu import make_scene
-    return make_scene(N, H, W, seed, dev)
-
-
-def _prior(H, W, K, dev, seed=21):
-    from tests.test_depth_loss_gpu import _prior as prior_of_another_cloud
-    return prior_of_another_cloud(H, W, K, dev, seed)
-
-
 @pytest.mark.parametrize("weights", [(0.0, 0.0, 0.05), (0.05, 0.05, 0.05)], ids=["smooth", "all_three"])
 def test_explicit_step_equals_autograd_step(weights, gpu):
     from syn3r_amd.gs import Camera, GSTrainer, OptimizationParams
@@ -434,21 +425,14 @@ def test_weight_zero_leaves_the_step_unchanged(gpu, monkeypatch):
     """depth_smooth_weight = 0: the explicit step's loss and the gradients it hands the rasteriser are bitwise those of a trainer
     without the option, no weights are computed or cached and depth_net is never called - nor is it with the term ON.  All three
     depth terms on: one depth-gradient buffer, the sum of the three separate ones.  depth_smooth_cameras selects its cameras."""
-    from syn3r_amd import raster
     from syn3r_amd.gs import Camera, GSTrainer, OptimizationParams
     from syn3r_amd.gs import trainer as trainer_module
-    from tests.test_depth_loss_gpu import _same, _step_bits
-    seen, computed = [], []
-    real_bwd, real_weights = raster.rasterize_backward, trainer_module.edge_weights_of_image
-
-    def spy(st, g_color, g_depth=None, g_alpha=None, **kw):
-        seen.append((g_color.clone(), None if g_depth is None else g_depth.clone()))
-        return real_bwd(st, g_color, g_depth, g_alpha, **kw)
+    seen, computed = spy_rasterize_backward(monkeypatch), []
+    real_weights = trainer_module.edge_weights_of_image
 
     def weights_spy(image, gamma):
         computed.append(float(gamma))
         return real_weights(image, gamma)
-    monkeypatch.setattr(raster, "rasterize_backward", spy)
     monkeypatch.setattr(trainer_module, "edge_weights_of_image", weights_spy)
     N, H, W = N_T, H_T, W_T
     target = torch.rand(3, H, W, generator=torch.Generator().manual_seed(2))

@@ -1,4 +1,4 @@
-"""Per-camera affine exposure compensation on the GPU: the kernels of csrc/exposure.hip through the operators of `train_ops.py` against
+"""Per-camera affine exposure compensation on the GPU: the kernels of csrc/exposure.hip through the operators of `train_ops` against
 the float64 restatement tests/exposure_ref.py, and the trainer's `OptimizationParams.exposure_opt` on the synthetic scene of
 tests/trainer_launches.py.
 

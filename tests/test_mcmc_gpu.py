@@ -1,4 +1,4 @@
-"""3DGS-MCMC density control on the GPU: the kernels of csrc/mcmc.hip through the operators of `train_ops.py` against the float64 /
+"""3DGS-MCMC density control on the GPU: the kernels of csrc/mcmc.hip through the operators of `train_ops` against the float64 /
 Python-integer restatement tests/mcmc_ref.py, and the trainer's `OptimizationParams.mcmc` on the synthetic scene of
 tests/trainer_launches.py.  Every operator that allocates runs under tests/poison.py.
 
