@@ -925,6 +925,58 @@ int syn3r_depth_smooth_loss_backward(const float* depth, const float* weights, i
 int syn3r_depth_smooth_loss_step(const float* depth, const float* weights, int H, int W, float weight, const float* grad_loss,
                                  float* parts, float* grad_depth, int accumulate, void* ws, size_t ws_bytes, void* stream);
 
+/* Multi-view photometric reprojection term (EXTENSION: the reference has none; Monodepth2's per-pixel minimum reprojection error,
+ * Godard et al., ICCV 2019, without its SSIM part and auto-mask, as unsupervised-MVS and MVS-guided sparse-view 3DGS pipelines use
+ * it).  Not to be confused with syn3r_reproj_error above, which serves the diffusion conditioning and is not differentiable.
+ * depth D and alpha a [H,W] fp32 are a render of the target view, target I_t [3,H,W] fp32 its photograph, sources[s] (HOST array of
+ * S DEVICE pointers) the photographs I_s [3,H,W] of S posed input views of the same H, W, 1 <= S <= 4.  views (HOST, S x 16 floats):
+ * per source M_s (3 x 3, row-major), t_s, fx_s, fy_s, cx_s, cy_s with [M_s | t_s] = w2c_s c2w_t; target_k (HOST, 4 floats):
+ * fx_t, fy_t, cx_t, cy_t.  The tables travel to the kernel by value, as syn3r_adam_step_multi's do: no per-step copy or stacking
+ * of images.  Pixel convention of the rasteriser: pixel index x sits at fx X/Z + (W-1)/2, so cx = (W-1)/2, fx = W / (2 tan(FoVx/2)).
+ * Per pixel p = (x, y):
+ *   z = D / a                                                    dead when !(a >= alpha_min) or !(D > 0)
+ *   r = ((x - cx_t) / fx_t, (y - cy_t) / fy_t, 1)       A = M_s r       X = z A + t_s
+ *   q = (fx_s X_x / X_z + cx_s, fy_s X_y / X_z + cy_s)           source s valid: X_z >= 0.01, 0 <= q_x <= W-1, 0 <= q_y <= H-1
+ *   e_s = (1/3) sum_c |I_s,c(q) - I_t,c(p)|     bilinear on the cell x0 = min(floor(q_x), W-2), y0 = min(floor(q_y), H-2)
+ *   e = min over the valid s of e_s (the lowest s on a tie); a pixel with no valid source is dead
+ *   loss = weight * sum_live e / max(N_live, 1)                  (N_live is a constant of the gradient)
+ *   dL/dz = weight * grad_loss[0] / N_live * (1/3) sum_c sgn(I_s,c(q) - I_t,c(p)) (dI_s,c/dq_x dq_x/dz + dI_s,c/dq_y dq_y/dz)
+ *   dq_x/dz = fx_s (A_x t_z - A_z t_x) / X_z^2       dq_y/dz = fy_s (A_y t_z - A_z t_y) / X_z^2       sgn(0) = 0
+ *   grad_depth = dL/dz / a        grad_alpha = -dL/dz z / a      dead pixels: 0 in both; N_live = 0: loss 0, zero gradients
+ * through the chosen source only, dI/dq the bilinear cell's own derivative (grad_loss: device scalar, NULL = 1).  The minimum and
+ * the L1 form are recalled from Monodepth2 (not available); no SSIM, no auto-mask and alpha_min are this library's choices: UNPINNED.
+ * The statistics pass does the geometry, the gathers and the minimum in fp32 and leaves in ws one row per block (sum e, N_live,
+ * N on source 0, sum e on source 0: per-thread running sums, added over the wave and the block's waves in a fixed order) and 8
+ * bytes per pixel: the unscaled dL/dz, and a record word = the fp32 bits of e with the two lowest mantissa bits replaced by the
+ * chosen source (0xffffffff: dead).  The gradient pass is elementwise: it adds the rows in fp64 in a fixed order, scales, and
+ * writes (accumulate 0: every pixel, the buffer may hold anything) or ADDS (accumulate 1) each of the two gradients; it repeats no
+ * gather.  No float atomics, no host read; the grid is a function of H and W alone: bitwise repeatable for a given shape.  Rows go
+ * through 16-byte accesses when every plane pointer is 16-byte aligned and W % 4 == 0, anything else through scalar ones, with the
+ * same bits.  parts (device, 16-byte aligned, 4 floats): [loss, mean e over live pixels, N_live / (H W), share of live pixels on
+ * source 0].
+ * ws: syn3r_photo_reproj_workspace_bytes(H, W, S) bytes (0 for a rejected shape), 16-byte aligned: 16 KiB of rows, then the dL/dz
+ * plane [H,W] fp32, then the record plane [H,W] uint32.  syn3r_photo_reproj_loss_backward takes the SAME workspace.
+ * Rejections before any HIP call (SYN3R_E_INVALID): H or W outside [2, 2^15], S outside [1, 4], null pointers, a non-finite weight,
+ * view or intrinsic, a zero target focal length, alpha_min not finite or <= 0, an accumulate flag not 0 or 1, a misaligned parts or
+ * workspace, a gradient overlapping depth, alpha, the other gradient or the workspace (the step entry: the target or a source image as well; the
+ * backward entry does not see the images), the workspace overlapping an input; a short
+ * workspace is SYN3R_E_WORKSPACE. */
+size_t syn3r_photo_reproj_workspace_bytes(int H, int W, int S);
+/* value only: two launches (statistics, one-block combine) */
+int syn3r_photo_reproj_loss(const float* depth, const float* alpha, const float* target, const float* const* sources,
+                            const float* views, const float* target_k, int H, int W, int S, float weight, float alpha_min,
+                            float* parts, void* ws, size_t ws_bytes, void* stream);
+/* the gradient launch on what syn3r_photo_reproj_loss left in ws */
+int syn3r_photo_reproj_loss_backward(const float* depth, const float* alpha, int H, int W, int S, float weight, float alpha_min,
+                                     const float* grad_loss, const void* ws, size_t ws_bytes, float* grad_depth, int accumulate_depth,
+                                     float* grad_alpha, int accumulate_alpha, void* stream);
+/* Value AND both gradients in two launches: the statistics, then the gradient, whose block 0 also writes parts.  Same bits as
+ * syn3r_photo_reproj_loss + syn3r_photo_reproj_loss_backward. */
+int syn3r_photo_reproj_loss_step(const float* depth, const float* alpha, const float* target, const float* const* sources,
+                                 const float* views, const float* target_k, int H, int W, int S, float weight, float alpha_min,
+                                 const float* grad_loss, float* parts, float* grad_depth, int accumulate_depth, float* grad_alpha,
+                                 int accumulate_alpha, void* ws, size_t ws_bytes, void* stream);
+
 /* Per-camera affine exposure compensation (EXTENSION: the reference has none; the published 3DGS code base has since grown a
  * per-image exposure model, gsplat an appearance optimisation).  A is 3 x 4 fp32, row-major, 12 floats in DEVICE memory; image,
  * out, grad_out and grad_image are [3,H,W] fp32 planes:

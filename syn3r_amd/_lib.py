@@ -148,6 +148,11 @@ SIGNATURES = {
     "syn3r_depth_smooth_loss": (c_i, [c_p, c_p, c_i, c_i, c_f, c_p, c_p, c_sz, c_p]),
     "syn3r_depth_smooth_loss_backward": (c_i, [c_p, c_p, c_i, c_i, c_f, c_p, c_p, c_sz, c_p, c_i, c_p]),
     "syn3r_depth_smooth_loss_step": (c_i, [c_p, c_p, c_i, c_i, c_f, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
+    "syn3r_photo_reproj_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
+    "syn3r_photo_reproj_loss": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_sz, c_p]),
+    "syn3r_photo_reproj_loss_backward": (c_i, [c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_sz, c_p, c_i, c_p, c_i, c_p]),
+    "syn3r_photo_reproj_loss_step": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_sz,
+                                           c_p]),
     "syn3r_exposure_backward_workspace_bytes": (c_sz, [c_i, c_i]),
     "syn3r_exposure_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_p, c_sz, c_p]),
     "syn3r_mcmc_noise": (c_i, [c_p, c_p, c_p, c_p, c_i, c_f, c_ll, c_i, c_p]),

@@ -30,7 +30,8 @@ COMMON_FLAGS = [
     "-fno-gpu-rdc",
 ]
 # files whose arithmetic mirrors torch/numpy elementwise op order: no fma contraction
-STRICT_FP = {"warp.hip", "sched.hip", "train.hip", "photo_loss.hip", "knn.hip", "exposure.hip", "mcmc.hip", "depth_smooth.hip"}
+STRICT_FP = {"warp.hip", "sched.hip", "train.hip", "photo_loss.hip", "knn.hip", "exposure.hip", "mcmc.hip", "depth_smooth.hip",
+             "reproj.hip"}
 
 
 def _hipcc() -> str:

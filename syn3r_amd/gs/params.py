@@ -43,6 +43,27 @@ class OptimizationParams:
     depth_smooth_weight: float = 0.0
     depth_smooth_gamma: float = 1.0             # recalled, UNPINNED
     depth_smooth_cameras: str = "all"
+    # Multi-view photometric reprojection (EXTENSION: the reference has none; Monodepth2's per-pixel minimum reprojection error, which
+    # unsupervised-MVS and MVS-guided sparse-view 3DGS pipelines use as well): the depth rendered for a target view, taken along the
+    # ray as z = depth / alpha, carries each pixel into up to `reproj_sources` other INPUT views, and `reproj_weight` x the mean over
+    # the live pixels of the smallest L1 colour difference found there is added to the loss (`train_ops.photo_reprojection_loss`,
+    # csrc/reproj.hip: two more launches), with gradients for the rendered depth AND alpha - the first term that hands the rasteriser
+    # a `g_alpha`.  It needs no depth prior; its evidence is the other photographs.  `reproj_cameras`: which TARGET cameras carry the
+    # term - "train" (the input views), "pseudo" or "all"; sources are always input views (`getTrainCameras()`) of the target's H, W
+    # whose viewing direction is within `reproj_max_angle` degrees of the target's, the nearest by camera-centre distance first (ties
+    # in list order); a target without one skips the term (`gs/reproj.py`).  A pixel is dead below `reproj_alpha_min`.  The term
+    # starts at iteration `reproj_from_iter`.  Weighted by `reproj_weight` alone, not by the camera confidence or its map, and it
+    # compares the RAW images: the exposure transform does not touch it.  The minimum over sources and the L1 form are RECALLED from
+    # Monodepth2, which is not available to check against; no SSIM part, no auto-mask (cameras are posed, the scene is static),
+    # alpha_min = 0.5 and the source rule are this project's choices: UNPINNED.  Out of scope: a gradient through the relative views (how q depends on
+    # the poses), exposure compensation between input views, an occlusion test against a second render.  Weight 0 = off: every render,
+    # gradient, launch, checkpoint file and decision is what it was.  Nothing of it goes into checkpoints.
+    reproj_weight: float = 0.0
+    reproj_sources: int = 2                     # 1 .. 4; chosen, UNPINNED
+    reproj_cameras: str = "train"
+    reproj_alpha_min: float = 0.5               # chosen, UNPINNED
+    reproj_max_angle: float = 45.0              # degrees; chosen, UNPINNED
+    reproj_from_iter: int = 0
     # adaptive density control, published 3DGS defaults (Kerbl et al. 2023 section 5.2 and its released arguments); used when
     # training()/finetune() run with disable_densification=False
     percent_dense: float = 0.01

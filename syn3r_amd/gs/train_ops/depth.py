@@ -123,11 +123,11 @@ class _DepthTerm(torch.autograd.Function):
         return (None, None, grad.reshape(shape), None) + (None,) * n_user
 
 
-def _check_grad_out(who: str, d: torch.Tensor, grad_out: torch.Tensor) -> None:
-    """A step function's `grad_out`: float32, contiguous, depth's number of elements, on its device."""
+def _check_grad_out(who: str, d: torch.Tensor, grad_out: torch.Tensor, name: str = "grad_out") -> None:
+    """A step function's `grad_out` (or the buffer `name`): float32, contiguous, depth's number of elements, on its device."""
     L.require_gpu(d, grad_out)
     if grad_out.dtype != torch.float32 or grad_out.numel() != d.numel() or not grad_out.is_contiguous():
-        raise ValueError(f"{who}: grad_out must be a contiguous float32 tensor of depth's {d.numel()} elements")
+        raise ValueError(f"{who}: {name} must be a contiguous float32 tensor of depth's {d.numel()} elements")
 
 
 def depth_correlation_loss(depth: torch.Tensor, prior: torch.Tensor, weight: float = 1.0, offset: float = 200.0, mode: str = "min",

@@ -41,6 +41,8 @@ from .train_ops import depth_correlation_loss_step, exposure_apply, exposure_app
 from .train_ops import depth_edge_weights as edge_weights_of_image
 from .train_ops import depth_smoothness_loss, depth_smoothness_loss_step
 from .train_ops import mcmc_noise, mcmc_reg_step
+from .train_ops import photo_reprojection_loss, photo_reprojection_loss_step
+from . import reproj as reproj_host
 
 
 DEPTH_SMOOTH_CAMERA_KINDS = ("all", "train", "pseudo")
@@ -68,6 +70,7 @@ class GSTrainer:
         if self.opt.depth_smooth_cameras not in DEPTH_SMOOTH_CAMERA_KINDS:
             raise ValueError("OptimizationParams.depth_smooth_cameras must be 'all', 'train' or 'pseudo', got "
                              f"{self.opt.depth_smooth_cameras!r}")
+        reproj_host.check_options(self.opt)
         if self.opt.mcmc:
             if self.opt.use_proximity_densify or self.opt.densify_abs_grad:
                 raise ValueError("OptimizationParams.mcmc replaces the clone / split / prune control: use_proximity_densify and "
@@ -80,6 +83,7 @@ class GSTrainer:
         self.filter3d = Filter3DCache()               # `opt.filter_3d`: the camera table and the age of `gaussians.filter_3D`
         self.pose = PoseTable(self)                   # `opt.pose_opt`: the camera-gradient table and its counts
         self.exposure = ExposureControl(self)         # `opt.exposure_opt`: which cameras have an exposure, its gradient and its Adam step
+        self.reproj = reproj_host.ReprojCache()       # `opt.reproj_weight`: per target its source views and their tables (not in checkpoints)
         self.background = torch.tensor(background, dtype=torch.float32, device=gaussians._xyz.device)
         self._rng = np.random.default_rng(self.opt.seed)
         self.reset_optimizers()
@@ -172,6 +176,7 @@ class GSTrainer:
         for scale, lst in self.scene.train_cameras.items():
             keep = list(lst) if append else [c for c in lst if not getattr(c, "is_pseudo", False)]
             self.scene.train_cameras[scale] = keep + cams
+        self.reproj.retain(self.scene.train_cameras[1.0])       # (a retired pseudo-view and its image must not live on in the source cache)
 
     # ---- checkpoints with the reference's file names (diffusionGS.py:1611-1625)
     def _ckpt_dir(self) -> str:
@@ -390,6 +395,12 @@ class GSTrainer:
             return None
         return self.depth_edge_weights(cam)
 
+    def _reproj_sources(self, cam: Camera):
+        """The sources of a step on `cam` when the reprojection term acts on it at this iteration: (source images, `ReprojViews`,
+        source cameras) from the per-target cache (`gs/reproj.py`), else None - the term is off, the iteration is before
+        `opt.reproj_from_iter`, the camera is not of `opt.reproj_cameras`, has no target image, or no input view passes the source rule."""
+        return reproj_host.sources_for(self.reproj, self.opt, cam, self.scene.getTrainCameras(), self.iteration)
+
     def _photo_loss(self, image: torch.Tensor, cam: Camera, with_grad: bool):
         """The photometric term of a step on `cam`: the scalar weight is `cam.cam_confidence`, the per-pixel one `cam.confidence_map`
         (None: none), `opt.lambda_dssim` > 0 takes the D-SSIM loss and 0 plain L1.  `with_grad` (the explicit route): the operators
@@ -419,6 +430,7 @@ class GSTrainer:
             raise ValueError("_explicit_step: a confidence tensor that requires grad needs train_step(explicit=False)")
         prior = self._depth_term_prior(cam)
         edge = self._depth_smooth_weights(cam)
+        rsrc = self._reproj_sources(cam)
         f3 = self.ensure_filter_3D()
         with torch.no_grad():
             # log-scales / raw quaternions / logits in, THEIR gradients out (syn3r_raster_*_raw)
@@ -441,12 +453,18 @@ class GSTrainer:
             if edge is not None:                      # prior-free smoothness: ADDED into the buffer of the terms above when one is on
                 d_loss, d_depth = depth_smoothness_loss_step(depth, edge, self.opt.depth_smooth_weight, grad_out=d_depth)
                 loss = loss + d_loss
+            d_alpha = None
+            if rsrc is not None:                      # reprojection: depth gradient ADDED into the buffer above, the alpha gradient is new
+                d_loss, d_depth, d_alpha = photo_reprojection_loss_step(depth, alpha, cam.original_image, rsrc[0], rsrc[1],
+                                                                        self.opt.reproj_weight, self.opt.reproj_alpha_min,
+                                                                        grad_out=d_depth)
+                loss = loss + d_loss
             extra = {}
             if self.opt.densify_abs_grad:             # (uninitialised: the backward writes every row)
                 extra["viewspace_abs_grad"] = torch.empty((g._xyz.shape[0], 2), dtype=torch.float32, device=g._xyz.device)
             pose_row = self.pose.row(cam)             # the camera gradient of this step is ADDED to the camera's row: no host read here
             d_m3, d_m2, d_sh, d_lg, d_ls, d_rr, _ = raster.rasterize_backward(
-                rstate, d_color, d_depth, abs_grad_out=extra.get("viewspace_abs_grad"),
+                rstate, d_color, d_depth, d_alpha, abs_grad_out=extra.get("viewspace_abs_grad"),
                 camera_grad_out=None if pose_row is None else self.pose.table[pose_row], camera_grad_accumulate=True)
             self.pose.count(pose_row)
             g._xyz.grad, g._features.grad, g._opacity.grad, g._scaling.grad, g._rotation.grad = d_m3, d_sh, d_lg.reshape(g._opacity.shape), d_ls, d_rr
@@ -483,6 +501,10 @@ class GSTrainer:
         edge = self._depth_smooth_weights(cam)
         if edge is not None:
             loss = loss + depth_smoothness_loss(out["depth"], edge, self.opt.depth_smooth_weight)
+        rsrc = self._reproj_sources(cam)
+        if rsrc is not None:
+            loss = loss + photo_reprojection_loss(out["depth"], out["alpha"], cam.original_image, rsrc[0], rsrc[1],
+                                                  self.opt.reproj_weight, self.opt.reproj_alpha_min)
         if self.opt.mcmc:                             # the two L1 regularisers on the plain opacity and scales (not the filter_3d ones)
             g = self.gaussians
             loss = loss + (self.opt.mcmc_opacity_reg * g.get_opacity.mean() + self.opt.mcmc_scale_reg * g.get_scaling.mean())
@@ -516,6 +538,20 @@ class GSTrainer:
         well.  The edge weights come from `depth_edge_weights(cam)` (once per camera, cached on it).  Weighted by
         `depth_smooth_weight` alone, not by the camera confidence or its map.  On the explicit route its gradient is added into the
         Pearson terms' buffer when one of them made one.  gamma = 1 and the division by the mean are recalled from Monodepth2: UNPINNED.
+        `opt.reproj_weight` > 0 (EXTENSION, default off: every launch is what it was) adds the multi-view photometric reprojection
+        term after the smoothness term (`train_ops.photo_reprojection_loss`: two more launches), on both routes: the rendered depth
+        along the ray, depth / alpha, carries each pixel of the target into up to `opt.reproj_sources` other input views, and
+        `reproj_weight` x the mean over the live pixels of the smallest L1 difference between the colour found there and the
+        target's own is the loss (Monodepth2's minimum reprojection error, no SSIM, no auto-mask: UNPINNED).  It acts on the cameras
+        of `opt.reproj_cameras` from iteration `opt.reproj_from_iter` on; sources are input views chosen by `gs/reproj.py`'s rule
+        (same size, viewing direction within `opt.reproj_max_angle` degrees, nearest first) and cached per target until a pose or the
+        camera list changes; a target without a source skips the term.  Weighted by `reproj_weight` alone, not by the camera
+        confidence or its map, and it compares the RAW images: the exposure transform does not touch it.  It has gradients for
+        depth AND alpha: on the explicit route the depth gradient is added into the buffer of the terms before it when one of them
+        made one, the alpha gradient is a new buffer, and `rasterize_backward` is handed a `g_alpha` only on a step on which the
+        term ran.  Out of scope: a gradient through the relative views (with `opt.pose_opt` the term sees the moved poses, and its
+        depth and alpha gradients reach the target's pose through the render as any depth gradient does, but how q depends on the poses
+        is not differentiated), exposure compensation between input views, an occlusion test against a second render.
         `cam.confidence_map` (EXTENSION, default None: the scalar-only, reference-shaped loss): a per-pixel weight on the photometric
         term (L1 and D-SSIM, `train_ops.photometric_loss(weight_map=)`) on top of the scalar `cam.cam_confidence`, on both the
         explicit and the autograd path.  The depth-correlation and LPIPS terms are NOT touched by the map.

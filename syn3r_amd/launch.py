@@ -109,6 +109,22 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--depth_smooth_cameras", type=str, default="all", choices=("all", "train", "pseudo"),
                     help="OptimizationParams.depth_smooth_cameras: the cameras --depth_smooth_weight acts on - the input views, the "
                          "diffusion pseudo-views, or both")
+    ap.add_argument("--reproj_weight", type=float, default=0.0,
+                    help="EXTENSION (not in the reference): weight of the multi-view photometric reprojection term - the rendered depth "
+                         "carries each pixel into other input views and the smallest L1 colour difference found there is penalised "
+                         "(Monodepth2's minimum reprojection error, no SSIM, no auto-mask; gradients for depth and alpha); 0 = off")
+    ap.add_argument("--reproj_sources", type=int, default=2, choices=(1, 2, 3, 4),
+                    help="OptimizationParams.reproj_sources: source views per target, the nearest input views first")
+    ap.add_argument("--reproj_cameras", type=str, default="train", choices=("train", "pseudo", "all"),
+                    help="OptimizationParams.reproj_cameras: the TARGET cameras --reproj_weight acts on - the input views, the diffusion "
+                         "pseudo-views, or both; sources are always input views")
+    ap.add_argument("--reproj_alpha_min", type=float, default=0.5,
+                    help="OptimizationParams.reproj_alpha_min: a pixel below this rendered alpha is left out (chosen, UNPINNED)")
+    ap.add_argument("--reproj_max_angle", type=float, default=45.0,
+                    help="OptimizationParams.reproj_max_angle: largest angle in degrees between the viewing directions of a target and "
+                         "a source (chosen, UNPINNED)")
+    ap.add_argument("--reproj_from_iter", type=int, default=0,
+                    help="OptimizationParams.reproj_from_iter: first iteration that carries the term")
     ap.add_argument("--pixel_confidence", type=int, default=0, choices=(0, 1),
                     help="1: EXTENSION (not in the reference) - every diffusion pseudo-view is weighted per pixel in the photometric loss by "
                          "1 - the fused uncertainty of its interpolation (backward_warp only), on top of --cam_confidence; the pairs' .pt "
@@ -196,7 +212,9 @@ def parse(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                                                        "--pose_opt_interval", "--exposure_opt", "--exposure_cameras", "--exposure_lr",
                                                        "--exposure_lr_final", "--mcmc", "--mcmc_cap_max", "--mcmc_noise_lr",
                                                        "--mcmc_opacity_reg", "--mcmc_scale_reg", "--depth_smooth_weight",
-                                                       "--depth_smooth_gamma", "--depth_smooth_cameras"]
+                                                       "--depth_smooth_gamma", "--depth_smooth_cameras", "--reproj_weight",
+                                                       "--reproj_sources", "--reproj_cameras", "--reproj_alpha_min",
+                                                       "--reproj_max_angle", "--reproj_from_iter"]
     # (a token that IS a declared flag is not an abbreviation of a longer one: --densify_abs_grad / --densify_abs_grad_threshold)
     cut = [t for t in given if t.startswith("--") and t.split("=")[0] not in declared
            and any(d.startswith(t.split("=")[0]) for d in declared)]
@@ -232,7 +250,9 @@ def apply_trainer_flags(opt, args):
     sets `pose_opt`; `--pose_opt_cameras`, `--pose_lr_rotation`, `--pose_lr_translation` and `--pose_opt_interval`, when given, set theirs.
     `--exposure_opt 1` sets `exposure_opt`; `--exposure_cameras`, `--exposure_lr` and `--exposure_lr_final`, when given, set theirs.
     `--mcmc 1` sets `mcmc`; `--mcmc_cap_max`, `--mcmc_noise_lr`, `--mcmc_opacity_reg` and `--mcmc_scale_reg`, when given, set theirs.
-    `--depth_smooth_weight`, `--depth_smooth_gamma` and `--depth_smooth_cameras` set theirs (the flags' defaults are the options' own: 0, 1, "all").  (--sh_degree
+    `--depth_smooth_weight`, `--depth_smooth_gamma` and `--depth_smooth_cameras` set theirs (the flags' defaults are the options' own: 0, 1, "all").
+    `--reproj_weight`, `--reproj_sources`, `--reproj_cameras`, `--reproj_alpha_min`, `--reproj_max_angle` and `--reproj_from_iter` set
+    theirs likewise (defaults 0, 2, "train", 0.5, 45, 0); a value the term cannot run with is a ValueError (`gs.reproj.check_options`).  (--sh_degree
     describes the model, not the optimiser: the scene factory reads it.)"""
     import dataclasses
     new = {}
@@ -270,7 +290,14 @@ def apply_trainer_flags(opt, args):
     for flag, typ in (("depth_smooth_weight", float), ("depth_smooth_gamma", float), ("depth_smooth_cameras", str)):
         if getattr(args, flag, None) is not None:
             new[flag] = typ(getattr(args, flag))
-    return dataclasses.replace(opt, **new)
+    for flag, typ in (("reproj_weight", float), ("reproj_sources", int), ("reproj_cameras", str), ("reproj_alpha_min", float),
+                      ("reproj_max_angle", float), ("reproj_from_iter", int)):
+        if getattr(args, flag, None) is not None:
+            new[flag] = typ(getattr(args, flag))
+    out = dataclasses.replace(opt, **new)
+    from .gs.reproj import check_options
+    check_options(out)
+    return out
 
 
 # scripts/train.py:44-46 builds FSGS' three parameter groups on the parser; these are the flags of theirs that the reference's
