@@ -19,6 +19,9 @@ import numpy as np
 import torch
 
 TILE = 16
+# the near-plane constant is the fp32 value the published kernels compare against (`p_view.z <= 0.2f`): a Gaussian whose view-space
+# z is exactly float32(0.2) = 0.2 + 2.98e-9 is culled there, and must be here
+NEAR_CLIP = float(np.float32(0.2))
 SH_C0 = 0.28209479177387814
 SH_C1 = 0.4886025119029199
 SH_C2 = [1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792, 0.5462742152960396]
@@ -68,7 +71,7 @@ def preprocess(means3D, scales, rotations, opacities, shs, confidence, viewmatri
     hom = ph @ Pm
     pw = 1.0 / (hom[:, 3] + 1e-7)
     ndc = hom[:, :2] * pw[:, None]
-    in_front = t[:, 2] > 0.2
+    in_front = t[:, 2] > NEAR_CLIP
     tz = torch.where(in_front, t[:, 2], torch.ones_like(t[:, 2]))
     R = quat_to_rot(rotations)
     Mm = R * (scale_modifier * scales)[:, None, :]

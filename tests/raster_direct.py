@@ -34,11 +34,13 @@ class Direct(NamedTuple):
     backward: Callable            # (gc, gd, ga) -> [d_means3D, d_scales, d_rotations, d_opacities, d_shs, d_means2D, d_confidence]
 
 
-def render_direct(lib, sc, dev, deg, family, raw=0, flags=0, filter3d=None) -> Direct:
+def render_direct(lib, sc, dev, deg, family, raw=0, flags=0, filter3d=None, scale_modifier=1.0) -> Direct:
     """The scene `sc` (tests/raster_aa_ref.scene) through syn3r_raster_preprocess<family>, syn3r_raster_render and, on request,
     syn3r_raster_backward<family>.  `raw` (the "raw" family: always): the tensors are the parameters of raster_f3d_ref.raw_params;
     `raw` and `flags` go to the "ex" and "f3d" entries, `filter3d` (a device tensor or None = NULL) to the "f3d" ones.  Every state
-    and output buffer starts from zeros, so two renders can be compared byte for byte."""
+    and output buffer starts from zeros, so two renders can be compared byte for byte.  `scale_modifier` goes to both passes; a scene
+    whose "cf" is None (or missing) is rendered without a confidence (a null pointer; the backward's d_confidence buffer is still
+    handed over and written)."""
     from syn3r_amd import _lib as L
     suffix, has_modes, has_filter = FAMILIES[family]
     raw = 1 if family == "raw" else raw
@@ -47,7 +49,8 @@ def render_direct(lib, sc, dev, deg, family, raw=0, flags=0, filter3d=None) -> D
     f = lambda t: t.float().to(dev).contiguous()
     N, H, W = sc["N"], sc["H"], sc["W"]
     p = F.raw_params(sc) if raw else sc
-    m3, s, q, o, sh, cf = f(sc["m"]), f(p["s"]), f(p["q"]), f(p["o"]), f(sc["sh"]), f(sc["cf"])
+    m3, s, q, o, sh = f(sc["m"]), f(p["s"]), f(p["q"]), f(p["o"]), f(sc["sh"])
+    cf = f(sc["cf"]) if sc.get("cf") is not None else None
     M = sh.shape[1]
     host = lambda t: L.host_f32(t.double().reshape(-1).tolist())
     view, proj, campos, bg = host(sc["view"].float()), host(sc["proj"].float()), host(sc["campos"].float()), host(sc["bg"].float())
@@ -57,7 +60,7 @@ def render_direct(lib, sc, dev, deg, family, raw=0, flags=0, filter3d=None) -> D
     geom, image = u8(lib.syn3r_raster_geom_bytes(N)), u8(lib.syn3r_raster_image_bytes(H, W))
     radii = torch.zeros(N, dtype=torch.int32, device=dev)
     P = C.c_longlong(0)
-    scene = (L.ptr(m3), L.ptr(s), L.ptr(q), L.ptr(o), L.ptr(sh), L.ptr(cf), 1.0, view, proj, campos, float(sc["tfx"]), float(sc["tfy"]), H, W)
+    scene = (L.ptr(m3), L.ptr(s), L.ptr(q), L.ptr(o), L.ptr(sh), L.ptr(cf), float(scale_modifier), view, proj, campos, float(sc["tfx"]), float(sc["tfy"]), H, W)
     L.check(getattr(lib, "syn3r_raster_preprocess" + suffix)(N, deg, M, *scene, L.ptr(radii), L.ptr(geom), geom.numel(), C.byref(P), *tail),
             "preprocess" + suffix)
     P = int(P.value)
