@@ -24,7 +24,7 @@
 // record per block; the gradient pass merges those records itself in every block (the same order everywhere, so every block
 // holds the same bits - no combine launch, no counter) and writes dL/dd; its block 0 also writes the loss.  The value-only
 // entry merges the records in a one-block launch.  Nothing travels to the host.
-#include "common.h"
+#include "plane_pass.h"
 
 using namespace syn3r;
 
@@ -202,14 +202,7 @@ __global__ void __launch_bounds__(kDcThreads) k_dcorr_grad(const float* __restri
     });
 }
 
-int dc_blocks(long long n) {
-    long long b = (n + kDcThreads * 16 - 1) / (kDcThreads * 16);      // ~16 elements per thread
-    if (b < 1) b = 1;
-    if (b > kDcMaxBlocks) b = kDcMaxBlocks;
-    return (int)b;
-}
-
-bool dc_aligned(const void* a, const void* b) { return (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
+int dc_blocks(long long n) { return pass_blocks(n, kDcThreads * 16, kDcMaxBlocks); }      // ~16 elements per thread
 
 // argument checks shared by the three entries (ws: the records of the statistics pass)
 int dc_check(const char* who, const float* depth, const float* prior, long long n, float weight, float offset, int mode,
@@ -224,11 +217,11 @@ int dc_check(const char* who, const float* depth, const float* prior, long long 
 
 void dc_stats(const float* depth, const float* prior, long long n, float offset, int mode, void* ws, hipStream_t stream) {
     const dim3 grid((unsigned)dc_blocks(n));
-    const bool vec = dc_aligned(depth, prior), inv = mode != SYN3R_DCORR_A;
     DcMom* rec = (DcMom*)ws;
-    auto kern = vec ? (inv ? k_dcorr_stats<true, true> : k_dcorr_stats<true, false>)
-                    : (inv ? k_dcorr_stats<false, true> : k_dcorr_stats<false, false>);
-    SYN3R_LAUNCH_NAMED("k_dcorr_stats", kern, grid, dim3(kDcThreads), 0, stream, depth, prior, n, offset, rec);
+    with_bools([&](auto vec, auto inv) {
+        SYN3R_LAUNCH_NAMED("k_dcorr_stats", (k_dcorr_stats<decltype(vec)::value, decltype(inv)::value>), grid, dim3(kDcThreads), 0, stream,
+                           depth, prior, n, offset, rec);
+    }, aligned16(depth, prior), mode != SYN3R_DCORR_A);
 }
 
 void dc_grad(const float* depth, const float* prior, long long n, float weight, float offset, int mode, const float* grad_loss,
@@ -236,12 +229,10 @@ void dc_grad(const float* depth, const float* prior, long long n, float weight, 
     const dim3 grid((unsigned)dc_blocks(n));
     const DcMom* rec = (const DcMom*)ws;
     const int nrec = dc_blocks(n);
-    if (dc_aligned(depth, prior) && ((uintptr_t)grad_depth & 15) == 0)
-        SYN3R_LAUNCH(k_dcorr_grad<true>, grid, dim3(kDcThreads), 0, stream, depth, prior, n, offset, rec, nrec, mode, weight, grad_loss,
-                     grad_depth, parts);
-    else
-        SYN3R_LAUNCH(k_dcorr_grad<false>, grid, dim3(kDcThreads), 0, stream, depth, prior, n, offset, rec, nrec, mode, weight, grad_loss,
-                     grad_depth, parts);
+    with_bools([&](auto vec) {      // (the trace names these two launches apart)
+        SYN3R_LAUNCH_NAMED(decltype(vec)::value ? "k_dcorr_grad<true>" : "k_dcorr_grad<false>", k_dcorr_grad<decltype(vec)::value>, grid,
+                           dim3(kDcThreads), 0, stream, depth, prior, n, offset, rec, nrec, mode, weight, grad_loss, grad_depth, parts);
+    }, aligned16(depth, prior, grad_depth));
 }
 
 }  // namespace

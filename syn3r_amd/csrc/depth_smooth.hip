@@ -12,27 +12,19 @@
 // gradient, never NaN.  The last column of wx and the last row of wy are absent: never used, whatever they hold.
 // PROVENANCE: gamma = 1 and the division by the mean are recalled from Monodepth2, which is not available to check: UNPINNED.
 //
-// Work is dealt in GROUPS of four consecutive pixels of one row (G = ceil(W / 4) groups per row, the last one ragged when W % 4),
-// group q = y G + gx, one group per thread and trip.
-// GRID RULE: blocks = min(ceil(H G / 256), 1024) of 256 threads for all three kernels, a grid-stride loop beyond (a second trip
-// from H G > 262144 groups on); a block's chunk of groups is xcd_remap(blockIdx) so that the rows above and below a group sit in
-// the same XCD's L2.  The grid is a function of H and W alone: the loss and the gradient are bitwise repeatable for a shape.
-// VEC: W % 4 == 0 and every plane pointer 16-byte aligned, so a group of a plane is one aligned 16-byte access; else four scalar
-// accesses.  All loads of a trip - the group, the rows above and below, the columns left and right - are unconditional (indices
-// past a border are clamped to the border and their values dropped by a select, never multiplied by zero) so that they are
-// requested together, not one wait each (README round 6).  After the loads both paths run the same arithmetic: the same bits.
-// The halo (rows y - 1, y + 1, columns 4 gx - 1, 4 gx + 4) comes through repeated loads, not LDS: measured, profiles/r20/depth_smooth.txt.
+// Groups of four pixels, the grid rule, VEC and the order of the sums: plane_pass.h (blocks = min(ceil(H G / 256), 1024) of 256
+// threads for all three kernels).  The halo (rows y - 1, y + 1, columns 4 gx - 1, 4 gx + 4) comes through repeated unconditional
+// loads, not LDS: measured, profiles/r20/depth_smooth.txt.
 //
 // k_dsmooth_weights: image in, the two planes out (zeros in the absent column and row); once per camera.  expf, no fast intrinsic.
 // k_dsmooth_stats:   one pass over d, wx, wy.  A thread keeps fp32 running sums of S_x N_x, S_y N_y and sum d (4 terms each per
-//                    trip, left to right); they are added over the wave (wave_sum), over the block's four waves in a fixed order
-//                    (block_sum4) and leave as ONE row per block.  ds_combine adds the rows in fp64 in a fixed order.
+//                    trip, left to right) and leaves ONE row per block (block_rows).  ds_combine: combine_rows and what follows from it.
 // k_dsmooth_final:   one block: ds_combine, writes parts.
 // k_dsmooth_grad:    GATHER form: the thread that owns pixel i forms i's incident edges itself and writes grad_depth_i once (fp64
 //                    arithmetic, one fp32 rounding); no scatter, no float atomics.  Every block runs ds_combine (the same order
 //                    everywhere, the same bits), block 0 writes parts when asked.  ACC: the value is ADDED to grad_depth.
 // Built without fma contraction (build.py STRICT_FP).
-#include "common.h"
+#include "plane_pass.h"
 
 using namespace syn3r;
 
@@ -40,48 +32,14 @@ namespace {
 
 constexpr int kDsThreads = 256;
 constexpr int kDsMaxBlocks = 1024;
+static_assert(kDsThreads == kPassThreads && kDsMaxBlocks == kPassMaxBlocks, "block_rows / combine_rows: 256 threads, four rows per thread");
 
 // what the combined rows give: the value record and the gradient's coefficients for weight * g = 1
 struct DsCoef { double sx, sy, m, loss1, ax, ay, c0; bool empty; };
 
-// the four values of row `y` of plane `p` at columns x0 .. x0 + 3 (columns past W - 1 read column W - 1 on the scalar path)
-template <bool VEC>
-__device__ __forceinline__ float4 ds_load4(const float* __restrict__ p, int y, int x0, int W) {
-    const float* r = p + (size_t)y * (size_t)W;
-    if constexpr (VEC) {
-        return *(const float4*)(r + x0);
-    } else {
-        const int l = W - 1;
-        return make_float4(r[x0], r[x0 + 1 < l ? x0 + 1 : l], r[x0 + 2 < l ? x0 + 2 : l], r[x0 + 3 < l ? x0 + 3 : l]);
-    }
-}
-template <bool VEC>
-__device__ __forceinline__ void ds_write4(float* __restrict__ p, int y, int x0, int W, float4 v) {
-    float* r = p + (size_t)y * (size_t)W + x0;
-    if constexpr (VEC) {
-        *(float4*)r = v;
-    } else {
-        r[0] = v.x;
-        if (x0 + 1 < W) r[1] = v.y;
-        if (x0 + 2 < W) r[2] = v.z;
-        if (x0 + 3 < W) r[3] = v.w;
-    }
-}
-
 __device__ __forceinline__ float ds_sel(bool ok, float v) { return ok ? v : 0.0f; }
 // sign(a - b) from the comparison itself: exact whatever the subtraction would round or flush to
 __device__ __forceinline__ double ds_sign(float a, float b) { return a > b ? 1.0 : (a < b ? -1.0 : 0.0); }
-
-// logical block of this physical one, and the group loop: f(y, x0) for every group of the block
-template <typename F>
-__device__ __forceinline__ void ds_walk(int H, int G, F&& f) {
-    const long long total = (long long)H * G, stride = (long long)gridDim.x * kDsThreads;
-    const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
-    for (long long q = (long long)lb * kDsThreads + threadIdx.x; q < total; q += stride) {
-        const int y = (int)(q / G);
-        f(y, ((int)(q - (long long)y * G)) << 2);
-    }
-}
 
 __device__ __forceinline__ float ds_weight1(float gamma, float a0, float b0, float a1, float b1, float a2, float b2) {
     return expf(-gamma * (((fabsf(b0 - a0) + fabsf(b1 - a1)) + fabsf(b2 - a2)) / 3.0f));
@@ -91,14 +49,14 @@ template <bool VEC>
 __global__ void __launch_bounds__(kDsThreads) k_dsmooth_weights(const float* __restrict__ image, int H, int W, int G, float gamma,
                                                                float* __restrict__ weights) {
     const size_t plane = (size_t)H * (size_t)W;
-    ds_walk(H, G, [&](int y, int x0) {
+    plane_walk<kDsThreads>(H, G, [&](int y, int x0) {
         const int yd = y + 1 < H ? y + 1 : H - 1, xr = x0 + 4 < W ? x0 + 4 : W - 1;
         float4 c[3], dn[3];
         float r[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            c[k] = ds_load4<VEC>(image + k * plane, y, x0, W);
-            dn[k] = ds_load4<VEC>(image + k * plane, yd, x0, W);
+            c[k] = load4<VEC>(image + k * plane, y, x0, W);
+            dn[k] = load4<VEC>(image + k * plane, yd, x0, W);
             r[k] = image[k * plane + (size_t)y * (size_t)W + xr];
         }
         const bool dy = y + 1 < H;
@@ -111,8 +69,8 @@ __global__ void __launch_bounds__(kDsThreads) k_dsmooth_weights(const float* __r
         wy.y = ds_sel(dy, ds_weight1(gamma, c[0].y, dn[0].y, c[1].y, dn[1].y, c[2].y, dn[2].y));
         wy.z = ds_sel(dy, ds_weight1(gamma, c[0].z, dn[0].z, c[1].z, dn[1].z, c[2].z, dn[2].z));
         wy.w = ds_sel(dy, ds_weight1(gamma, c[0].w, dn[0].w, c[1].w, dn[1].w, c[2].w, dn[2].w));
-        ds_write4<VEC>(weights, y, x0, W, wx);
-        ds_write4<VEC>(weights + plane, y, x0, W, wy);
+        store4<VEC>(weights, y, x0, W, wx);
+        store4<VEC>(weights + plane, y, x0, W, wy);
     });
 }
 
@@ -122,10 +80,10 @@ __global__ void __launch_bounds__(kDsThreads) k_dsmooth_stats(const float* __res
     const float* wxp = wgt;
     const float* wyp = wgt + (size_t)H * (size_t)W;
     float sx = 0.0f, sy = 0.0f, sd = 0.0f;
-    ds_walk(H, G, [&](int y, int x0) {
+    plane_walk<kDsThreads>(H, G, [&](int y, int x0) {
         const int yd = y + 1 < H ? y + 1 : H - 1, xr = x0 + 4 < W ? x0 + 4 : W - 1;
-        const float4 c = ds_load4<VEC>(d, y, x0, W), dn = ds_load4<VEC>(d, yd, x0, W);
-        const float4 wx = ds_load4<VEC>(wxp, y, x0, W), wy = ds_load4<VEC>(wyp, y, x0, W);
+        const float4 c = load4<VEC>(d, y, x0, W), dn = load4<VEC>(d, yd, x0, W);
+        const float4 wx = load4<VEC>(wxp, y, x0, W), wy = load4<VEC>(wyp, y, x0, W);
         const float r = d[(size_t)y * (size_t)W + xr];
         const bool dy = y + 1 < H;
         sx += ds_sel(x0 + 1 < W, wx.x * fabsf(c.y - c.x));
@@ -141,37 +99,13 @@ __global__ void __launch_bounds__(kDsThreads) k_dsmooth_stats(const float* __res
         sd += ds_sel(x0 + 2 < W, c.z);
         sd += ds_sel(x0 + 3 < W, c.w);
     });
-    __shared__ float red[3][kDsThreads / 64];
-    sx = wave_sum(sx); sy = wave_sum(sy); sd = wave_sum(sd);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sx; red[1][threadIdx.x >> 6] = sy; red[2][threadIdx.x >> 6] = sd; }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        rows[xcd_remap(blockIdx.x, gridDim.x)] = make_float4(block_sum4(red[0]), block_sum4(red[1]), block_sum4(red[2]), 0.0f);
+    if (block_rows(sx, sy, sd)) rows[xcd_remap(blockIdx.x, gridDim.x)] = make_float4(sx, sy, sd, 0.0f);
 }
 
-// The block rows added in fp64, in the same order by every caller, the result on EVERY thread: thread t takes rows t, t + 256,
-// t + 512, t + 768 in that order (four unconditional loads; a row past the end reads the last one and counts as zero), then the
-// wave tree and the four waves in the fixed order.
+// what every caller derives from the combined rows (the same bits on every thread of every block)
 __device__ DsCoef ds_combine(const float4* __restrict__ rows, int nrows, int H, int W) {
-    static_assert(kDsMaxBlocks == 4 * kDsThreads, "ds_combine: four rows per thread");
-    __shared__ double red[3][kDsThreads / 64];
-    float4 v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int r = (int)threadIdx.x + k * kDsThreads;
-        v[k] = rows[r < nrows ? r : nrows - 1];
-    }
-    double sx = 0.0, sy = 0.0, sd = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const bool ok = (int)threadIdx.x + k * kDsThreads < nrows;
-        sx += ok ? (double)v[k].x : 0.0; sy += ok ? (double)v[k].y : 0.0; sd += ok ? (double)v[k].z : 0.0;
-    }
-    sx = wave_sum_d(sx); sy = wave_sum_d(sy); sd = wave_sum_d(sd);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sx; red[1][threadIdx.x >> 6] = sy; red[2][threadIdx.x >> 6] = sd; }
-    __syncthreads();
-    sx = block_sum4(red[0]); sy = block_sum4(red[1]); sd = block_sum4(red[2]);
-    __syncthreads();
+    double sx, sy, sd;
+    combine_rows(rows, nrows, sx, sy, sd);
     DsCoef k{};
     const double n = (double)H * (double)W, nx = (double)H * (double)(W - 1), ny = (double)(H - 1) * (double)W;
     k.m = sd / n;
@@ -210,15 +144,15 @@ __global__ void __launch_bounds__(kDsThreads) k_dsmooth_grad(const float* __rest
     const bool empty = k.empty;
     const float* wxp = wgt;
     const float* wyp = wgt + (size_t)H * (size_t)W;
-    ds_walk(H, G, [&](int y, int x0) {
+    plane_walk<kDsThreads>(H, G, [&](int y, int x0) {
         const int yu = y > 0 ? y - 1 : 0, yd = y + 1 < H ? y + 1 : H - 1;
         const int xl = x0 > 0 ? x0 - 1 : 0, xr = x0 + 4 < W ? x0 + 4 : W - 1;
         const size_t row = (size_t)y * (size_t)W;
-        const float4 c = ds_load4<VEC>(d, y, x0, W), up = ds_load4<VEC>(d, yu, x0, W), dn = ds_load4<VEC>(d, yd, x0, W);
-        const float4 wx = ds_load4<VEC>(wxp, y, x0, W), wy = ds_load4<VEC>(wyp, y, x0, W), wu = ds_load4<VEC>(wyp, yu, x0, W);
+        const float4 c = load4<VEC>(d, y, x0, W), up = load4<VEC>(d, yu, x0, W), dn = load4<VEC>(d, yd, x0, W);
+        const float4 wx = load4<VEC>(wxp, y, x0, W), wy = load4<VEC>(wyp, y, x0, W), wu = load4<VEC>(wyp, yu, x0, W);
         const float dl = d[row + xl], dr = d[row + xr], wl = wxp[row + xl];
         float4 old = make_float4(0.f, 0.f, 0.f, 0.f);
-        if constexpr (ACC) old = ds_load4<VEC>(grad, y, x0, W);
+        if constexpr (ACC) old = load4<VEC>(grad, y, x0, W);
         const bool hu = y > 0, hd = y + 1 < H;
         // pixel x: its left edge (weight wa, neighbour a), right edge (wb, b), the edges above (wc, e) and below (wd, f)
         auto one = [&](bool has_l, float wa, float a, bool has_r, float wb, float b, float v, float wc, float e, float wd, float f) -> float {
@@ -233,19 +167,12 @@ __global__ void __launch_bounds__(kDsThreads) k_dsmooth_grad(const float* __rest
         o.z = one(true, wx.y, c.y, x0 + 3 < W, wx.z, c.w, c.z, wu.z, up.z, wy.z, dn.z);
         o.w = one(true, wx.z, c.z, x0 + 4 < W, wx.w, dr, c.w, wu.w, up.w, wy.w, dn.w);
         if constexpr (ACC) { o.x = old.x + o.x; o.y = old.y + o.y; o.z = old.z + o.z; o.w = old.w + o.w; }
-        ds_write4<VEC>(grad, y, x0, W, o);
+        store4<VEC>(grad, y, x0, W, o);
     });
 }
 
-int ds_groups_per_row(int W) { return (W + 3) >> 2; }
-
 // blocks of all three grids: a function of H and W alone
-int ds_blocks(int H, int W) {
-    long long b = ((long long)H * ds_groups_per_row(W) + kDsThreads - 1) / kDsThreads;
-    if (b < 1) b = 1;
-    if (b > kDsMaxBlocks) b = kDsMaxBlocks;
-    return (int)b;
-}
+int ds_blocks(int H, int W) { return pass_blocks((long long)H * groups_per_row(W), kDsThreads, kDsMaxBlocks); }
 
 // argument checks shared by the three loss entries, all before any HIP call (ws: the rows of the statistics pass)
 int ds_check(const char* who, const float* depth, const float* weights, int H, int W, float weight, const void* ws, size_t ws_bytes) {
@@ -257,34 +184,29 @@ int ds_check(const char* who, const float* depth, const float* weights, int H, i
 
 // the checks of an entry that writes grad_depth
 int ds_check_grad(const char* who, const float* depth, const float* weights, int H, int W, const float* grad_depth, int accumulate) {
-    SYN3R_REQUIRE(grad_depth, "%s: null pointer", who);
-    SYN3R_REQUIRE(accumulate == 0 || accumulate == 1, "%s: accumulate=%d must be 0 or 1", who, accumulate);
+    if (const int rc = check_grad_target(who, grad_depth, accumulate, "accumulate")) return rc;
     const size_t bytes = (size_t)H * (size_t)W * sizeof(float);
     SYN3R_REQUIRE(!ranges_overlap(grad_depth, bytes, depth, bytes) && !ranges_overlap(grad_depth, bytes, weights, 2 * bytes),
                   "%s: grad_depth aliases an input", who);
     return SYN3R_OK;
 }
 
-bool ds_vec(int W, const void* a, const void* b, const void* c) {
-    return W % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
-}
-
 void ds_stats(const float* depth, const float* weights, int H, int W, void* ws, hipStream_t stream) {
     const dim3 grid((unsigned)ds_blocks(H, W));
-    const int G = ds_groups_per_row(W);
-    if (ds_vec(W, depth, weights, nullptr))
-        SYN3R_LAUNCH_NAMED("k_dsmooth_stats", k_dsmooth_stats<true>, grid, dim3(kDsThreads), 0, stream, depth, weights, H, W, G, (float4*)ws);
-    else
-        SYN3R_LAUNCH_NAMED("k_dsmooth_stats", k_dsmooth_stats<false>, grid, dim3(kDsThreads), 0, stream, depth, weights, H, W, G, (float4*)ws);
+    const int G = groups_per_row(W);
+    with_bools([&](auto vec) {
+        SYN3R_LAUNCH_NAMED("k_dsmooth_stats", k_dsmooth_stats<decltype(vec)::value>, grid, dim3(kDsThreads), 0, stream, depth, weights, H, W,
+                           G, (float4*)ws);
+    }, W % 4 == 0 && aligned16(depth, weights));
 }
 
 void ds_grad(const float* depth, const float* weights, int H, int W, float weight, const float* grad_loss, const void* ws,
              float* grad_depth, int accumulate, float* parts, hipStream_t stream) {
-    const int nb = ds_blocks(H, W), G = ds_groups_per_row(W);
+    const int nb = ds_blocks(H, W), G = groups_per_row(W);
     with_bools([&](auto vec, auto acc) {
         SYN3R_LAUNCH_NAMED("k_dsmooth_grad", (k_dsmooth_grad<decltype(vec)::value, decltype(acc)::value>), dim3((unsigned)nb), dim3(kDsThreads),
                            0, stream, depth, weights, H, W, G, (const float4*)ws, nb, weight, grad_loss, grad_depth, parts);
-    }, ds_vec(W, depth, weights, grad_depth), accumulate != 0);
+    }, W % 4 == 0 && aligned16(depth, weights, grad_depth), accumulate != 0);
 }
 
 }  // namespace
@@ -296,12 +218,12 @@ extern "C" int syn3r_depth_edge_weights(const float* image, int H, int W, float 
     const size_t plane = (size_t)H * (size_t)W * sizeof(float);
     SYN3R_REQUIRE(!ranges_overlap(weights, 2 * plane, image, 3 * plane), "depth_edge_weights: weights aliases an input");
     const dim3 grid((unsigned)ds_blocks(H, W));
-    const int G = ds_groups_per_row(W);
+    const int G = groups_per_row(W);
     hipStream_t stream = (hipStream_t)stream_;
-    if (ds_vec(W, image, weights, nullptr))
-        SYN3R_LAUNCH_NAMED("k_dsmooth_weights", k_dsmooth_weights<true>, grid, dim3(kDsThreads), 0, stream, image, H, W, G, gamma, weights);
-    else
-        SYN3R_LAUNCH_NAMED("k_dsmooth_weights", k_dsmooth_weights<false>, grid, dim3(kDsThreads), 0, stream, image, H, W, G, gamma, weights);
+    with_bools([&](auto vec) {
+        SYN3R_LAUNCH_NAMED("k_dsmooth_weights", k_dsmooth_weights<decltype(vec)::value>, grid, dim3(kDsThreads), 0, stream, image, H, W, G,
+                           gamma, weights);
+    }, W % 4 == 0 && aligned16(image, weights));
     SYN3R_LAUNCH_CHECK("depth_edge_weights launch");
     return SYN3R_OK;
 }

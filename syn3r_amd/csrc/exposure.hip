@@ -9,12 +9,11 @@
 // LDS in a fixed order, and leave as ONE row of twelve partials per block.  The one-block finish kernel adds the rows in a fixed
 // order in fp64.  The grid is a function of H * W alone, so the result is the same bits from call to call for a given shape.
 //
-// Work is dealt in groups of four consecutive pixels, one group per thread and trip (kExpThreads * 4 pixels per block and trip, at
-// most kExpMaxBlocks blocks, a grid-stride loop beyond).  VEC: H * W % 4 == 0 and every plane pointer 16-byte aligned, so a group of a
-// plane is one aligned 16-byte access; else four scalar accesses, the loads of pixels past the end redirected to the last pixel
-// (and their values dropped) so that all loads of a trip are unconditional and issue together (README round 6).
+// The planes are walked flat (n = H * W pixels as one row) in groups of four, at most kExpMaxBlocks blocks; groups, the grid rule,
+// VEC (here: n % 4 == 0) and the unconditional loads: plane_pass.h.  The device code keeps its own group load / store and row tail:
+// on plane_pass.h's load4 / store4 / block_rows_column both kernels compile to other code (k_exposure_pass<false> to two VGPRs more).
 // Built without fma contraction (build.py STRICT_FP): the sums are evaluated left to right as written above.
-#include "common.h"
+#include "plane_pass.h"
 
 using namespace syn3r;
 
@@ -161,14 +160,7 @@ __global__ void __launch_bounds__(kFinishThreads) k_exposure_finish(int nrows, c
 }
 
 // blocks of both grids: a function of the pixel count alone
-int exp_blocks(long long n) {
-    long long b = ((n + 3) / 4 + kExpThreads - 1) / kExpThreads;
-    if (b < 1) b = 1;
-    if (b > kExpMaxBlocks) b = kExpMaxBlocks;
-    return (int)b;
-}
-
-bool exp_aligned16(const void* a, const void* b, const void* c) { return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0; }
+int exp_blocks(long long n) { return pass_blocks((n + 3) / 4, kExpThreads, kExpMaxBlocks); }
 
 }  // namespace
 
@@ -181,10 +173,9 @@ extern "C" int syn3r_exposure_apply(const float* image, const float* A, int H, i
     SYN3R_REQUIRE(!ranges_overlap(out, bytes, image, bytes) && !ranges_overlap(out, bytes, A, a_bytes), "exposure_apply: out aliases an input");
     hipStream_t stream = (hipStream_t)stream_;
     const dim3 grid((unsigned)exp_blocks(n));
-    if (n % 4 == 0 && exp_aligned16(image, out, nullptr))
-        SYN3R_LAUNCH_NAMED("k_exposure_apply", k_exposure_apply<true>, grid, dim3(kExpThreads), 0, stream, image, A, n, out);
-    else
-        SYN3R_LAUNCH_NAMED("k_exposure_apply", k_exposure_apply<false>, grid, dim3(kExpThreads), 0, stream, image, A, n, out);
+    with_bools([&](auto vec) {
+        SYN3R_LAUNCH_NAMED("k_exposure_apply", k_exposure_apply<decltype(vec)::value>, grid, dim3(kExpThreads), 0, stream, image, A, n, out);
+    }, n % 4 == 0 && aligned16(image, out));
     SYN3R_LAUNCH_CHECK("exposure_apply launch");
     return SYN3R_OK;
 }
@@ -209,12 +200,10 @@ extern "C" int syn3r_exposure_backward(const float* image, const float* A, const
     hipStream_t stream = (hipStream_t)stream_;
     const int nb = exp_blocks(n);
     float* rows = (float*)ws;
-    if (n % 4 == 0 && exp_aligned16(image, grad_out, grad_image))
-        SYN3R_LAUNCH_NAMED("k_exposure_pass", k_exposure_pass<true>, dim3((unsigned)nb), dim3(kExpThreads), 0, stream, image, A, grad_out, n,
-                           grad_image, rows);
-    else
-        SYN3R_LAUNCH_NAMED("k_exposure_pass", k_exposure_pass<false>, dim3((unsigned)nb), dim3(kExpThreads), 0, stream, image, A, grad_out, n,
-                           grad_image, rows);
+    with_bools([&](auto vec) {
+        SYN3R_LAUNCH_NAMED("k_exposure_pass", k_exposure_pass<decltype(vec)::value>, dim3((unsigned)nb), dim3(kExpThreads), 0, stream, image, A,
+                           grad_out, n, grad_image, rows);
+    }, n % 4 == 0 && aligned16(image, grad_out, grad_image));
     SYN3R_LAUNCH(k_exposure_finish, dim3(1), dim3(kFinishThreads), 0, stream, nb, (const float*)rows, grad_A, accumulate);
     SYN3R_LAUNCH_CHECK("exposure_backward launch");
     return SYN3R_OK;

@@ -16,7 +16,7 @@
 // (profiles/r16/mcmc.txt).  The relocation sums 51 alternating binomial terms (sum |term| / |sum| up to 8.9e3): fp64 as well.
 // Built without fma contraction (build.py STRICT_FP).  No floating-point atomics; the integer atomics of the sampler count draws and
 // do not depend on order.  Every result is the same bits from call to call.
-#include "common.h"
+#include "plane_pass.h"
 
 using namespace syn3r;
 
@@ -48,12 +48,7 @@ __device__ __forceinline__ U4 philox4x32_10(unsigned c0, unsigned c1, unsigned c
     return U4{c0, c1, c2, c3};
 }
 
-int blocks_for(long long items) {
-    long long b = (items + kThreads - 1) / kThreads;
-    if (b < 1) b = 1;
-    if (b > kMaxBlocks) b = kMaxBlocks;
-    return (int)b;
-}
+int blocks_for(long long items) { return pass_blocks(items, kThreads, kMaxBlocks); }
 
 size_t round256(size_t b) { return ((b + 255) / 256) * 256; }
 
@@ -120,6 +115,7 @@ __global__ void __launch_bounds__(kThreads) k_mcmc_reg_pass(const float* __restr
             ss += (e0 + e1) + e2;
         }
     }
+    // (not plane_pass.h's block_rows: thread k stores column k here, and on the shared staging the kernel compiled to other code)
     __shared__ float part[kThreads / 64][2];
     const float wo = wave_sum(so), ws = wave_sum(ss);
     if ((threadIdx.x & 63) == 0) { part[threadIdx.x >> 6][0] = wo; part[threadIdx.x >> 6][1] = ws; }

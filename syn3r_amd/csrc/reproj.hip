@@ -16,11 +16,8 @@
 // PROVENANCE: the minimum over sources and the L1 form are recalled from Monodepth2 (not available to check); alpha_min and the
 // absence of SSIM and auto-mask are this project's choices: UNPINNED.
 //
-// Work is dealt as in depth_smooth.hip: GROUPS of four consecutive pixels of one row (G = ceil(W / 4) per row), one group per
-// thread and trip.  GRID RULE: blocks = min(ceil(H G / 256), 1024) of 256 threads for both passes, a grid-stride loop beyond (a
-// second trip from H G > 262144 groups on), the block's chunk through xcd_remap.  The grid is a function of H and W alone.
-// VEC: W % 4 == 0 and every plane pointer 16-byte aligned: a group of a plane is one 16-byte access, else four scalar ones; both
-// run the same arithmetic after the loads: the same bits.
+// Groups of four pixels, the grid rule, VEC and the order of the sums: plane_pass.h (blocks = min(ceil(H G / 256), 1024) of 256
+// threads for both passes).
 // k_reproj_stats: geometry, gathers, minimum and the UNSCALED per-pixel dL/dz (weight / N_live = 1).  Per source the 48 taps of a
 //                 group (4 pixels x 4 corners x 3 channels) are unconditional loads at clamped cells (an invalid pixel reads cell
 //                 (0, 0) and drops the values by a select), requested together before the first use (README round 6).  No LDS
@@ -28,12 +25,12 @@
 //                 floats per source) travels by value, as syn3r_adam_step_multi's pointer tables do.  It leaves, per pixel, 8
 //                 bytes: the fp32 dL/dz (0 when dead) and a record word (e's fp32 bits with the two lowest mantissa bits replaced
 //                 by the chosen source; 0xffffffff when dead), and ONE row per block (sum e, N_live, N on source 0, sum e on
-//                 source 0): per-thread fp32 running sums left to right, then wave_sum, then block_sum4.
-// k_reproj_final: one block: rp_combine (the rows in fp64, fixed order), writes parts.
+//                 source 0): per-thread fp32 running sums left to right, then block_rows.
+// k_reproj_final: one block: rp_combine (combine_rows), writes parts.
 // k_reproj_grad:  elementwise over D, a and the dL/dz plane (no gathers): every block runs rp_combine, scales in fp64, one fp32
 //                 rounding per output, writes or ADDS g_depth and g_alpha; block 0 writes parts when asked.
 // No float atomics, no host read.  Built without fma contraction (build.py STRICT_FP).
-#include "common.h"
+#include "plane_pass.h"
 
 using namespace syn3r;
 
@@ -41,6 +38,7 @@ namespace {
 
 constexpr int kRpThreads = 256;
 constexpr int kRpMaxBlocks = 1024;
+static_assert(kRpThreads == kPassThreads && kRpMaxBlocks == kPassMaxBlocks, "block_rows / combine_rows: 256 threads, four rows per thread");
 constexpr int kRpMaxSources = 4;
 constexpr size_t kRpRowBytes = (size_t)kRpMaxBlocks * sizeof(float4);      // head of the workspace; the two planes follow
 constexpr unsigned kRpDead = 0xffffffffu;
@@ -50,42 +48,8 @@ struct RpView { float m[9]; float t[3]; float fx, fy, cx, cy; };
 struct RpTable { const float* img[kRpMaxSources]; RpView v[kRpMaxSources]; };
 struct RpTarget { float fx, fy, cx, cy; };
 
-template <bool VEC>
-__device__ __forceinline__ float4 rp_load4(const float* __restrict__ p, int y, int x0, int W) {
-    const float* r = p + (size_t)y * (size_t)W;
-    if constexpr (VEC) {
-        return *(const float4*)(r + x0);
-    } else {
-        const int l = W - 1;
-        return make_float4(r[x0], r[x0 + 1 < l ? x0 + 1 : l], r[x0 + 2 < l ? x0 + 2 : l], r[x0 + 3 < l ? x0 + 3 : l]);
-    }
-}
-template <bool VEC>
-__device__ __forceinline__ void rp_write4(float* __restrict__ p, int y, int x0, int W, float4 v) {
-    float* r = p + (size_t)y * (size_t)W + x0;
-    if constexpr (VEC) {
-        *(float4*)r = v;
-    } else {
-        r[0] = v.x;
-        if (x0 + 1 < W) r[1] = v.y;
-        if (x0 + 2 < W) r[2] = v.z;
-        if (x0 + 3 < W) r[3] = v.w;
-    }
-}
-
-template <typename F>
-__device__ __forceinline__ void rp_walk(int H, int G, F&& f) {
-    const long long total = (long long)H * G, stride = (long long)gridDim.x * kRpThreads;
-    const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
-    for (long long q = (long long)lb * kRpThreads + threadIdx.x; q < total; q += stride) {
-        const int y = (int)(q / G);
-        f(y, ((int)(q - (long long)y * G)) << 2);
-    }
-}
-
 __device__ __forceinline__ float rp_sign(float a, float b) { return a > b ? 1.0f : (a < b ? -1.0f : 0.0f); }
 __device__ __forceinline__ bool rp_live(float d, float a, float alpha_min) { return a >= alpha_min && d > 0.0f; }
-__device__ __forceinline__ float rp_get(const float4& v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : (k == 2 ? v.z : v.w)); }
 
 // what one pixel knows of one source before its taps arrive
 struct RpGeo { float fx, fy, dqx, dqy; int cell; bool valid; };
@@ -119,18 +83,18 @@ __global__ void __launch_bounds__(kRpThreads) k_reproj_stats(const float* __rest
                                                             unsigned* __restrict__ rec_plane) {
     const size_t plane = (size_t)H * (size_t)W;
     float se = 0.0f, sn = 0.0f, sn0 = 0.0f, se0 = 0.0f;
-    rp_walk(H, G, [&](int y, int x0) {
-        const float4 d4 = rp_load4<VEC>(depth, y, x0, W), a4 = rp_load4<VEC>(alpha, y, x0, W);
+    plane_walk<kRpThreads>(H, G, [&](int y, int x0) {
+        const float4 d4 = load4<VEC>(depth, y, x0, W), a4 = load4<VEC>(alpha, y, x0, W);
         float4 t4[3];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) t4[c] = rp_load4<VEC>(target + c * plane, y, x0, W);
+        for (int c = 0; c < 3; ++c) t4[c] = load4<VEC>(target + c * plane, y, x0, W);
         const float ry = ((float)y - tk.cy) / tk.fy;
         float z[4], rx[4], best_e[4], best_g[4];
         int best_s[4];
         bool live[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float d = rp_get(d4, k), a = rp_get(a4, k);
+            const float d = row_get(d4, k), a = row_get(a4, k);
             live[k] = rp_live(d, a, alpha_min) && x0 + k < W;
             z[k] = live[k] ? d / a : 1.0f;
             rx[k] = ((float)(x0 + k) - tk.cx) / tk.fx;
@@ -161,7 +125,7 @@ __global__ void __launch_bounds__(kRpThreads) k_reproj_stats(const float* __rest
                     const float val = gy1 * (gx1 * i00 + fx * i01) + fy * (gx1 * i10 + fx * i11);
                     const float dx = gy1 * (i01 - i00) + fy * (i11 - i10);
                     const float dy = gx1 * (i10 - i00) + fx * (i11 - i01);
-                    const float tc = rp_get(t4[c], k);
+                    const float tc = row_get(t4[c], k);
                     ad[c] = fabsf(val - tc);
                     gr[c] = rp_sign(val, tc) * (dx * g[k].dqx + dy * g[k].dqy);
                 }
@@ -189,46 +153,19 @@ __global__ void __launch_bounds__(kRpThreads) k_reproj_stats(const float* __rest
         }
         dz4 = make_float4(gz[0], gz[1], gz[2], gz[3]);
         rec4 = make_uint4(rc[0], rc[1], rc[2], rc[3]);
-        rp_write4<VEC>(dz_plane, y, x0, W, dz4);
-        rp_write4<VEC>((float*)rec_plane, y, x0, W,
+        store4<VEC>(dz_plane, y, x0, W, dz4);
+        store4<VEC>((float*)rec_plane, y, x0, W,
                        make_float4(__uint_as_float(rec4.x), __uint_as_float(rec4.y), __uint_as_float(rec4.z), __uint_as_float(rec4.w)));
     });
-    __shared__ float red[4][kRpThreads / 64];
-    se = wave_sum(se); sn = wave_sum(sn); sn0 = wave_sum(sn0); se0 = wave_sum(se0);
-    if ((threadIdx.x & 63) == 0) {
-        const int w = threadIdx.x >> 6;
-        red[0][w] = se; red[1][w] = sn; red[2][w] = sn0; red[3][w] = se0;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        rows[xcd_remap(blockIdx.x, gridDim.x)] = make_float4(block_sum4(red[0]), block_sum4(red[1]), block_sum4(red[2]), block_sum4(red[3]));
+    if (block_rows(se, sn, sn0, se0)) rows[xcd_remap(blockIdx.x, gridDim.x)] = make_float4(se, sn, sn0, se0);
 }
 
 // what the combined rows give: sum e, N_live, N on source 0 (sum e on source 0 is kept in the rows for diagnostics)
 struct RpCoef { double se, n, n0; };
 
-// The block rows added in fp64, in the same order by every caller, the result on EVERY thread (depth_smooth.hip's ds_combine).
 __device__ RpCoef rp_combine(const float4* __restrict__ rows, int nrows) {
-    static_assert(kRpMaxBlocks == 4 * kRpThreads, "rp_combine: four rows per thread");
-    __shared__ double red[3][kRpThreads / 64];
-    float4 v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int r = (int)threadIdx.x + k * kRpThreads;
-        v[k] = rows[r < nrows ? r : nrows - 1];
-    }
-    double se = 0.0, n = 0.0, n0 = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const bool ok = (int)threadIdx.x + k * kRpThreads < nrows;
-        se += ok ? (double)v[k].x : 0.0; n += ok ? (double)v[k].y : 0.0; n0 += ok ? (double)v[k].z : 0.0;
-    }
-    se = wave_sum_d(se); n = wave_sum_d(n); n0 = wave_sum_d(n0);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = se; red[1][threadIdx.x >> 6] = n; red[2][threadIdx.x >> 6] = n0; }
-    __syncthreads();
     RpCoef k;
-    k.se = block_sum4(red[0]); k.n = block_sum4(red[1]); k.n0 = block_sum4(red[2]);
-    __syncthreads();
+    combine_rows(rows, nrows, k.se, k.n, k.n0);
     return k;
 }
 
@@ -253,38 +190,31 @@ __global__ void __launch_bounds__(kRpThreads) k_reproj_grad(const float* __restr
     const RpCoef k = rp_combine(rows, nrows);
     if (parts && blockIdx.x == 0 && threadIdx.x == 0) rp_write_parts(k, H, W, weight, parts);
     const double scale = (double)weight * (go ? (double)*go : 1.0) / (k.n > 1.0 ? k.n : 1.0);
-    rp_walk(H, G, [&](int y, int x0) {
-        const float4 d4 = rp_load4<VEC>(depth, y, x0, W), a4 = rp_load4<VEC>(alpha, y, x0, W), z4 = rp_load4<VEC>(dz_plane, y, x0, W);
+    plane_walk<kRpThreads>(H, G, [&](int y, int x0) {
+        const float4 d4 = load4<VEC>(depth, y, x0, W), a4 = load4<VEC>(alpha, y, x0, W), z4 = load4<VEC>(dz_plane, y, x0, W);
         float4 od = make_float4(0.f, 0.f, 0.f, 0.f), oa = od;
-        if constexpr (ACCD) od = rp_load4<VEC>(grad_depth, y, x0, W);
-        if constexpr (ACCA) oa = rp_load4<VEC>(grad_alpha, y, x0, W);
+        if constexpr (ACCD) od = load4<VEC>(grad_depth, y, x0, W);
+        if constexpr (ACCA) oa = load4<VEC>(grad_alpha, y, x0, W);
         float gd[4], ga[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const float d = rp_get(d4, i), a = rp_get(a4, i);
+            const float d = row_get(d4, i), a = row_get(a4, i);
             const bool live = rp_live(d, a, alpha_min);
             const double da = live ? (double)a : 1.0;
-            const double g = scale * (double)rp_get(z4, i);              // dL/dz (the plane holds 0 for a pixel without a source)
+            const double g = scale * (double)row_get(z4, i);              // dL/dz (the plane holds 0 for a pixel without a source)
             gd[i] = live ? (float)(g / da) : 0.0f;
             ga[i] = live ? (float)(-(g * ((double)d / da)) / da) : 0.0f;
         }
         float4 vd = make_float4(gd[0], gd[1], gd[2], gd[3]), va = make_float4(ga[0], ga[1], ga[2], ga[3]);
         if constexpr (ACCD) { vd.x = od.x + vd.x; vd.y = od.y + vd.y; vd.z = od.z + vd.z; vd.w = od.w + vd.w; }
         if constexpr (ACCA) { va.x = oa.x + va.x; va.y = oa.y + va.y; va.z = oa.z + va.z; va.w = oa.w + va.w; }
-        rp_write4<VEC>(grad_depth, y, x0, W, vd);
-        rp_write4<VEC>(grad_alpha, y, x0, W, va);
+        store4<VEC>(grad_depth, y, x0, W, vd);
+        store4<VEC>(grad_alpha, y, x0, W, va);
     });
 }
 
-int rp_groups_per_row(int W) { return (W + 3) >> 2; }
-
 // blocks of both grids: a function of H and W alone
-int rp_blocks(int H, int W) {
-    long long b = ((long long)H * rp_groups_per_row(W) + kRpThreads - 1) / kRpThreads;
-    if (b < 1) b = 1;
-    if (b > kRpMaxBlocks) b = kRpMaxBlocks;
-    return (int)b;
-}
+int rp_blocks(int H, int W) { return pass_blocks((long long)H * groups_per_row(W), kRpThreads, kRpMaxBlocks); }
 
 bool rp_shape_ok(int H, int W, int S) { return SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W) && H >= 2 && W >= 2 && S >= 1 && S <= kRpMaxSources; }
 
@@ -329,9 +259,8 @@ int rp_check_stats(const char* who, const float* depth, const float* alpha, cons
 // the checks of an entry that writes the two gradients
 int rp_check_grad(const char* who, const float* depth, const float* alpha, int H, int W, const void* ws, size_t ws_bytes,
                   const float* grad_depth, int acc_depth, const float* grad_alpha, int acc_alpha) {
-    SYN3R_REQUIRE(grad_depth && grad_alpha, "%s: null pointer", who);
-    SYN3R_REQUIRE((acc_depth == 0 || acc_depth == 1) && (acc_alpha == 0 || acc_alpha == 1),
-                  "%s: accumulate_depth=%d, accumulate_alpha=%d must be 0 or 1", who, acc_depth, acc_alpha);
+    if (const int rc = check_grad_target(who, grad_depth, acc_depth, "accumulate_depth")) return rc;
+    if (const int rc = check_grad_target(who, grad_alpha, acc_alpha, "accumulate_alpha")) return rc;
     const size_t bytes = (size_t)H * (size_t)W * sizeof(float);
     for (const float* g : {grad_depth, grad_alpha})
         SYN3R_REQUIRE(!ranges_overlap(g, bytes, depth, bytes) && !ranges_overlap(g, bytes, alpha, bytes) &&
@@ -340,31 +269,25 @@ int rp_check_grad(const char* who, const float* depth, const float* alpha, int H
     return SYN3R_OK;
 }
 
-bool rp_vec(int W, const void* a, const void* b, const void* c, const void* d) {
-    return W % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
-}
-
 void rp_stats(const float* depth, const float* alpha, const float* target, int H, int W, int S, const RpTable& tab, const RpTarget& tk,
               float alpha_min, void* ws, hipStream_t stream) {
     const dim3 grid((unsigned)rp_blocks(H, W));
-    const int G = rp_groups_per_row(W);
+    const int G = groups_per_row(W);
     // (the planes of the workspace are 16-byte aligned by construction: with W % 4 == 0 so is every group of them)
-    if (rp_vec(W, depth, alpha, target, nullptr))
-        SYN3R_LAUNCH_NAMED("k_reproj_stats", k_reproj_stats<true>, grid, dim3(kRpThreads), 0, stream, depth, alpha, target, H, W, G, S, tab, tk,
-                           alpha_min, (float4*)ws, rp_dz_plane(ws), rp_rec_plane(ws, H, W));
-    else
-        SYN3R_LAUNCH_NAMED("k_reproj_stats", k_reproj_stats<false>, grid, dim3(kRpThreads), 0, stream, depth, alpha, target, H, W, G, S, tab, tk,
-                           alpha_min, (float4*)ws, rp_dz_plane(ws), rp_rec_plane(ws, H, W));
+    with_bools([&](auto vec) {
+        SYN3R_LAUNCH_NAMED("k_reproj_stats", k_reproj_stats<decltype(vec)::value>, grid, dim3(kRpThreads), 0, stream, depth, alpha, target, H, W,
+                           G, S, tab, tk, alpha_min, (float4*)ws, rp_dz_plane(ws), rp_rec_plane(ws, H, W));
+    }, W % 4 == 0 && aligned16(depth, alpha, target));
 }
 
 void rp_grad(const float* depth, const float* alpha, int H, int W, float weight, float alpha_min, const float* grad_loss, const void* ws,
              float* grad_depth, int acc_depth, float* grad_alpha, int acc_alpha, float* parts, hipStream_t stream) {
-    const int nb = rp_blocks(H, W), G = rp_groups_per_row(W);
+    const int nb = rp_blocks(H, W), G = groups_per_row(W);
     with_bools([&](auto vec, auto accd, auto acca) {
         SYN3R_LAUNCH_NAMED("k_reproj_grad", (k_reproj_grad<decltype(vec)::value, decltype(accd)::value, decltype(acca)::value>),
                            dim3((unsigned)nb), dim3(kRpThreads), 0, stream, depth, alpha, H, W, G, (const float4*)ws, nb,
                            (const float*)rp_dz_plane(ws), weight, alpha_min, grad_loss, grad_depth, grad_alpha, parts);
-    }, rp_vec(W, depth, alpha, grad_depth, grad_alpha), acc_depth != 0, acc_alpha != 0);
+    }, W % 4 == 0 && aligned16(depth, alpha, grad_depth, grad_alpha), acc_depth != 0, acc_alpha != 0);
 }
 
 }  // namespace

@@ -10,7 +10,7 @@
 //   Adam         one kernel per parameter tensor, torch.optim.Adam's operation order (lerp / addcmul / addcdiv)
 //                so the result matches the torch optimiser to rounding.
 // HBM-bound: 8 B/element (forward), 12 B/element (backward), 28 B/element (Adam).
-#include "common.h"
+#include "plane_pass.h"
 
 using namespace syn3r;
 
@@ -38,11 +38,7 @@ __global__ void __launch_bounds__(kThreads) k_l1_partial(const float* __restrict
         long long i = (n4 << 2) + threadIdx.x;
         if (i < n) s += dist_term<SQ>(a[i] - b[i]);
     }
-    s = wave_sum(s);
-    __shared__ float ws[kThreads / 64];
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = block_sum4(ws);
+    if (block_rows(s)) partial[blockIdx.x] = s;
 }
 
 // one block: fixed-order sum of the block partials (bitwise reproducible run to run)
@@ -127,11 +123,7 @@ __global__ void __launch_bounds__(kThreads) k_l1_partial_map(const float* __rest
         long long i = (n4 << 2) + threadIdx.x;
         if (i < n) s += m[l1_map_rem(i, plane)] * fabsf(a[i] - b[i]);
     }
-    s = wave_sum(s);
-    __shared__ float ws[kThreads / 64];
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = block_sum4(ws);
+    if (block_rows(s)) partial[blockIdx.x] = s;
 }
 
 template <bool VEC>

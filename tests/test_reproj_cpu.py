@@ -344,6 +344,8 @@ def test_exports_header_and_signatures():
     assert "UNPINNED" in header[header.index("Multi-view photometric reprojection"):header.index(ENTRIES[0] + "(")]
     src = (ROOT / "syn3r_amd" / "csrc" / "reproj.hip").read_text()
     assert "atomic" not in src.split("#include")[1]                 # no float atomics (the word appears in the header comment alone)
+    assert '#include "plane_pass.h"' in src                            # the walk, the block rows and their sum live there: nor there
+    assert "atomic" not in (ROOT / "syn3r_amd" / "csrc" / "plane_pass.h").read_text()
     assert f"kRpMaxBlocks = {R.MAX_BLOCKS};" in src and f"kRpThreads = {R.THREADS};" in src
     with pytest.raises(_lib.Syn3rError):                               # no CPU fallback
         train_ops.photo_reprojection_loss(torch.rand(4, 4), torch.rand(4, 4), torch.rand(3, 4, 4), [torch.rand(3, 4, 4)],
