@@ -705,20 +705,27 @@ extern "C" int syn3r_conv2d3x3_up4_f16(const void* X, const void* W4, void* out,
     return launch_z_up4(p, (hipStream_t)stream, gn_written);
 }
 
-extern "C" int syn3r_conv2d3x3_act_f16(const void* X, const void* W, void* out, const void* bias, int relu, const void* relu_mask,
-                                       int NB, int Hi, int Wi, int Cin, int Cout, void* stream) {
-    SYN3R_REQUIRE(NB > 0 && Hi > 0 && Wi > 0 && Cin > 0 && Cout > 0, "conv2d3x3_act: bad sizes");
-    SYN3R_REQUIRE(Cin % BK == 0 && Cout % 8 == 0, "conv2d3x3_act: Cin=%d must be a multiple of %d, Cout=%d of 8", Cin, BK, Cout);
-    GemmParams p{};
-    p.A = (const __half*)X; p.W = (const __half*)W; p.out = (__half*)out; p.ldc = Cout; p.bias = (const __half*)bias;
+namespace {
+// The problem of the two bias / ReLU / mask convolution entries below, checked (`who`: the entry's name in error messages)
+int conv3x3_act_params(const char* who, const void* X, const void* W, void* out, long long ldc, const void* bias, int relu, const void* relu_mask,
+                       long long ld_mask, int NB, int Hi, int Wi, int Cin, int Cout, GemmParams& p) {
+    SYN3R_REQUIRE(NB > 0 && Hi > 0 && Wi > 0 && Cin > 0 && Cout > 0, "%s: bad sizes", who);
+    SYN3R_REQUIRE(Cin % BK == 0 && Cout % 8 == 0, "%s: Cin=%d must be a multiple of %d, Cout=%d of 8", who, Cin, BK, Cout);
+    p.A = (const __half*)X; p.W = (const __half*)W; p.out = (__half*)out; p.ldc = ldc; p.bias = (const __half*)bias;
     p.s_acc = 1.0f; p.s_res = 0.f; p.s_aux = 0.f;
-    p.relu = relu ? 1 : 0; p.relu_mask = (const __half*)relu_mask;
+    p.relu = relu ? 1 : 0; p.relu_mask = (const __half*)relu_mask; p.ld_mask = (int)ld_mask;
     p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.stride = 1; p.ups = 0; p.pad = 1; p.Ho = Hi; p.Wo = Wi;
     long long M = (long long)NB * Hi * Wi;
-    SYN3R_REQUIRE(M < (1ll << 31), "conv2d3x3_act: too many output pixels");
+    SYN3R_REQUIRE(M < (1ll << 31), "%s: too many output pixels", who);
     p.M = (int)M; p.N = Cout; p.K = 9 * Cin;
-    int rc = check_common(p, "conv2d3x3_act");
-    if (rc) return rc;
+    return check_common(p, who);
+}
+}  // namespace
+
+extern "C" int syn3r_conv2d3x3_act_f16(const void* X, const void* W, void* out, const void* bias, int relu, const void* relu_mask,
+                                       int NB, int Hi, int Wi, int Cin, int Cout, void* stream) {
+    GemmParams p{};
+    if (int rc = conv3x3_act_params("conv2d3x3_act", X, W, out, Cout, bias, relu, relu_mask, 0, NB, Hi, Wi, Cin, Cout, p)) return rc;
     SYN3R_REQUIRE(((uintptr_t)relu_mask % 16) == 0, "conv2d3x3_act: mask must be 16-byte aligned");
     // the persistent kernels have their own (lean) epilogue: the convolution modes never use them (launch_dma_bm)
     return launch_dma<MODE_CONV2D>(p, (hipStream_t)stream);
@@ -732,21 +739,12 @@ extern "C" int syn3r_conv2d3x3_act_f16(const void* X, const void* W, void* out, 
 // k_splitk_finish, and the ReLU launches of the fp16 mode do not split either (launch_splitk).
 extern "C" int syn3r_conv2d3x3_split_f16(const void* X, const void* W, void* out, long long ld_out, const void* bias, int relu, int split_out,
                                          const void* relu_mask, long long ld_mask, int NB, int Hi, int Wi, int Cin, int Cout, void* stream) {
-    SYN3R_REQUIRE(NB > 0 && Hi > 0 && Wi > 0 && Cin > 0 && Cout > 0, "conv2d3x3_split: bad sizes");
-    SYN3R_REQUIRE(Cin % BK == 0 && Cout % 8 == 0, "conv2d3x3_split: Cin=%d must be a multiple of %d, Cout=%d of 8", Cin, BK, Cout);
+    // (ahead of the shared checks: a short ld_out is reported as such, not as check_common's ldc)
     SYN3R_REQUIRE(ld_out >= (split_out ? 2ll : 1ll) * Cout, "conv2d3x3_split: ld_out=%lld is short of %d columns", ld_out, (split_out ? 2 : 1) * Cout);
     SYN3R_REQUIRE(!(split_out && relu_mask), "conv2d3x3_split: a mask goes with the plain output only");
     SYN3R_REQUIRE(!relu_mask || (ld_mask >= Cout && ld_mask % 8 == 0 && ld_mask < (1ll << 31)), "conv2d3x3_split: bad mask stride %lld", ld_mask);
     GemmParams p{};
-    p.A = (const __half*)X; p.W = (const __half*)W; p.out = (__half*)out; p.ldc = ld_out; p.bias = (const __half*)bias;
-    p.s_acc = 1.0f; p.s_res = 0.f; p.s_aux = 0.f;
-    p.relu = relu ? 1 : 0; p.relu_mask = (const __half*)relu_mask; p.ld_mask = (int)ld_mask;
-    p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.stride = 1; p.ups = 0; p.pad = 1; p.Ho = Hi; p.Wo = Wi;
-    long long M = (long long)NB * Hi * Wi;
-    SYN3R_REQUIRE(M < (1ll << 31), "conv2d3x3_split: too many output pixels");
-    p.M = (int)M; p.N = Cout; p.K = 9 * Cin;
-    int rc = check_common(p, "conv2d3x3_split");
-    if (rc) return rc;
+    if (int rc = conv3x3_act_params("conv2d3x3_split", X, W, out, ld_out, bias, relu, relu_mask, ld_mask, NB, Hi, Wi, Cin, Cout, p)) return rc;
     SYN3R_REQUIRE((((uintptr_t)relu_mask | (uintptr_t)bias) % 16) == 0, "conv2d3x3_split: mask and bias must be 16-byte aligned");
     static_assert(8 * WM * EPI_LD * sizeof(__half) <= DMA256_LDS, "one staged fp16 plane must fit in the ring");
     if (split_out)

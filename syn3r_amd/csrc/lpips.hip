@@ -31,25 +31,11 @@ __constant__ float kShift[3] = {-0.030f, -0.088f, -0.188f};
 __constant__ float kScale[3] = {0.458f, 0.448f, 0.450f};
 
 // [3,H,W] fp32 in [0,1] -> [H*W, 64] fp16: channel c = ((2x - 1) - shift_c) / scale_c, channels 3..63 zero (the convolution
-// kernel wants Cin % 64 == 0)
+// kernel wants Cin % 64 == 0).  SPLIT: every channel as a pair, hi in channels 0..2, lo in 3..5 (conv1_1's weights are repeated
+// there), 6..63 zero
+template <bool SPLIT>
 __global__ void __launch_bounds__(256) k_lpips_image(const float* __restrict__ img, long long hw, __half* __restrict__ out) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;          // one thread per (pixel, 8-channel chunk)
-    if (i >= hw * 8) return;
-    const long long p = i >> 3;
-    const int ch = (int)(i & 7);
-    half8 v;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (_Float16)0.0f;
-    if (ch == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = (_Float16)(((2.0f * img[c * hw + p] - 1.0f) - kShift[c]) / kScale[c]);
-    }
-    *(half8*)(out + p * 64 + ch * 8) = v;
-}
-
-// the same with every channel as a pair: hi in channels 0..2, lo in 3..5 (conv1_1's weights are repeated there), 6..63 zero
-__global__ void __launch_bounds__(256) k_lpips_image_split(const float* __restrict__ img, long long hw, __half* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= hw * 8) return;
     const long long p = i >> 3;
     const int ch = (int)(i & 7);
@@ -61,7 +47,7 @@ __global__ void __launch_bounds__(256) k_lpips_image_split(const float* __restri
         for (int c = 0; c < 3; ++c) {
             const float f = ((2.0f * img[c * hw + p] - 1.0f) - kShift[c]) / kScale[c];
             v[c] = (_Float16)f;
-            v[3 + c] = (_Float16)(f - (float)v[c]);
+            if constexpr (SPLIT) v[3 + c] = (_Float16)(f - (float)v[c]);
         }
     }
     *(half8*)(out + p * 64 + ch * 8) = v;
@@ -75,27 +61,74 @@ __global__ void __launch_bounds__(256) k_lpips_image_bwd(const __half* __restric
     for (int c = 0; c < 3; ++c) d_img[c * hw + p] = __half2float(g[p * 64 + c]) * (2.0f / kScale[c]) * inv_scale;
 }
 
-// 2x2 / stride-2 max pooling on [H,W,C] -> [H/2,W/2,C] (floor, as nn.MaxPool2d(2,2))
+// The first maximum of a window in row-major order (torch's rule)
+__device__ __forceinline__ int first_max4(float va, float vb, float vc, float vd) {
+    int arg = 0;
+    float m = va;
+    if (vb > m) { m = vb; arg = 1; }
+    if (vc > m) { m = vc; arg = 2; }
+    if (vd > m) { m = vd; arg = 3; }
+    return arg;
+}
+
+// One 2x2 window of a map at 8 channels: hi[k] (and, SPLIT, lo[k]), k = the window's cell in row-major order
+template <bool SPLIT>
+struct Window {
+    half8 hi[4], lo[4];
+    // cell k at channel e as fp32 (the pair's sum is exact)
+    __device__ __forceinline__ float val(int k, int e) const {
+        if constexpr (SPLIT) return (float)hi[k][e] + (float)lo[k][e];
+        else return (float)hi[k][e];
+    }
+    __device__ __forceinline__ int first_max(int e) const { return first_max4(val(0, e), val(1, e), val(2, e), val(3, e)); }
+};
+
+// the window (yo, xo) of x [H,W,C] (SPLIT: of a split map [H,W,2C])
+template <bool SPLIT>
+__device__ __forceinline__ Window<SPLIT> load_window(const __half* __restrict__ x, int W, int C, int yo, int xo, int ch) {
+    const long long ld = SPLIT ? 2ll * C : C;
+    const __half* s = x + ((long long)(2 * yo) * W + 2 * xo) * ld + ch * 8;
+    Window<SPLIT> w;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const __half* c = s + ((k >> 1) ? (long long)W * ld : 0) + ((k & 1) ? ld : 0);
+        w.hi[k] = *(const half8*)c;
+        if constexpr (SPLIT) w.lo[k] = *(const half8*)(c + C);
+    }
+    return w;
+}
+
+// 2x2 / stride-2 max pooling on [H,W,C] -> [H/2,W/2,C] (floor, as nn.MaxPool2d(2,2)).  SPLIT: [H,W,2C] -> [H/2,W/2,2C], the cells
+// are compared as float(hi) + float(lo) and the winning PAIR is copied (ties in the sum: the first cell, as the backward below and torch)
+template <bool SPLIT>
 __global__ void __launch_bounds__(256) k_maxpool2(const __half* __restrict__ x, int H, int W, int C, __half* __restrict__ y) {
     const int Ho = H / 2, Wo = W / 2, C8 = C / 8;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)Ho * Wo * C8) return;
     const int ch = (int)(i % C8);
     const long long q = i / C8;
-    const int xo = (int)(q % Wo), yo = (int)(q / Wo);
-    const __half* s = x + ((long long)(2 * yo) * W + 2 * xo) * C + ch * 8;
-    const half8 a = *(const half8*)s, b = *(const half8*)(s + C), c = *(const half8*)(s + (long long)W * C), d = *(const half8*)(s + (long long)W * C + C);
-    half8 o;
+    const Window<SPLIT> w = load_window<SPLIT>(x, W, C, (int)(q / Wo), (int)(q % Wo), ch);
+    half8 oh, ol;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const float m = fmaxf(fmaxf((float)a[e], (float)b[e]), fmaxf((float)c[e], (float)d[e]));
-        o[e] = (_Float16)m;
+        if constexpr (SPLIT) {
+            const int arg = w.first_max(e);
+            oh[e] = arg == 0 ? w.hi[0][e] : (arg == 1 ? w.hi[1][e] : (arg == 2 ? w.hi[2][e] : w.hi[3][e]));
+            ol[e] = arg == 0 ? w.lo[0][e] : (arg == 1 ? w.lo[1][e] : (arg == 2 ? w.lo[2][e] : w.lo[3][e]));
+        } else {
+            // not a selection by first_max4: fmaxf differs from it on NaN and on signed zeros, and this entry's bits are public
+            oh[e] = (_Float16)fmaxf(fmaxf(w.val(0, e), w.val(1, e)), fmaxf(w.val(2, e), w.val(3, e)));
+        }
     }
-    *(half8*)(y + q * C + ch * 8) = o;
+    __half* d = y + q * (SPLIT ? 2 : 1) * C;
+    *(half8*)(d + ch * 8) = oh;
+    if constexpr (SPLIT) *(half8*)(d + C + ch * 8) = ol;
 }
 
 // its backward: the gradient of an output cell goes to the FIRST maximum of its window (row-major order, as torch); cells of
 // an odd last row / column receive zero.  gx is written in full (no accumulation: a pooled activation feeds nothing else).
+// gy [H/2,W/2,C] and gx [H,W,C] are plain fp16 gradients in both modes.
+template <bool SPLIT>
 __global__ void __launch_bounds__(256) k_maxpool2_bwd(const __half* __restrict__ x, const __half* __restrict__ gy, int H, int W, int C,
                                                      __half* __restrict__ gx) {
     const int Ho = H / 2, Wo = W / 2, C8 = C / 8;
@@ -109,91 +142,12 @@ __global__ void __launch_bounds__(256) k_maxpool2_bwd(const __half* __restrict__
     for (int e = 0; e < 8; ++e) o[e] = (_Float16)0.0f;
     const int yo = yi >> 1, xo = xi >> 1;
     if (yo < Ho && xo < Wo) {
-        const __half* s = x + ((long long)(2 * yo) * W + 2 * xo) * C + ch * 8;
-        const half8 a = *(const half8*)s, b = *(const half8*)(s + C), c = *(const half8*)(s + (long long)W * C), d = *(const half8*)(s + (long long)W * C + C);
+        const Window<SPLIT> w = load_window<SPLIT>(x, W, C, yo, xo, ch);
         const half8 g = *(const half8*)(gy + ((long long)yo * Wo + xo) * C + ch * 8);
         const int me = (yi & 1) * 2 + (xi & 1);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float va = (float)a[e], vb = (float)b[e], vc = (float)c[e], vd = (float)d[e];
-            int arg = 0;
-            float m = va;
-            if (vb > m) { m = vb; arg = 1; }
-            if (vc > m) { m = vc; arg = 2; }
-            if (vd > m) { m = vd; arg = 3; }
-            if (arg == me) o[e] = g[e];
-        }
-    }
-    *(half8*)(gx + q * C + ch * 8) = o;
-}
-
-// The first maximum of a window in row-major order (torch's rule; k_maxpool2_bwd above spells out the same comparisons)
-__device__ __forceinline__ int first_max4(float va, float vb, float vc, float vd) {
-    int arg = 0;
-    float m = va;
-    if (vb > m) { m = vb; arg = 1; }
-    if (vc > m) { m = vc; arg = 2; }
-    if (vd > m) { m = vd; arg = 3; }
-    return arg;
-}
-
-// the four pairs of a window of a split map x [H,W,2C] at 8 channels: hi[k], lo[k], k = the window's cell in row-major order
-__device__ __forceinline__ void load_window_split(const __half* __restrict__ x, int W, int C, int yo, int xo, int ch, half8 (&hi)[4], half8 (&lo)[4]) {
-    const long long ld = 2ll * C;
-    const __half* s = x + ((long long)(2 * yo) * W + 2 * xo) * ld + ch * 8;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const __half* c = s + ((k >> 1) ? (long long)W * ld : 0) + ((k & 1) ? ld : 0);
-        hi[k] = *(const half8*)c;
-        lo[k] = *(const half8*)(c + C);
-    }
-}
-
-// 2x2 max pooling of a split map [H,W,2C] -> [H/2,W/2,2C]: the cells are compared as float(hi) + float(lo) and the winning PAIR
-// is copied (ties in the sum: the first cell, as the backward below and torch)
-__global__ void __launch_bounds__(256) k_maxpool2_split(const __half* __restrict__ x, int H, int W, int C, __half* __restrict__ y) {
-    const int Ho = H / 2, Wo = W / 2, C8 = C / 8;
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long long)Ho * Wo * C8) return;
-    const int ch = (int)(i % C8);
-    const long long q = i / C8;
-    half8 hi[4], lo[4], oh, ol;
-    load_window_split(x, W, C, (int)(q / Wo), (int)(q % Wo), ch, hi, lo);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int arg = first_max4((float)hi[0][e] + (float)lo[0][e], (float)hi[1][e] + (float)lo[1][e], (float)hi[2][e] + (float)lo[2][e],
-                                   (float)hi[3][e] + (float)lo[3][e]);
-        oh[e] = arg == 0 ? hi[0][e] : (arg == 1 ? hi[1][e] : (arg == 2 ? hi[2][e] : hi[3][e]));
-        ol[e] = arg == 0 ? lo[0][e] : (arg == 1 ? lo[1][e] : (arg == 2 ? lo[2][e] : lo[3][e]));
-    }
-    *(half8*)(y + q * 2 * C + ch * 8) = oh;
-    *(half8*)(y + q * 2 * C + C + ch * 8) = ol;
-}
-
-// its backward: x the split input [H,W,2C], gy [H/2,W/2,C] and gx [H,W,C] plain fp16 gradients (k_maxpool2_bwd's rules)
-__global__ void __launch_bounds__(256) k_maxpool2_bwd_split(const __half* __restrict__ x, const __half* __restrict__ gy, int H, int W, int C,
-                                                           __half* __restrict__ gx) {
-    const int Ho = H / 2, Wo = W / 2, C8 = C / 8;
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long long)H * W * C8) return;
-    const int ch = (int)(i % C8);
-    const long long q = i / C8;
-    const int xi = (int)(q % W), yi = (int)(q / W);
-    half8 o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (_Float16)0.0f;
-    const int yo = yi >> 1, xo = xi >> 1;
-    if (yo < Ho && xo < Wo) {
-        half8 hi[4], lo[4];
-        load_window_split(x, W, C, yo, xo, ch, hi, lo);
-        const half8 g = *(const half8*)(gy + ((long long)yo * Wo + xo) * C + ch * 8);
-        const int me = (yi & 1) * 2 + (xi & 1);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int arg = first_max4((float)hi[0][e] + (float)lo[0][e], (float)hi[1][e] + (float)lo[1][e], (float)hi[2][e] + (float)lo[2][e],
-                                       (float)hi[3][e] + (float)lo[3][e]);
-            if (arg == me) o[e] = g[e];
-        }
+        for (int e = 0; e < 8; ++e)
+            if (w.first_max(e) == me) o[e] = g[e];
     }
     *(half8*)(gx + q * C + ch * 8) = o;
 }
@@ -352,14 +306,38 @@ int lpips_layer_bwd(const void* a, const void* b, const float* w, long long P, i
     return SYN3R_OK;
 }
 
+// The host side of the image and pooling entries (`who`: the entry's name in error messages)
+template <bool SPLIT>
+int lpips_image(const char* who, const float* img, int H, int W, void* out, void* stream_) {
+    SYN3R_REQUIRE(img && out && SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W), "%s: bad arguments H=%d W=%d", who, H, W);
+    const long long hw = (long long)H * W;
+    SYN3R_LAUNCH_NAMED(SPLIT ? "k_lpips_image_split" : "k_lpips_image", k_lpips_image<SPLIT>, dim3((unsigned)((hw * 8 + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream_, img, hw, (__half*)out);
+    return check_launch(who);
+}
+
+template <bool SPLIT>
+int maxpool2(const char* who, const void* x, int H, int W, int C, void* y, void* stream_) {
+    SYN3R_REQUIRE(x && y && SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W) && H >= 2 && W >= 2 && SYN3R_DIM_OK(C) && C % 8 == 0, "%s: bad arguments H=%d W=%d C=%d", who, H, W, C);
+    const long long n = (long long)(H / 2) * (W / 2) * (C / 8);
+    SYN3R_LAUNCH_NAMED(SPLIT ? "k_maxpool2_split" : "k_maxpool2", k_maxpool2<SPLIT>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_,
+                       (const __half*)x, H, W, C, (__half*)y);
+    return check_launch(who);
+}
+
+template <bool SPLIT>
+int maxpool2_bwd(const char* who, const void* x, const void* gy, int H, int W, int C, void* gx, void* stream_) {
+    SYN3R_REQUIRE(x && gy && gx && SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W) && H >= 2 && W >= 2 && SYN3R_DIM_OK(C) && C % 8 == 0, "%s: bad arguments", who);
+    const long long n = (long long)H * W * (C / 8);
+    SYN3R_LAUNCH_NAMED(SPLIT ? "k_maxpool2_bwd_split" : "k_maxpool2_bwd", k_maxpool2_bwd<SPLIT>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream_, (const __half*)x, (const __half*)gy, H, W, C, (__half*)gx);
+    return check_launch(who);
+}
+
 }  // namespace
 
 extern "C" int syn3r_lpips_image_f16(const float* img, int H, int W, void* out, void* stream_) {
-    SYN3R_REQUIRE(img && out && SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W), "lpips_image: bad arguments H=%d W=%d", H, W);
-    const long long hw = (long long)H * W;
-    SYN3R_LAUNCH(k_lpips_image, dim3((unsigned)((hw * 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, img, hw, (__half*)out);
-    SYN3R_LAUNCH_CHECK("lpips_image launch");
-    return SYN3R_OK;
+    return lpips_image<false>("lpips_image", img, H, W, out, stream_);
 }
 
 extern "C" int syn3r_lpips_image_bwd(const void* grad64, int H, int W, float loss_scale, float* d_img, void* stream_) {
@@ -372,20 +350,11 @@ extern "C" int syn3r_lpips_image_bwd(const void* grad64, int H, int W, float los
 }
 
 extern "C" int syn3r_maxpool2_f16(const void* x, int H, int W, int C, void* y, void* stream_) {
-    SYN3R_REQUIRE(x && y && SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W) && H >= 2 && W >= 2 && SYN3R_DIM_OK(C) && C % 8 == 0, "maxpool2: bad arguments H=%d W=%d C=%d", H, W, C);
-    const long long n = (long long)(H / 2) * (W / 2) * (C / 8);
-    SYN3R_LAUNCH(k_maxpool2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, (const __half*)x, H, W, C, (__half*)y);
-    SYN3R_LAUNCH_CHECK("maxpool2 launch");
-    return SYN3R_OK;
+    return maxpool2<false>("maxpool2", x, H, W, C, y, stream_);
 }
 
 extern "C" int syn3r_maxpool2_bwd_f16(const void* x, const void* gy, int H, int W, int C, void* gx, void* stream_) {
-    SYN3R_REQUIRE(x && gy && gx && SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W) && H >= 2 && W >= 2 && SYN3R_DIM_OK(C) && C % 8 == 0, "maxpool2_bwd: bad arguments");
-    const long long n = (long long)H * W * (C / 8);
-    SYN3R_LAUNCH(k_maxpool2_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, (const __half*)x, (const __half*)gy, H, W, C,
-                 (__half*)gx);
-    SYN3R_LAUNCH_CHECK("maxpool2_bwd launch");
-    return SYN3R_OK;
+    return maxpool2_bwd<false>("maxpool2_bwd", x, gy, H, W, C, gx, stream_);
 }
 
 extern "C" size_t syn3r_lpips_layer_workspace_bytes(long long P, int C) {
@@ -408,28 +377,15 @@ extern "C" int syn3r_lpips_layer_bwd_f16(const void* a, const void* b, const flo
 
 // ---- the split-activation entries: feature maps / activations are [.., 2C] pairs, gradients single fp16 tensors [.., C]
 extern "C" int syn3r_lpips_image_split_f16(const float* img, int H, int W, void* out, void* stream_) {
-    SYN3R_REQUIRE(img && out && SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W), "lpips_image_split: bad arguments H=%d W=%d", H, W);
-    const long long hw = (long long)H * W;
-    SYN3R_LAUNCH(k_lpips_image_split, dim3((unsigned)((hw * 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, img, hw, (__half*)out);
-    SYN3R_LAUNCH_CHECK("lpips_image_split launch");
-    return SYN3R_OK;
+    return lpips_image<true>("lpips_image_split", img, H, W, out, stream_);
 }
 
 extern "C" int syn3r_maxpool2_split_f16(const void* x, int H, int W, int C, void* y, void* stream_) {
-    SYN3R_REQUIRE(x && y && SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W) && H >= 2 && W >= 2 && SYN3R_DIM_OK(C) && C % 8 == 0, "maxpool2_split: bad arguments H=%d W=%d C=%d", H, W, C);
-    const long long n = (long long)(H / 2) * (W / 2) * (C / 8);
-    SYN3R_LAUNCH(k_maxpool2_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, (const __half*)x, H, W, C, (__half*)y);
-    SYN3R_LAUNCH_CHECK("maxpool2_split launch");
-    return SYN3R_OK;
+    return maxpool2<true>("maxpool2_split", x, H, W, C, y, stream_);
 }
 
 extern "C" int syn3r_maxpool2_bwd_split_f16(const void* x, const void* gy, int H, int W, int C, void* gx, void* stream_) {
-    SYN3R_REQUIRE(x && gy && gx && SYN3R_SIDE_OK(H) && SYN3R_SIDE_OK(W) && H >= 2 && W >= 2 && SYN3R_DIM_OK(C) && C % 8 == 0, "maxpool2_bwd_split: bad arguments");
-    const long long n = (long long)H * W * (C / 8);
-    SYN3R_LAUNCH(k_maxpool2_bwd_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, (const __half*)x, (const __half*)gy, H, W, C,
-                 (__half*)gx);
-    SYN3R_LAUNCH_CHECK("maxpool2_bwd_split launch");
-    return SYN3R_OK;
+    return maxpool2_bwd<true>("maxpool2_bwd_split", x, gy, H, W, C, gx, stream_);
 }
 
 extern "C" int syn3r_lpips_layer_split_f16(const void* a, const void* b, const float* w, long long P, int C, int accumulate, float* value,

@@ -23,7 +23,8 @@ both modes.
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional, Tuple
+from collections import namedtuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -42,17 +43,25 @@ _SLICES: Tuple[Tuple[Tuple[int, int, int], ...], ...] = (
 _CHNS = (64, 128, 256, 512, 512)
 
 
-PRECISIONS = ("fp16", "fp16x2")
+# The ABI entries of a precision, and `width`: the fp16 per channel of a stored forward activation (2: pairs [H*W, 2C], hi plane | lo plane)
+_Entries = namedtuple("_Entries", "image pool pool_bwd layer layer_bwd width")
+_ENTRIES = {
+    "fp16": _Entries("syn3r_lpips_image_f16", "syn3r_maxpool2_f16", "syn3r_maxpool2_bwd_f16", "syn3r_lpips_layer_f16", "syn3r_lpips_layer_bwd_f16", 1),
+    "fp16x2": _Entries("syn3r_lpips_image_split_f16", "syn3r_maxpool2_split_f16", "syn3r_maxpool2_bwd_split_f16", "syn3r_lpips_layer_split_f16",
+                       "syn3r_lpips_layer_bwd_split_f16", 2),
+}
+PRECISIONS = tuple(_ENTRIES)
+
+
+def _call(entry: str, *args) -> None:
+    L.check(getattr(L.load(), entry)(*args), entry)       # a failure is reported under the entry's own name
 
 
 def _conv(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], Hh: int, Ww: int, relu: bool, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [H*W, Cin] fp16, w [Cout,3,3,Cin] -> [H*W, Cout] (syn3r_conv2d3x3_act_f16)."""
-    dev = x.device
     Cin, Cout = x.shape[1], w.shape[0]
-    out = torch.empty((Hh * Ww, Cout), dtype=H16, device=dev)
-    rc = L.load().syn3r_conv2d3x3_act_f16(L.ptr(x), L.ptr(w), L.ptr(out), L.ptr(b), 1 if relu else 0, L.ptr(mask), 1, Hh, Ww, Cin, Cout,
-                                          L.stream_ptr(dev))
-    L.check(rc, "syn3r_conv2d3x3_act_f16")
+    out = torch.empty((Hh * Ww, Cout), dtype=H16, device=x.device)
+    _call("syn3r_conv2d3x3_act_f16", L.ptr(x), L.ptr(w), L.ptr(out), L.ptr(b), 1 if relu else 0, L.ptr(mask), 1, Hh, Ww, Cin, Cout, L.stream_ptr(x.device))
     return out
 
 
@@ -61,13 +70,11 @@ def _conv_split(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], Hh:
     """syn3r_conv2d3x3_split_f16.  Forward (`split_out`): x a split map [H*W, 2 Cin] (or the image tensor [H*W, 64]), w the
     duplicated weights [Cout,3,3,x.shape[1]] -> the split map [H*W, 2 Cout].  Backward-data: x a gradient [H*W, Cout], w the
     transposed, flipped weights -> the gradient [H*W, Cin], zeroed where the hi plane of the split map `mask` [H*W, 2 Cin] is <= 0."""
-    dev = x.device
     Cin, Cout = x.shape[1], w.shape[0]
     ld_out = 2 * Cout if split_out else Cout
-    out = torch.empty((Hh * Ww, ld_out), dtype=H16, device=dev)
-    rc = L.load().syn3r_conv2d3x3_split_f16(L.ptr(x), L.ptr(w), L.ptr(out), ld_out, L.ptr(b), 1 if relu else 0, 1 if split_out else 0, L.ptr(mask),
-                                            mask.shape[1] if mask is not None else 0, 1, Hh, Ww, Cin, Cout, L.stream_ptr(dev))
-    L.check(rc, "syn3r_conv2d3x3_split_f16")
+    out = torch.empty((Hh * Ww, ld_out), dtype=H16, device=x.device)
+    _call("syn3r_conv2d3x3_split_f16", L.ptr(x), L.ptr(w), L.ptr(out), ld_out, L.ptr(b), 1 if relu else 0, 1 if split_out else 0, L.ptr(mask),
+          mask.shape[1] if mask is not None else 0, 1, Hh, Ww, Cin, Cout, L.stream_ptr(x.device))
     return out
 
 
@@ -81,7 +88,8 @@ class LPIPS:
         if precision not in PRECISIONS:
             raise ValueError(f"LPIPS: precision must be one of {PRECISIONS}, got {precision!r}")
         self.precision = precision
-        self.split = precision == "fp16x2"      # forward activations as fp16 pairs [H*W, 2C] (hi plane | lo plane)
+        self.entries = _ENTRIES[precision]
+        self.split = self.entries.width == 2
         self.shapes: Dict[str, Tuple[int, ...]] = {}
         for s, convs in enumerate(_SLICES):
             for idx, cin, cout in convs:
@@ -150,17 +158,22 @@ class LPIPS:
         return self.load_state_dict(sd, device)
 
     # ------------------------------------------------------------------ forward pieces
+    def _convolve(self, x, w, b, h: int, w_: int, forward: bool, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Every convolution of the model: forward (bias, ReLU) or backward-data (`mask`: the activation below, if it has a ReLU).
+        Split mode: a forward call writes pairs and a masked backward-data call reads its mask as the hi plane of a split map (row
+        stride 2 Cin), both on the split entry; an unmasked backward-data call has nothing split about it: the plain entry."""
+        if self.split and (forward or mask is not None):
+            return _conv_split(x, w, b, h, w_, relu=forward, split_out=forward, mask=mask)
+        return _conv(x, w, b, h, w_, relu=forward, mask=mask)
+
     def _features(self, img: torch.Tensor, keep: bool):
         """img [3,H,W] fp32 in [0,1] on the device -> the five feature maps [(H_k*W_k, C_k)] (+ every post-ReLU activation and
         the pooled inputs when `keep`, for the backward)."""
         dev = img.device
-        lib = L.load()
+        e = self.entries
         _, Hh, Ww = img.shape
         x = torch.empty((Hh * Ww, 64), dtype=H16, device=dev)
-        if self.split:
-            L.check(lib.syn3r_lpips_image_split_f16(L.ptr(img), Hh, Ww, L.ptr(x), L.stream_ptr(dev)), "syn3r_lpips_image_split_f16")
-        else:
-            L.check(lib.syn3r_lpips_image_f16(L.ptr(img), Hh, Ww, L.ptr(x), L.stream_ptr(dev)), "syn3r_lpips_image_f16")
+        _call(e.image, L.ptr(img), Hh, Ww, L.ptr(x), L.stream_ptr(dev))
         feats, acts, dims = [], [], []
         h, w_ = Hh, Ww
         for s, convs in enumerate(self.fwd):
@@ -168,15 +181,12 @@ class LPIPS:
                 if h < 2 or w_ < 2:
                     raise ValueError("LPIPS: image too small for the five VGG stages (needs >= 16 pixels per side)")
                 y = torch.empty(((h // 2) * (w_ // 2), x.shape[1]), dtype=H16, device=dev)
-                if self.split:
-                    L.check(lib.syn3r_maxpool2_split_f16(L.ptr(x), h, w_, x.shape[1] // 2, L.ptr(y), L.stream_ptr(dev)), "syn3r_maxpool2_split_f16")
-                else:
-                    L.check(lib.syn3r_maxpool2_f16(L.ptr(x), h, w_, x.shape[1], L.ptr(y), L.stream_ptr(dev)), "syn3r_maxpool2_f16")
+                _call(e.pool, L.ptr(x), h, w_, x.shape[1] // e.width, L.ptr(y), L.stream_ptr(dev))
                 h, w_ = h // 2, w_ // 2
                 x = y
             layer_acts = [x]                       # input of the slice (the image tensor or the pooled map)
             for wf, b in convs:
-                x = _conv_split(x, wf, b, h, w_, relu=True, split_out=True) if self.split else _conv(x, wf, b, h, w_, relu=True)
+                x = self._convolve(x, wf, b, h, w_, forward=True)
                 layer_acts.append(x)
             feats.append(x)
             dims.append((h, w_))
@@ -210,18 +220,15 @@ class _LpipsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target, model: LPIPS):
         dev = pred.device
-        lib = L.load()
         x = pred.detach().to(torch.float32).contiguous()
         feats, acts, dims = model._features(x, keep=True)
         tfeats = model._target_features(target)
         value = torch.zeros(1, dtype=torch.float32, device=dev)
         for k in range(5):
             P, C = feats[k].shape[0], _CHNS[k]
-            ws = L.workspace(dev, lib.syn3r_lpips_layer_workspace_bytes(P, C), "lpips")
-            layer = lib.syn3r_lpips_layer_split_f16 if model.split else lib.syn3r_lpips_layer_f16
-            rc = layer(L.ptr(feats[k]), L.ptr(tfeats[k]), L.ptr(model.lin[k]), P, C, 1 if k else 0, L.ptr(value), L.ptr(ws), ws.numel(),
-                       L.stream_ptr(dev))
-            L.check(rc, "syn3r_lpips_layer_split_f16" if model.split else "syn3r_lpips_layer_f16")
+            ws = L.workspace(dev, L.load().syn3r_lpips_layer_workspace_bytes(P, C), "lpips")
+            _call(model.entries.layer, L.ptr(feats[k]), L.ptr(tfeats[k]), L.ptr(model.lin[k]), P, C, 1 if k else 0, L.ptr(value), L.ptr(ws),
+                  ws.numel(), L.stream_ptr(dev))
         ctx.model, ctx.acts, ctx.dims, ctx.tfeats = model, acts, dims, tfeats
         ctx.shape = tuple(pred.shape)
         return value[0]
@@ -230,7 +237,6 @@ class _LpipsFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         L.join_active_trace()
         model, acts, dims, tfeats = ctx.model, ctx.acts, ctx.dims, ctx.tfeats
-        lib = L.load()
         _, Hh, Ww = ctx.shape
         dev = acts[0][0].device
         scale = model.LOSS_SCALE_PER_PIXEL * Hh * Ww
@@ -244,9 +250,7 @@ class _LpipsFn(torch.autograd.Function):
                 acc = 0
             else:
                 acc = 1
-            layer_bwd = lib.syn3r_lpips_layer_bwd_split_f16 if model.split else lib.syn3r_lpips_layer_bwd_f16
-            rc = layer_bwd(L.ptr(feat), L.ptr(tfeats[k]), L.ptr(model.lin[k]), P, C, up * scale, acc, L.ptr(g), L.stream_ptr(dev))
-            L.check(rc, "syn3r_lpips_layer_bwd_split_f16" if model.split else "syn3r_lpips_layer_bwd_f16")
+            _call(model.entries.layer_bwd, L.ptr(feat), L.ptr(tfeats[k]), L.ptr(model.lin[k]), P, C, up * scale, acc, L.ptr(g), L.stream_ptr(dev))
             h, w_ = dims[k]
             # back through the slice's convolutions: g is d/d(post-ReLU output of conv n) -> mask by (output > 0) -> backward-data
             # convolution -> d/d(input of conv n) = d/d(post-ReLU output of conv n-1), whose own mask is applied in the epilogue
@@ -255,18 +259,13 @@ class _LpipsFn(torch.autograd.Function):
             for n in range(nconv - 1, -1, -1):
                 below = acts[k][n]                     # input of conv n (post-ReLU of conv n-1, or the slice input)
                 mask = below if n > 0 else None        # the slice input is a pooled map / the image tensor: no ReLU of its own
-                if model.split and mask is not None:   # the mask is the hi plane of the split map (row stride 2 Cin)
-                    g = _conv_split(g, model.bwd[k][n], None, h, w_, relu=False, split_out=False, mask=mask)
-                else:
-                    g = _conv(g, model.bwd[k][n], None, h, w_, relu=False, mask=mask)
+                g = model._convolve(g, model.bwd[k][n], None, h, w_, forward=False, mask=mask)
             if k > 0:                                  # through the max-pool into the previous slice's output
                 ph, pw = dims[k - 1]
                 prev = acts[k - 1][-1]
                 gp = torch.empty((ph * pw, _CHNS[k - 1]), dtype=H16, device=dev)
-                pool_bwd = lib.syn3r_maxpool2_bwd_split_f16 if model.split else lib.syn3r_maxpool2_bwd_f16
-                rc = pool_bwd(L.ptr(prev), L.ptr(g), ph, pw, _CHNS[k - 1], L.ptr(gp), L.stream_ptr(dev))
-                L.check(rc, "syn3r_maxpool2_bwd_split_f16" if model.split else "syn3r_maxpool2_bwd_f16")
+                _call(model.entries.pool_bwd, L.ptr(prev), L.ptr(g), ph, pw, _CHNS[k - 1], L.ptr(gp), L.stream_ptr(dev))
                 g = gp                                 # the previous slice's layer term is ADDED to it at the top of the loop
         d_img = torch.empty((3, Hh, Ww), dtype=torch.float32, device=dev)
-        L.check(lib.syn3r_lpips_image_bwd(L.ptr(g), Hh, Ww, float(scale), L.ptr(d_img), L.stream_ptr(dev)), "syn3r_lpips_image_bwd")
+        _call("syn3r_lpips_image_bwd", L.ptr(g), Hh, Ww, float(scale), L.ptr(d_img), L.stream_ptr(dev))
         return d_img * grad_out.to(torch.float32), None, None

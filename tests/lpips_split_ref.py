@@ -1,6 +1,7 @@
 """TEST INFRASTRUCTURE - what tests/test_lpips_split_cpu.py and tests/test_lpips_split_gpu.py share: the seeded weights and images
 of tests/test_lpips_gpu.py::test_lpips_value_and_gradient_vs_oracle, and a float64 restatement of oracle/lpips_oracle.py into which
-the individual roundings of the HIP path can be inserted (`emulate`)."""
+the individual roundings of the HIP path can be inserted (`emulate`); tests/test_lpips_gpu.py takes its images, weights and trainer
+setup from here too."""
 import math
 
 import torch
@@ -37,6 +38,27 @@ def seeded_state_dict(shapes, seed=3):
 def parameter_shapes():
     from syn3r_amd.gs.lpips import LPIPS
     return LPIPS().parameter_shapes()
+
+
+def trainer_with_lpips(gpu, precision):
+    """The trainer-step tests' setup: 600 Gaussians seen by one 48 x 64 camera whose image is their own render, a GSTrainer on a
+    perturbed copy (lpips_weight 1, the term still switched off) with a seeded LPIPS of `precision` attached -> (trainer, camera)."""
+    import numpy as np
+    from oracle import raster_oracle as RO
+    from syn3r_amd.gs import Camera, GaussianModel, GSTrainer, OptimizationParams
+    from syn3r_amd.gs.lpips import LPIPS
+    N, H, W = 600, 48, 64
+    mm, s, q, o, sh = RO.synthetic_gaussians(N, seed=2, log_scale_mean=np.log(0.08))
+    logit = torch.log(o.clamp(1e-3, 1 - 1e-3) / (1 - o.clamp(1e-3, 1 - 1e-3)))
+    f = W / (2 * math.tan(math.radians(30)))
+    K = np.array([[f, 0, W / 2], [0, f, H / 2], [0, 0, 1]], dtype=np.float32)
+    gt = GSTrainer(GaussianModel(mm, torch.log(s), q, logit, sh, device=gpu), [Camera.from_w2c(np.eye(4, dtype=np.float32), K, H, W, data_device=gpu)])
+    img = gt.render_view(gt.scene.getTrainCameras()[0])["render"].detach().clamp(0, 1)
+    cam = Camera.from_w2c(np.eye(4, dtype=np.float32), K, H, W, image=img, data_device=gpu)
+    gm = GaussianModel(mm + 0.02 * torch.randn_like(mm), torch.log(s), q, logit, sh, device=gpu)
+    tr = GSTrainer(gm, [cam], OptimizationParams(iterations=3, lpips_weight=1.0))
+    tr.lpips = LPIPS(precision=precision).init_random(gpu, seed=1)
+    return tr, cam
 
 
 def round_fp16(x):

@@ -1,38 +1,28 @@
 """LPIPS (VGG16) loss term on the HIP path against the torch oracle (oracle/lpips_oracle.py): value and
-gradient wrt the rendered image, shared seeded weights; PARITY UNPINNED (the `lpips` package and its weights are absent)."""
+gradient wrt the rendered image, shared seeded weights; PARITY UNPINNED (the `lpips` package and its weights are absent).  And the
+pooling and image kernels of csrc/lpips.hip one by one (the pooling of a split map: tests/test_lpips_split_gpu.py)."""
+import sys
+from pathlib import Path
+
 import numpy as np
 import pytest
 import torch
 
-from oracle import lpips_oracle as LO
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+
+import lpips_split_ref as R  # noqa: E402
+from oracle import lpips_oracle as LO  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-def _images(H, W, seed):
-    g = torch.Generator().manual_seed(seed)
-    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
-    base = torch.stack([0.5 + 0.4 * torch.sin(xs / 7 + c) * torch.cos(ys / 5 - c) for c in range(3)])
-    a = (base + 0.08 * torch.randn(3, H, W, generator=g)).clamp(0, 1)
-    b = (base.roll(2, 2) + 0.08 * torch.randn(3, H, W, generator=g)).clamp(0, 1)
-    return a, b
+H16 = torch.float16
 
 
 @pytest.mark.parametrize("H,W", [(64, 96), (50, 70), (136, 240)])
 def test_lpips_value_and_gradient_vs_oracle(gpu, H, W, measurements):
     from syn3r_amd.gs.lpips import LPIPS
     m = LPIPS().init_random(gpu, seed=3)
-    sd = {}
-    g = torch.Generator().manual_seed(3)                      # the same draws as init_random
-    import math
-    for k, shape in m.parameter_shapes().items():
-        if k.startswith("lin"):
-            sd[k] = torch.rand(shape, generator=g) * 0.2 + 0.01
-        elif k.endswith(".bias"):
-            sd[k] = 0.05 * torch.randn(shape, generator=g)
-        else:
-            sd[k] = torch.randn(shape, generator=g) * math.sqrt(2.0 / (shape[1] * 9))
-    a, b = _images(H, W, H)
+    sd = R.seeded_state_dict(m.parameter_shapes(), seed=3)    # the same draws as init_random
+    a, b = R.images(H, W, H)
     pred = a.to(gpu).requires_grad_(True)
     target = b.to(gpu)
     loss = m(pred, target)
@@ -77,21 +67,7 @@ def test_lpips_state_dict_names_and_errors(gpu):
 def test_trainer_uses_lpips_when_switched_on(gpu, tmp_path):
     """`opt.use_lpips_loss` (raised by DiffusionGS.run around refine_GS) x `opt.lpips_weight`: the term enters train_step and
     evaluate() reports the metric; off -> the loss is the photometric one alone."""
-    import math
-    from oracle import raster_oracle as RO
-    from syn3r_amd.gs import Camera, GaussianModel, GSTrainer, OptimizationParams
-    from syn3r_amd.gs.lpips import LPIPS
-    N, H, W = 600, 48, 64
-    mm, s, q, o, sh = RO.synthetic_gaussians(N, seed=2, log_scale_mean=np.log(0.08))
-    logit = torch.log(o.clamp(1e-3, 1 - 1e-3) / (1 - o.clamp(1e-3, 1 - 1e-3)))
-    f = W / (2 * math.tan(math.radians(30)))
-    K = np.array([[f, 0, W / 2], [0, f, H / 2], [0, 0, 1]], dtype=np.float32)
-    gt = GSTrainer(GaussianModel(mm, torch.log(s), q, logit, sh, device=gpu), [Camera.from_w2c(np.eye(4, dtype=np.float32), K, H, W, data_device=gpu)])
-    img = gt.render_view(gt.scene.getTrainCameras()[0])["render"].detach().clamp(0, 1)
-    cam = Camera.from_w2c(np.eye(4, dtype=np.float32), K, H, W, image=img, data_device=gpu)
-    gm = GaussianModel(mm + 0.02 * torch.randn_like(mm), torch.log(s), q, logit, sh, device=gpu)
-    tr = GSTrainer(gm, [cam], OptimizationParams(iterations=3, lpips_weight=1.0))
-    tr.lpips = LPIPS().init_random(gpu, seed=1)
+    tr, cam = R.trainer_with_lpips(gpu, "fp16")
     base = float(tr.train_step(cam))
     tr.opt.use_lpips_loss = True
     with_term = float(tr.train_step(cam))
@@ -130,3 +106,56 @@ def test_lpips_layer_backward_saturates_instead_of_overflowing(gpu):
     torch.cuda.synchronize()
     gf = grad.float()
     assert bool(torch.isfinite(gf).all()) and float(gf.abs().max()) == 65504.0
+
+
+@pytest.mark.parametrize("H,W,C", [(9, 14, 64), (5, 3, 8)])
+def test_maxpool_and_backward_exact_with_ties(gpu, H, W, C):
+    """syn3r_maxpool2_f16 / syn3r_maxpool2_bwd_f16 per element against torch on values of the quarter grid (fp16 and fp32 hold them
+    exactly, ties are common): the odd last row / column is dropped by the forward and zeroed by the backward, the gradient of a
+    tied window goes to its first cell, and the backward writes every cell (gx enters as 7).  5 x 3 x 8: one 8-channel chunk."""
+    from syn3r_amd import _lib as L
+    lib = L.load()
+    Ho, Wo = H // 2, W // 2
+    g = torch.Generator().manual_seed(12)                 # (a seed at which the 16 windows of the small case have their share of ties too)
+    v = torch.randint(0, 6, (H, W, C), generator=g).float() * 0.25
+    win = v[:2 * Ho, :2 * Wo].reshape(Ho, 2, Wo, 2, C)
+    n_max = (win.amax(dim=(1, 3), keepdim=True) == win).sum(dim=(1, 3)).float()
+    assert float(n_max.max()) >= 2 and float(n_max.mean()) > 1.25                # tied windows exist and are common
+    x = v.reshape(-1, C).half().to(gpu)
+    y = torch.full((Ho * Wo, C), 7.0, dtype=H16, device=gpu)
+    L.check(lib.syn3r_maxpool2_f16(L.ptr(x), H, W, C, L.ptr(y), L.stream_ptr(gpu)), "maxpool2")
+    vt = v.permute(2, 0, 1)[None].clone().requires_grad_(True)                   # [1, C, H, W] fp32
+    ref = torch.nn.functional.max_pool2d(vt, 2, 2)
+    assert torch.equal(y.cpu().float().reshape(Ho, Wo, C).permute(2, 0, 1)[None], ref.detach())
+    gy = torch.randn(Ho * Wo, C, generator=g).half()
+    ref.backward(gy.float().reshape(Ho, Wo, C).permute(2, 0, 1)[None])
+    gx, gyd = torch.full((H * W, C), 7.0, dtype=H16, device=gpu), gy.to(gpu)
+    L.check(lib.syn3r_maxpool2_bwd_f16(L.ptr(x), L.ptr(gyd), H, W, C, L.ptr(gx), L.stream_ptr(gpu)), "maxpool2_bwd")
+    assert torch.equal(gx.cpu().float().reshape(H, W, C), vt.grad[0].permute(1, 2, 0))
+
+
+@pytest.mark.parametrize("H,W", [(5, 7), (16, 16)])
+def test_image_kernels_zero_fill_and_pair_value(gpu, H, W, measurements):
+    """syn3r_lpips_image_f16 / syn3r_lpips_image_split_f16 on a uniform random image that holds the pixels 0 and 1 (5 x 7: two
+    blocks, the second partial).  The padding channels are exactly zero (the outputs enter as 7), the hi plane of the split entry
+    is the plain entry's output, and the pair float(hi) + float(lo) lies within 2^-20 absolute of ((2x - 1) - shift) / scale in
+    float64 on the fp32-rounded constants: three fp32 operations on |f| < 2.7 give at most ~2^-21, the fp16 rounding of a remainder
+    of at most 2^-9.5 at most 2^-20.5 - under 2^-19.5 together; a float32 / float16 emulation of the kernel's arithmetic on 2M
+    pixels reaches 2^-20.96 at worst, the bar is twice that."""
+    from syn3r_amd import _lib as L
+    lib = L.load()
+    img = torch.rand(3, H, W, generator=torch.Generator().manual_seed(13))
+    img[:, 0, 0], img[:, 0, 1] = 0.0, 1.0
+    x = img.to(gpu)
+    plain = torch.full((H * W, 64), 7.0, dtype=H16, device=gpu)
+    split = torch.full((H * W, 64), 7.0, dtype=H16, device=gpu)
+    L.check(lib.syn3r_lpips_image_f16(L.ptr(x), H, W, L.ptr(plain), L.stream_ptr(gpu)), "lpips_image")
+    L.check(lib.syn3r_lpips_image_split_f16(L.ptr(x), H, W, L.ptr(split), L.stream_ptr(gpu)), "lpips_image_split")
+    p, s = plain.cpu(), split.cpu()
+    assert bool((p[:, 3:] == 0).all())
+    assert bool((s[:, 6:] == 0).all()) and torch.equal(s[:, :3], p[:, :3])
+    ref = ((2 * img.double()[None] - 1) - LO.SHIFT.double()) / LO.SCALE.double()          # fp32 constants, as the kernel's
+    err = float((s[:, :3].double() + s[:, 3:6].double() - ref[0].reshape(3, H * W).T).abs().max())
+    measurements(f"lpips:image_pair:{H}x{W}", max_abs=err)
+    print(f"lpips image pair {H}x{W}: max abs error {err:.3e} (2^{np.log2(max(err, 1e-300)):.2f})")
+    assert err <= 2.0 ** -20, err

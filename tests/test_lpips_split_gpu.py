@@ -224,20 +224,7 @@ def test_split_backward_data_convolution_masks_by_the_hi_plane(gpu):
 
 def test_trainer_step_with_split_lpips(gpu):
     """One GSTrainer.train_step with a split-mode LPIPS attached: finite loss, the term is in it, the parameters move."""
-    from oracle import raster_oracle as RO
-    from syn3r_amd.gs import Camera, GaussianModel, GSTrainer, OptimizationParams
-    from syn3r_amd.gs.lpips import LPIPS
-    N, Hh, Ww = 600, 48, 64
-    mm, s, q, o, sh = RO.synthetic_gaussians(N, seed=2, log_scale_mean=np.log(0.08))
-    logit = torch.log(o.clamp(1e-3, 1 - 1e-3) / (1 - o.clamp(1e-3, 1 - 1e-3)))
-    f = Ww / (2 * math.tan(math.radians(30)))
-    K = np.array([[f, 0, Ww / 2], [0, f, Hh / 2], [0, 0, 1]], dtype=np.float32)
-    gt = GSTrainer(GaussianModel(mm, torch.log(s), q, logit, sh, device=gpu), [Camera.from_w2c(np.eye(4, dtype=np.float32), K, Hh, Ww, data_device=gpu)])
-    img = gt.render_view(gt.scene.getTrainCameras()[0])["render"].detach().clamp(0, 1)
-    cam = Camera.from_w2c(np.eye(4, dtype=np.float32), K, Hh, Ww, image=img, data_device=gpu)
-    gm = GaussianModel(mm + 0.02 * torch.randn_like(mm), torch.log(s), q, logit, sh, device=gpu)
-    tr = GSTrainer(gm, [cam], OptimizationParams(iterations=3, lpips_weight=1.0))
-    tr.lpips = LPIPS(precision="fp16x2").init_random(gpu, seed=1)
+    tr, cam = R.trainer_with_lpips(gpu, "fp16x2")
     base = float(tr.train_step(cam))
     tr.opt.use_lpips_loss = True
     before = tr.gaussians.get_xyz.detach().clone()

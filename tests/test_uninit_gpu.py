@@ -773,7 +773,7 @@ def test_lpips_rows(precision, gpu, monkeypatch):
     def run(dev):
         from syn3r_amd.gs.lpips import LPIPS
         m = LPIPS(precision=precision).init_random(dev, seed=3)
-        a, b = TL._images(H, W, H)
+        a, b = TLS.R.images(H, W, H)
         pred = a.to(dev).requires_grad_(True)
         loss = m(pred, b.to(dev))
         (3.0 * loss).backward()
